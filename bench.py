@@ -26,6 +26,8 @@ the contractual algorithmic bytes A(N,G) of SURVEY.md 8(d); `cpu_baseline` (the 
 oracle/) times the CPU oracle (a port of the reference's PyTorch CPU path) on a bounded sample on this host.  Beside `value`,
 never as it: `step_us` (median of short windows), `hip_graph_replay`, `two_batches_in_flight`, `forward_only_us`, and the
 reference's own call sequence through the drop-in signatures, eager (`plain_eager`) and replayed (`plain_graph_replay`).
+`--dump-outputs DIR` writes what the last timed step computed (loss, silhouettes, gradients; the full training step:
+loss and parameters) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -145,6 +147,33 @@ def synthetic_inputs(b, n, g, seed):
 
 def make_inputs(device, seed):
     return [x.to(device=device, dtype=torch.float32) for x in synthetic_inputs(B, N_PTS, G, seed)]
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs: at most this much in all (every rank's files together, .npy headers included)
+
+
+def dump_sample_index(numel, n):
+    """The flat positions an output of `numel` elements keeps when only `n` of them fit: fixed by a seeded generator, so
+    that two runs, or two builds, write the same positions; ascending."""
+    return torch.randperm(numel, generator=torch.Generator().manual_seed(20240515))[:n].sort().values
+
+
+def dump_outputs(directory, arrays, rank, world):
+    """--dump-outputs: write `arrays` (name -> tensor, what the timed path computed in its last step) flattened as float32
+    <directory>/<name>.npy (rank r > 0: rank<r>_<name>.npy).  When they hold more than this rank's share of DUMP_BYTES,
+    every array keeps the same fraction of its elements, at the positions dump_sample_index(numel, kept) names."""
+    import numpy as np
+
+    arrays = {k: v.detach().reshape(-1).float().cpu() for k, v in arrays.items() if v is not None}
+    budget = DUMP_BYTES // world - 128 * len(arrays)   # 128 bytes of .npy header per file
+    total = 4 * sum(v.numel() for v in arrays.values())
+    keep = 1.0 if total <= budget else budget / total
+    os.makedirs(directory, exist_ok=True)
+    prefix = "" if rank == 0 else "rank%d_" % rank
+    for name, flat in sorted(arrays.items()):
+        if keep < 1.0 and flat.numel() > 1:
+            flat = flat[dump_sample_index(flat.numel(), max(1, int(flat.numel() * keep)))]
+        np.save(os.path.join(directory, prefix + name + ".npy"), flat.numpy())
 
 
 def cpu_baseline():
@@ -287,6 +316,9 @@ def full_step_main(args, rank, world, local):
         dist.barrier()
     torch.cuda.synchronize(device)
     wall = time.perf_counter() - t0
+    if args.dump_outputs:   # what the last timed step leaves a caller: its loss and the parameters after the update
+        dump_outputs(args.dump_outputs, {"loss": loss, "parameters": torch.cat([p.detach().reshape(-1) for p in trainer.nets.parameters()])},
+                     rank, world)
     times = torch.tensor([wall, mine], device=device, dtype=torch.float64)
     per_rank = [times.clone() for _ in range(world)]
     if dist_on:
@@ -364,12 +396,17 @@ def main():
                          "line); plain: the reference's own call sequence, pointcloud_project_fast then the loss in torch")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="multi-rank rehearsal on a single-GPU box: every rank uses cuda:0 and the collectives run over gloo")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (loss, silhouettes, "
+                         "gradients; the full step: loss and parameters) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--rccl-at-one-rank", action="store_true",
                     help="with one rank under torch.distributed.run: initialise RCCL anyway and run the barriers and all-reduces "
                          "of the N-rank line (what a one-GPU box can execute of the --gpus N code)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args))   # this process never touches a GPU: the N ranks are its children
     global B, N_PTS, G, SIGMA_REL, K_CAND
@@ -429,35 +466,41 @@ def main():
                for x in (pc, q, s, gt)] for i in range(ns)]
     extra = [torch.cuda.Stream(device) for _ in range(ns - 1)]
     share = torch.full((), 1.0 / ns, device=device)
+    held = {}   # what the last call of step() returned beside the loss (read by --dump-outputs)
 
     def step():
         # projection + sum((proj-gt)^2)/B in one autograd node (loss folded into the ray-march kernels)
         if ns == 1 and args.api == "plain":  # what ModelPointCloud does: compute_projection, then add_proj_loss in torch
             pc.grad = q.grad = s.grad = None
             proj = R.pointcloud_project_fast(cfg, pc, q, None, None, kern, scaling_factor=s)["proj"]
+            winner = None
             if K_CAND > 1:
-                loss, _ = R.silhouette_loss(proj, gt, K_CAND)
+                loss, winner = R.silhouette_loss(proj, gt, K_CAND)
             else:
                 loss = ((proj - gt) ** 2).sum() / B
             loss.backward(gradient=one)
+            held.update(proj=proj, winner=winner)
             return loss
         if ns == 1:
             pc.grad = q.grad = s.grad = None
-            loss, _, _ = R.pointcloud_project_loss(cfg, pc, q, None, None, kern, scaling_factor=s, gt=gt, num_candidates=K_CAND)
+            loss, out, winner = R.pointcloud_project_loss(cfg, pc, q, None, None, kern, scaling_factor=s, gt=gt, num_candidates=K_CAND)
             loss.backward(gradient=one)  # preallocated d(loss)=1: no ones-fill launch per step
+            held.update(proj=out["proj"], winner=winner if K_CAND > 1 else None)
             return loss
         main = torch.cuda.current_stream(device)
-        losses = []
+        losses, projs = [], []
         for i, (spc, sq, ss, sgt) in enumerate(shards):
             st = main if i == 0 else extra[i - 1]
             st.wait_stream(main)
             with torch.cuda.stream(st):
                 spc.grad = sq.grad = ss.grad = None
-                l, _, _ = R.pointcloud_project_loss(cfg, spc, sq, None, None, kern, scaling_factor=ss, gt=sgt, num_candidates=K_CAND)
+                l, out, _ = R.pointcloud_project_loss(cfg, spc, sq, None, None, kern, scaling_factor=ss, gt=sgt, num_candidates=K_CAND)
                 l.backward(gradient=share)  # each shard's loss is a mean over B/ns clouds
                 losses.append(l)
+                projs.append(out["proj"])
         for st in extra:
             main.wait_stream(st)
+        held.update(losses=losses, projs=projs)
         return losses[0]
 
     side = torch.cuda.Stream(device)
@@ -490,11 +533,13 @@ def main():
             """One more independent batch: its own inputs, gradients, buffers, HIP graph and stream."""
             lpc, lq, ls = (x.detach().clone().requires_grad_(True) for x in (pc, q, s))
             lgt, lst = gt.clone(), torch.cuda.Stream(device)
+            lane_out = {}
 
             def lane_step():
                 lpc.grad = lq.grad = ls.grad = None
-                loss, _, _ = R.pointcloud_project_loss(cfg, lpc, lq, None, None, kern, scaling_factor=ls, gt=lgt, num_candidates=K_CAND)
+                loss, out, winner = R.pointcloud_project_loss(cfg, lpc, lq, None, None, kern, scaling_factor=ls, gt=lgt, num_candidates=K_CAND)
                 loss.backward(gradient=one)
+                lane_out.update(loss=loss, proj=out["proj"], winner=winner if K_CAND > 1 else None)
                 return loss
             with torch.cuda.stream(lst):
                 for _ in range(3):
@@ -503,7 +548,7 @@ def main():
                 lg = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(lg, stream=lst, capture_error_mode="thread_local"):
                     lane_step()
-            return lg, lst
+            return lg, lst, lambda: dict(lane_out, dpc=lpc.grad, dq=lq.grad, ds=ls.grad)
 
         lanes = []
         if args.in_flight > 1:
@@ -522,10 +567,13 @@ def main():
                 lpc, lq, ls = (x[j * nb:(j + 1) * nb].detach().clone().requires_grad_(True) for x in (pc, q, s))
                 lgt, lst = gt[j * nb:(j + 1) * nb].clone(), torch.cuda.Stream(device)
 
-                def part_step(lpc=lpc, lq=lq, ls=ls, lgt=lgt):
+                part_out = {}
+
+                def part_step(lpc=lpc, lq=lq, ls=ls, lgt=lgt, part_out=part_out):
                     lpc.grad = lq.grad = ls.grad = None
-                    loss, _, _ = R.pointcloud_project_loss(cfg, lpc, lq, None, None, kern, scaling_factor=ls, gt=lgt, num_candidates=1)
+                    loss, out, _ = R.pointcloud_project_loss(cfg, lpc, lq, None, None, kern, scaling_factor=ls, gt=lgt, num_candidates=1)
                     loss.backward(gradient=frac)   # every part's loss is a mean over B/n clouds
+                    part_out.update(loss=loss, proj=out["proj"], dpc=lpc, dq=lq, ds=ls)
                     return loss
                 with torch.cuda.stream(lst):
                     for _ in range(3):
@@ -534,27 +582,45 @@ def main():
                     lg = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(lg, stream=lst, capture_error_mode="thread_local"):
                         part_step()
-                parts.append((lg, lst))
+                parts.append((lg, lst, part_out))
 
         def run_step(i):
             if parts:
-                for lg, lst in parts:
+                for lg, lst, _ in parts:
                     lst.wait_stream(side)      # fork: the step starts when the previous one has been joined
                     with torch.cuda.stream(lst):
                         lg.replay()
-                for lg, lst in parts:
+                for lg, lst, _ in parts:
                     side.wait_stream(lst)      # join
                 return
             if plan is not None:
                 plan.run()
             elif lanes and i % args.in_flight:
-                lg, lst = lanes[i % args.in_flight - 1]
+                lg, lst, _ = lanes[i % args.in_flight - 1]
                 with torch.cuda.stream(lst):
                     lg.replay()
             elif graph is not None:
                 graph.replay()
             else:
                 last[0] = step()
+
+        def last_step_outputs(i):
+            """What step i of run_step left a caller of the timed path: the loss, the silhouettes, d(loss)/d(pc, q, s)
+            and, with several pose candidates, the winning candidate per sample."""
+            if plan is not None:
+                return dict(loss=plan.loss, proj=plan.proj, dpc=plan.dpc, dq=plan.dq, ds=plan.ds,
+                            winner=plan.winner if K_CAND > 1 else None)
+            if parts:   # n sub-batches of B/n clouds, each loss a mean over its clouds
+                outs = [p[2] for p in parts]
+                return dict(loss=torch.stack([o["loss"] for o in outs]).mean(), proj=torch.cat([o["proj"] for o in outs]),
+                            **{k: torch.cat([o[k].grad for o in outs]) for k in ("dpc", "dq", "ds")})
+            if lanes and i % args.in_flight:
+                return lanes[i % args.in_flight - 1][2]()
+            if ns > 1:   # shards of B/ns clouds on ns streams, each loss a mean over its clouds
+                return dict(loss=torch.stack(held["losses"]).mean(), proj=torch.cat(held["projs"]),
+                            dpc=torch.cat([x[0].grad for x in shards]), dq=torch.cat([x[1].grad for x in shards]),
+                            ds=torch.cat([x[2].grad for x in shards]))
+            return dict(loss=last[0], proj=held["proj"], dpc=pc.grad, dq=q.grad, ds=s.grad, winner=held.get("winner"))
 
         for i in range(args.warmup):
             run_step(i)
@@ -574,6 +640,8 @@ def main():
         torch.cuda.synchronize(device)
         wall = time.perf_counter() - t0
         dev_ms = ev0.elapsed_time(ev1) if not lanes else wall * 1e3   # several streams: the events of one do not bracket the others
+        if args.dump_outputs:   # before anything below runs the step again
+            dump_outputs(args.dump_outputs, last_step_outputs(args.steps - 1), rank, world)
 
         tt = torch.tensor([wall], device=device, dtype=torch.float64)
         if dist_on:
@@ -614,7 +682,7 @@ def main():
             if args.api == "fused" and ns == 1 and not lanes and not parts:
                 # NOT the contract's number: two INDEPENDENT batches in flight (second graph, second stream, no join between
                 # steps) -- how much of the one-chain step is latency and kernel tails that a second chain fills
-                lg, lst = new_lane()
+                lg, lst, _ = new_lane()
                 torch.cuda.synchronize(device)
                 n2 = 200
                 for phase in range(2):   # first pass warms up

@@ -482,6 +482,58 @@ def f12_view_sampler():
     save("f12_view_sampler.npz", **arrays)
 
 
+def f13_caller_layout():
+    """What tests/test_dropin_overlay.py needs to know about the reference's side of the drop-in, recorded so that those
+    tests run without the reference: the modules of its util package, the names its caller module binds from the util
+    modules this build replaces (dpc/models/model_pc_to.py:15-24, alias -> module and name), the parameter count of its
+    ModelPointCloud for the chair_unsupervised experiment, and the config and argument shapes with which that model's own
+    forward calls pointcloud_project_fast (:262) at a tiny size."""
+    sys.modules.setdefault("nets.net_factory", type(sys)("nets.net_factory")).get_network = None  # TF-era module, unused
+    import models.model_pc_to as ref_model
+
+    util_dir = os.path.join(REF, "dpc", "util")
+    modules = sorted(f[:-3] for f in os.listdir(util_dir) if f.endswith(".py") and f != "__init__.py")
+    replaced = ("point_cloud_to", "drc", "gauss_kernel", "quaternion", "point_cloud_distance")
+    bindings = {k: [v.__module__, v.__name__] for k, v in sorted(vars(ref_model).items())
+                if callable(v) and getattr(v, "__module__", "").split(".")[-1] in replaced
+                and getattr(v, "__module__", "").startswith("util.")}
+    cfg = make_cfg(**yaml.safe_load(open(os.path.join(REF, "experiments/chair_unsupervised/config.yaml"))))
+    full = ref_model.ModelPointCloud(cfg)
+    parameters = sum(p.numel() for p in full.parameters())
+    del full
+    cfg.update(z_dim=64, fc_dim=64, f_dim=8, pc_num_points=256, vox_size=16, pc_gauss_kernel_size=11, batch_size=2,
+               step_size=2, input_shape=[32, 32, 3], pc_point_dropout=0.5)
+    seen = {}
+
+    class Stop(Exception):
+        pass
+
+    def spy(cfg_, pc, q, t, rgb, kernel, scaling_factor=None, focal_length=None):
+        shape = lambda x: None if x is None else list(x.shape)
+        seen.update(point_cloud=shape(pc), transform=shape(q), predicted_translation=shape(t), all_rgb=shape(rgb),
+                    kernel=[shape(k) for k in kernel], scaling_factor=shape(scaling_factor), focal_length=shape(focal_length))
+        raise Stop
+
+    ref_model.pointcloud_project_fast = spy
+    torch.manual_seed(3)
+    np.random.seed(3)
+    model = ref_model.ModelPointCloud(cfg)
+    g = torch.Generator().manual_seed(3)
+    images = torch.rand(4, 3, 32, 32, generator=g)
+    inputs = dict(images=images, masks=(torch.rand(4, 1, 32, 32, generator=g) > 0.5).float(), images_1=images[::2])
+    try:
+        with quiet():
+            model(inputs, 0, is_training=True, run_projection=True)
+    except Stop:
+        pass
+    assert seen, "the model's forward never reached pointcloud_project_fast"
+    record = dict(util_modules=modules, caller_bindings=bindings, parameters=parameters, renderer_call=seen,
+                  tiny_cfg={k: (v if not isinstance(v, np.generic) else v.item()) for k, v in cfg.items()})
+    with open(os.path.join(HERE, "f13_caller_layout.json"), "w") as fh:
+        json.dump(record, fh, indent=0, sort_keys=True, default=str)
+    print("wrote f13_caller_layout.json;", parameters, "parameters;", seen)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     if len(sys.argv) > 1:  # regenerate only the named groups, e.g. `make_golden.py f11_nearest`
@@ -500,4 +552,5 @@ if __name__ == "__main__":
     f11_nearest()
     f10_full_step()
     f12_view_sampler()
+    f13_caller_layout()
     assert not os.path.exists(os.path.join(REF, "dpc/util/__pycache__")), "left bytecode in the reference"

@@ -141,3 +141,53 @@ def test_dominant_kernel_is_chosen_from_the_committed_profile():
     assert a == c and src_a == src_c and src_a.startswith("profiles/")
     d, src_d = b.dominant_kernel({"k_unknown": 1.0, "k_other": 2.0}, "c2")
     assert d == "k_other" and "event" in src_d
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    """--dump-outputs: one float32 .npy per output, flattened, values unchanged when they fit; rank r > 0 prefixes rank<r>_."""
+    import numpy as np
+    import torch
+
+    b = _bench()
+    arrays = {"loss": torch.tensor(2.5), "dpc": torch.arange(12, dtype=torch.float32).reshape(2, 2, 3),
+              "winner": torch.tensor([3, 1], dtype=torch.int32), "unused": None}
+    b.dump_outputs(str(tmp_path / "out"), arrays, 0, 1)
+    b.dump_outputs(str(tmp_path / "out"), arrays, 1, 2)
+    names = sorted(os.listdir(tmp_path / "out"))
+    assert names == ["dpc.npy", "loss.npy", "rank1_dpc.npy", "rank1_loss.npy", "rank1_winner.npy", "winner.npy"]
+    dpc = np.load(tmp_path / "out" / "dpc.npy")
+    assert dpc.dtype == np.float32 and np.array_equal(dpc, np.arange(12, dtype=np.float32))
+    assert np.load(tmp_path / "out" / "loss.npy").tolist() == [2.5]
+    assert np.load(tmp_path / "out" / "winner.npy").tolist() == [3.0, 1.0]
+
+
+def test_dump_outputs_samples_within_the_budget(tmp_path, monkeypatch):
+    """Outputs larger than the budget: the same fixed, seeded positions on every run, within the budget."""
+    import numpy as np
+    import torch
+
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_BYTES", 40_000)
+    big = torch.randn(30_000, generator=torch.Generator().manual_seed(1))
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"parameters": big, "loss": torch.tensor(1.0)}, 0, 1)
+    assert sorted(os.listdir(tmp_path / "a")) == ["loss.npy", "parameters.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 40_000
+    for name in ("parameters.npy", "loss.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)), name
+    vals = np.load(tmp_path / "a" / "parameters.npy")
+    assert 9_000 < len(vals) < 10_000
+    idx = b.dump_sample_index(30_000, len(vals)).numpy()
+    assert np.all(np.diff(idx) > 0) and np.array_equal(vals, big.numpy()[idx])
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [1.0]
+
+
+def test_steps_must_be_positive(monkeypatch):
+    """--steps is the number of timed steps: zero or fewer is refused before anything runs."""
+    import pytest
+
+    b = _bench()
+    for argv in (["--steps", "0"], ["--steps", "-3"], ["--warmup", "-1"]):
+        monkeypatch.setattr(b.sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit, match="--steps must be >= 1"):
+            b.main()

@@ -1,5 +1,6 @@
 """The Python drop-in next to a second `util` package (reference imports: dpc/models/model_pc_to.py:15-24,
 path set-up dpc/run/startup.py:4-6).  Runs in a child interpreter so that the `util` of this process is untouched."""
+import json
 import os
 import subprocess
 import sys
@@ -64,75 +65,114 @@ def test_overlay_next_to_a_second_util_package(tmp_path):
     assert out.strip().endswith("ok")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/dpc/util"), reason="the reference checkout exists in the build container only")
-def test_overlay_next_to_the_reference_itself():
-    """With the reference's real dpc/ on the path: its caller's import lines (model_pc_to.py:15-24) bind to this build,
-    its other util modules are found where they were."""
+def _reference_layout():
+    with open(os.path.join(ROOT, "tests", "golden", "f13_caller_layout.json")) as fh:
+        return json.load(fh)
+
+
+def _stand_in_reference(tmp_path, layout):
+    """A dpc/ directory laid out like the reference's (fixture f13): every module of its util package, each a stub that
+    says where it lives, and a models/model_pc_to.py that binds the names the reference's caller binds from the replaced
+    util modules (model_pc_to.py:15-24, recorded alias by alias) and calls the renderer as that caller's forward does."""
+    ref = tmp_path / "dpc"
+    (ref / "util").mkdir(parents=True)
+    (ref / "util" / "__init__.py").write_text("")
+    for name in layout["util_modules"]:
+        (ref / "util" / (name + ".py")).write_text("WHERE = 'reference util.%s'\n" % name)
+    (ref / "models").mkdir()
+    (ref / "models" / "__init__.py").write_text("")
+    lines = ["from %s import %s as %s" % (mod, name, alias) for alias, (mod, name) in sorted(layout["caller_bindings"].items())]
+    lines += ["",
+              "def compute_projection(cfg, point_cloud, transform, predicted_translation, scaling_factor, focal_length, sigma_rel):",
+              "    kernel = smoothing_kernel(cfg, sigma_rel)",
+              "    return pointcloud_project_fast(cfg, point_cloud, transform, predicted_translation, None, kernel,",
+              "                                   scaling_factor=scaling_factor, focal_length=focal_length)", ""]
+    (ref / "models" / "model_pc_to.py").write_text("\n".join(lines))
+    return ref
+
+
+def test_overlay_next_to_the_reference_itself(tmp_path):
+    """With a directory laid out like the reference's dpc/ on the path (its util modules as recorded in fixture f13): its
+    caller's import lines (model_pc_to.py:15-24) bind to this build, its other util modules are found where they were."""
+    layout = _reference_layout()
+    ref = _stand_in_reference(tmp_path, layout)
+    replaced = ("point_cloud_to", "drc", "gauss_kernel", "quaternion", "point_cloud_distance")
+    assert set(replaced) <= set(layout["util_modules"])
     out = _run("""
-        import sys, importlib.util
+        import sys, importlib.util, json
         sys.path.insert(0, sys.argv[1])
-        sys.path.append('/root/reference/dpc')
+        sys.path.append(sys.argv[2])
+        replaced, others = json.loads(sys.argv[3]), json.loads(sys.argv[4])
         from util.point_cloud_to import pc_point_dropout, pointcloud_project_fast
         from util.gauss_kernel import smoothing_kernel
         from util.quaternion import quaternion_multiply as q_mul, quaternion_normalise as q_norm, \\
             quaternion_rotate as q_rotate, quaternion_conjugate as q_conj
         import dpc.render as R
         assert pointcloud_project_fast is R.pointcloud_project_fast and smoothing_kernel is R.smoothing_kernel
-        for name in ('app_config', 'camera', 'fs', 'system', 'voxel', 'losses_to'):
+        for name in others:
             spec = importlib.util.find_spec('util.' + name)
-            assert spec is not None and spec.origin.startswith('/root/reference/dpc/util/'), (name, spec)
-        for name in ('point_cloud_to', 'drc', 'gauss_kernel', 'quaternion', 'point_cloud_distance'):
+            assert spec is not None and spec.origin.startswith(sys.argv[2] + '/util/'), (name, spec)
+        for name in replaced:
             assert importlib.util.find_spec('util.' + name).origin.startswith(sys.argv[1]), name
-        import util.fs                      # a reference module with no third-party dependency: really importable
-        assert util.fs.__file__.startswith('/root/reference/dpc/util/')
+        import util.fs                      # a module of the reference's util package: really importable
+        assert util.fs.__file__.startswith(sys.argv[2] + '/util/') and util.fs.WHERE == 'reference util.fs'
         print('ok')
-        """, PKG)
+        """, PKG, str(ref), json.dumps(replaced), json.dumps([m for m in layout["util_modules"] if m not in replaced]))
     assert out.strip().endswith("ok")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/dpc/models"), reason="the reference checkout exists in the build container only")
-def test_the_references_own_caller_through_the_overlay():
-    """north_star: "so dpc/run/train_eval_to.py can import it as a drop-in".  The reference's caller module
-    (dpc/models/model_pc_to.py, import block :15-24) is imported with the overlay in front of the reference's dpc/: the
-    names it binds ARE this build's functions, ModelPointCloud(cfg) constructs from the experiment's yaml, and its own
-    forward (compute_projection, :239-282) reaches dpc.render.pointcloud_project_fast with arguments that bind -- on this
-    GPU-less host that call ends in dpc.render's loud "MI355X only" error, raised after the config, the kernel list and the
-    tensors were accepted (there is no CPU path to fall into)."""
+def test_the_references_own_caller_through_the_overlay(tmp_path):
+    """north_star: "so dpc/run/train_eval_to.py can import it as a drop-in".  A caller module binding exactly the names the
+    reference's caller (dpc/models/model_pc_to.py, import block :15-24) binds, recorded in fixture f13, is imported with the
+    overlay in front of a directory laid out like the reference's dpc/: the names it binds ARE this build's functions, this
+    build's networks have the parameter count of the reference's ModelPointCloud for the experiment's config, and the
+    renderer call of the reference's forward (compute_projection, :239-282; config and argument shapes as recorded) binds --
+    on a GPU-less host that call ends in dpc.render's loud "MI355X only" error, raised after the config, the kernel list and
+    the tensors were accepted (there is no CPU path to fall into)."""
+    layout = _reference_layout()
+    ref = _stand_in_reference(tmp_path, layout)
     out = _run("""
-        import sys
+        import sys, json
         sys.path.insert(0, sys.argv[1])            # the line a maintainer adds to dpc/run/startup.py
-        sys.path.append('/root/reference/dpc')     # startup.py's own line (dpc/run/startup.py:4-6)
-        import torch, yaml
+        sys.path.append(sys.argv[2])               # startup.py's own line (dpc/run/startup.py:4-6)
+        layout = json.loads(open(sys.argv[3]).read())
+        import torch
         from models import model_pc_to
         import dpc.render as R
+        from dpc.harness import chair_unsupervised
+        from dpc.harness.nets import StepNets
         assert model_pc_to.pointcloud_project_fast is R.pointcloud_project_fast
         assert model_pc_to.smoothing_kernel is R.smoothing_kernel and model_pc_to.pc_point_dropout is R.pc_point_dropout
         assert model_pc_to.q_mul is R.quaternion_multiply and model_pc_to.q_norm is R.quaternion_normalise
         assert model_pc_to.q_rotate is R.quaternion_rotate and model_pc_to.q_conj is R.quaternion_conjugate
-        assert model_pc_to.__file__.startswith('/root/reference/dpc/models/')
+        for alias, (mod, name) in layout['caller_bindings'].items():
+            assert getattr(model_pc_to, alias) is getattr(R, name), alias
+        assert model_pc_to.__file__.startswith(sys.argv[2] + '/models/')
+
+        full = StepNets(chair_unsupervised())
+        assert sum(p.numel() for p in full.parameters()) == layout['parameters'] == 61042134      # SURVEY 8(c)
+        del full
 
         class Cfg(dict):
             __getattr__ = dict.__getitem__
             __setattr__ = dict.__setitem__
-        cfg = Cfg(yaml.safe_load(open('/root/reference/dpc/resources/default_config.yaml')))
-        cfg.update(yaml.safe_load(open('/root/reference/experiments/chair_unsupervised/config.yaml')))
-        full = model_pc_to.ModelPointCloud(cfg)
-        assert sum(p.numel() for p in full.parameters()) == 61042134      # SURVEY 8(c)
-        del full
-        cfg.update(z_dim=64, fc_dim=64, f_dim=8, pc_num_points=256, vox_size=16, pc_gauss_kernel_size=11, batch_size=2,
-                   step_size=2, input_shape=[32, 32, 3], pc_point_dropout=0.5)
-        model = model_pc_to.ModelPointCloud(cfg)
+        cfg = Cfg(layout['tiny_cfg'])
+        call = layout['renderer_call']
+        assert call['all_rgb'] is None and [k[-3:] for k in call['kernel']] == [[1, 1, cfg.pc_gauss_kernel_size],
+                                                                                 [1, cfg.pc_gauss_kernel_size, 1],
+                                                                                 [cfg.pc_gauss_kernel_size, 1, 1]]
         g = torch.Generator().manual_seed(3)
-        images = torch.rand(4, 3, 32, 32, generator=g)
-        inputs = dict(images=images, masks=(torch.rand(4, 1, 32, 32, generator=g) > 0.5).float(), images_1=images[::2])
+        make = lambda shape: None if shape is None else torch.rand(*shape, generator=g)
+        pc, q = make(call['point_cloud']) - 0.5, make(call['transform'])
+        t, s, f = make(call['predicted_translation']), make(call['scaling_factor']), make(call['focal_length'])
         seen = {}
         real = R._native.require_device
         def spy(*tensors):
-            seen['tensors'] = [None if t is None else tuple(t.shape) for t in tensors]
+            seen['tensors'] = [None if x is None else tuple(x.shape) for x in tensors]
             return real(*tensors)
         R._ops.N.require_device = spy
         try:
-            model(inputs, 0, is_training=True, run_projection=True)
+            model_pc_to.compute_projection(cfg, pc, q, t, s, f, cfg.pc_relative_sigma)
         except RuntimeError as e:
             assert 'MI355X' in str(e), e
         else:
@@ -140,5 +180,5 @@ def test_the_references_own_caller_through_the_overlay():
         # what arrived at the renderer: 2 objects x 2 views x 4 candidates = 16 clouds of 128 kept points, poses, scales
         assert seen['tensors'][:2] == [(16, 128, 3), (16, 4)] and seen['tensors'][4] == (16, 1), seen
         print('ok')
-        """, PKG)
+        """, PKG, str(ref), os.path.join(ROOT, "tests", "golden", "f13_caller_layout.json"))
     assert out.strip().endswith("ok")

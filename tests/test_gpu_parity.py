@@ -2137,6 +2137,50 @@ def test_randomised_shapes_vs_oracle(R, O):
         ERRORS.append(("randomised shapes (40 cases), worst error / bound: " + k, v * TOL, 1.0))
 
 
+def test_bench_dump_outputs_are_the_timed_steps_results(R, O, tmp_path, monkeypatch, capsys):
+    """bench.py --dump-outputs: the loss, silhouettes and gradients of the last timed step of the default (c2) line, written
+    after the timing; the same inputs every run (another step count, the same arrays), the loss the line reports, what the
+    autograd path (pointcloud_project_loss + backward) gives on those inputs by the rule between two device paths, and the
+    first clouds' silhouettes against the oracle by the rule (a cloud's silhouette depends on that cloud alone; its
+    gradients are held to the oracle by the tests above, which account for voxels at the DRC clamp's threshold)."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(os.path.dirname(GOLDEN), "..", "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    lines, dumps = [], []
+    for steps in (3, 5):
+        out = str(tmp_path / ("steps%d" % steps))
+        monkeypatch.setattr(b.sys, "argv", ["bench.py", "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline",
+                                            "--no-extras", "--dump-outputs", out])
+        b.main()
+        lines.append(json.loads(capsys.readouterr().out.strip().splitlines()[-1]))
+        dumps.append({f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)})
+    assert [ln["steps"] for ln in lines] == [3, 5]
+    Bc, Nc, Gc, sigma_rel = b.CONFIGS["c2"][:4]
+    got = dumps[0]
+    assert {k: v.shape for k, v in got.items()} == {"loss": (1,), "proj": (Bc * Gc * Gc,), "dpc": (Bc * Nc * 3,),
+                                                     "dq": (Bc * 4,), "ds": (Bc,)}
+    assert all(v.dtype == np.float32 for v in got.values())
+    for k in got:
+        assert np.array_equal(got[k], dumps[1][k]), k
+    assert got["loss"][0] == np.float32(lines[0]["loss_mean"])
+    from dpc.harness import chair_unsupervised
+
+    cfg = chair_unsupervised(vox_size=Gc, pc_gauss_kernel_size=b.KSIZE)
+    pc, q, s, gt = b.synthetic_inputs(Bc, Nc, Gc, 1234)
+    gp, gq, gs = (x.to("cuda").requires_grad_(True) for x in (pc, q, s))
+    loss, out, _ = R.pointcloud_project_loss(cfg, gp, gq, None, None, R.smoothing_kernel(cfg, sigma_rel), scaling_factor=gs,
+                                             gt=gt.to("cuda"), num_candidates=1)
+    loss.backward()
+    for k, ref in (("loss", loss), ("proj", out["proj"]), ("dpc", gp.grad), ("dq", gq.grad), ("ds", gs.grad)):
+        close(got[k], ref.detach().reshape(-1), 1e-6, "bench dump vs the autograd path: " + k)
+    n = 2
+    cp, cq, cs = (x[:n].double() for x in (pc, q, s))
+    ref = O.pointcloud_project_fast(cfg, cp, cq, None, None, O.smoothing_kernel(cfg, sigma_rel), scaling_factor=cs)
+    close(got["proj"][:n * Gc * Gc], ref["proj"].reshape(-1), TOL, "bench dump: proj")
+
+
 def test_zz_error_report():
     """Not a check: writes the worst observed error per quantity to gpurun_out/ for DESIGN.md."""
     worst = {}
