@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define DPC_ABI_VERSION 13
+#define DPC_ABI_VERSION 14
 #define DPC_MAX_TAPS 63 /* longest 1-D smoothing kernel accepted (pc_gauss_kernel_size) */
 /* Size limits, checked by every entry point (DPC_ERR_SHAPE): grid sides <= 1024 (10-bit cell indices in a point record),
  * B <= 65535, and N <= DPC_MAX_POINTS points per cloud: a voxel's splat weights are summed in 64-bit fixed point with 44
@@ -299,13 +299,17 @@ int dpc_point_cloud_distance(const void* vs, const void* vt, int ns, int nt, int
 /* ---------------------------------------------------------------------------------------------------
  * Opt-in measurement aid (nothing in the reference corresponds to it).  After dpc_profile_enable(capacity)
  * every launch of the fused path is bracketed by hipEvents on its stream; synchronise the stream, then read
- * dpc_profile_count() entries with dpc_profile_get(i, &kernel_name, &milliseconds).  Off by default; the only
+ * dpc_profile_count() entries with dpc_profile_get(i, &kernel_name, &milliseconds) and dpc_profile_get_id.  Off by default; the only
  * global state in the library; not usable while a hipGraph is being captured.
  * ------------------------------------------------------------------------------------------------- */
 int dpc_profile_enable(int capacity);
 int dpc_profile_disable(void);
 int dpc_profile_count(void);
 int dpc_profile_get(int i, const char** name, float* ms);
+/* ABI 14.  The template instantiation entry i launched, as the device symbol's demangled template: "k_gather_hw<64, 8, 3>",
+ * "k_zcol_fwdbwd<64, 3, 1>", "k_zcol_fwd_dyn" (no template arguments: the name alone).  Written NUL-terminated into id[cap];
+ * DPC_ERR_SHAPE when i is out of range or cap is too small.  What dpc_profile_get names is the kernel family alone. */
+int dpc_profile_get_id(int i, char* id, int cap);
 /* What an EMPTY begin/end event pair reads on `stream` (synchronising; call outside timed regions): subtract it from
  * dpc_profile_get's figures to compare with rocprofv3's kernel durations. */
 int dpc_profile_pair_overhead(void* stream, int pairs, float* ms);

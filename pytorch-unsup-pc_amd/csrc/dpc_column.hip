@@ -567,9 +567,9 @@ int launch_zcol_fwdbwd(const DpcParams* p, const float* host_kern_z, const TapPl
 #define DPC_ZFB(RB)                                                                                                \
   {                                                                                                                \
     const TapsT<RB> tzf = make_taps<RB>(host_kern_z, pz, false), tza = make_taps<RB>(host_kern_z, pz, true);       \
-    if (p->D == 32) DPC_LAUNCH("k_zcol_fwdbwd", (k_zcol_fwdbwd<32, RB, kRpl>), gpair, dim3(kColThreads), 0, st, *p, rh, Tbuf, s, tzf, tza, proj, dT, ds_part, ntile, tickets, cf, bf, bwd_dsmall, cg_count, la); \
-    else if (p->D == 64) DPC_LAUNCH("k_zcol_fwdbwd", (k_zcol_fwdbwd<64, RB, kRpl>), gpair, dim3(kColThreads), 0, st, *p, rh, Tbuf, s, tzf, tza, proj, dT, ds_part, ntile, tickets, cf, bf, bwd_dsmall, cg_count, la); \
-    else DPC_LAUNCH("k_zcol_fwdbwd", (k_zcol_fwdbwd<128, RB, kRpl>), gpair, dim3(kColThreads), 0, st, *p, rh, Tbuf, s, tzf, tza, proj, dT, ds_part, ntile, tickets, cf, bf, bwd_dsmall, cg_count, la); \
+    if (p->D == 32) DPC_LAUNCH("k_zcol_fwdbwd", dpc_kid("k_zcol_fwdbwd", 32, RB, kRpl), (k_zcol_fwdbwd<32, RB, kRpl>), gpair, dim3(kColThreads), 0, st, *p, rh, Tbuf, s, tzf, tza, proj, dT, ds_part, ntile, tickets, cf, bf, bwd_dsmall, cg_count, la); \
+    else if (p->D == 64) DPC_LAUNCH("k_zcol_fwdbwd", dpc_kid("k_zcol_fwdbwd", 64, RB, kRpl), (k_zcol_fwdbwd<64, RB, kRpl>), gpair, dim3(kColThreads), 0, st, *p, rh, Tbuf, s, tzf, tza, proj, dT, ds_part, ntile, tickets, cf, bf, bwd_dsmall, cg_count, la); \
+    else DPC_LAUNCH("k_zcol_fwdbwd", dpc_kid("k_zcol_fwdbwd", 128, RB, kRpl), (k_zcol_fwdbwd<128, RB, kRpl>), gpair, dim3(kColThreads), 0, st, *p, rh, Tbuf, s, tzf, tza, proj, dT, ds_part, ntile, tickets, cf, bf, bwd_dsmall, cg_count, la); \
   }
   DPC_FOR_BUCKET(pz.bucket, DPC_ZFB)
 #undef DPC_ZFB
@@ -585,15 +585,15 @@ int launch_zcol_fwd(const DpcParams* p, const float* host_kern_z, const TapPlan&
 #define DPC_ZFWD(RB)                                                                                             \
   {                                                                                                              \
     const TapsT<RB> tz = make_taps<RB>(host_kern_z, pz, false);                                                  \
-    if (p->D == 32) { DPC_LAUNCH("k_zcol_fwd", (k_zcol_fwd<32, RB>), gcol, dim3(kColThreads), 0, st, *p, rh, Tbuf, s, tz, smoothed, proj, trans, la); done = true; } \
-    else if (p->D == 64) { DPC_LAUNCH("k_zcol_fwd", (k_zcol_fwd<64, RB>), gcol, dim3(kColThreads), 0, st, *p, rh, Tbuf, s, tz, smoothed, proj, trans, la); done = true; } \
-    else if (p->D == 128) { DPC_LAUNCH("k_zcol_fwd", (k_zcol_fwd<128, RB>), gcol, dim3(kColThreads), 0, st, *p, rh, Tbuf, s, tz, smoothed, proj, trans, la); done = true; } \
+    if (p->D == 32) { DPC_LAUNCH("k_zcol_fwd", dpc_kid("k_zcol_fwd", 32, RB), (k_zcol_fwd<32, RB>), gcol, dim3(kColThreads), 0, st, *p, rh, Tbuf, s, tz, smoothed, proj, trans, la); done = true; } \
+    else if (p->D == 64) { DPC_LAUNCH("k_zcol_fwd", dpc_kid("k_zcol_fwd", 64, RB), (k_zcol_fwd<64, RB>), gcol, dim3(kColThreads), 0, st, *p, rh, Tbuf, s, tz, smoothed, proj, trans, la); done = true; } \
+    else if (p->D == 128) { DPC_LAUNCH("k_zcol_fwd", dpc_kid("k_zcol_fwd", 128, RB), (k_zcol_fwd<128, RB>), gcol, dim3(kColThreads), 0, st, *p, rh, Tbuf, s, tz, smoothed, proj, trans, la); done = true; } \
   }
   if (pz.bucket >= 0) { DPC_FOR_BUCKET(pz.bucket, DPC_ZFWD) }
 #undef DPC_ZFWD
   if (rc != DPC_OK) return rc;
   if (!done) {  // other depths / longer kernels: same arithmetic, column re-read from global
-    DPC_LAUNCH("k_zcol_fwd", k_zcol_fwd_dyn, gcol, dim3(kColThreads), 0, st, *p, rh, Tbuf, s,
+    DPC_LAUNCH("k_zcol_fwd", dpc_kid("k_zcol_fwd_dyn"), k_zcol_fwd_dyn, gcol, dim3(kColThreads), 0, st, *p, rh, Tbuf, s,
                make_taps_dyn(host_kern_z, p->taps_z, false), smoothed, proj, trans, la);
   }
   return launch_ok();
@@ -609,15 +609,15 @@ int launch_zcol_bwd(const DpcParams* p, const float* host_kern_z, const TapPlan&
 #define DPC_ZBWD(RB)                                                                                              \
   {                                                                                                               \
     const TapsT<RB> tz = make_taps<RB>(host_kern_z, pz, true), tzf = make_taps<RB>(host_kern_z, pz, false);       \
-    if (p->D == 32) { DPC_LAUNCH("k_zcol_bwd", (k_zcol_bwd<32, RB>), gcol, dim3(kColThreads), 0, st, *p, rh, grid_wh, s, dproj, proj, trans, tzf, tz, dT, ds_part, dsmall, cg_count, dgrid_extra, la); done = true; } \
-    else if (p->D == 64) { DPC_LAUNCH("k_zcol_bwd", (k_zcol_bwd<64, RB>), gcol, dim3(kColThreads), 0, st, *p, rh, grid_wh, s, dproj, proj, trans, tzf, tz, dT, ds_part, dsmall, cg_count, dgrid_extra, la); done = true; } \
-    else if (p->D == 128) { DPC_LAUNCH("k_zcol_bwd", (k_zcol_bwd<128, RB>), gcol, dim3(kColThreads), 0, st, *p, rh, grid_wh, s, dproj, proj, trans, tzf, tz, dT, ds_part, dsmall, cg_count, dgrid_extra, la); done = true; } \
+    if (p->D == 32) { DPC_LAUNCH("k_zcol_bwd", dpc_kid("k_zcol_bwd", 32, RB), (k_zcol_bwd<32, RB>), gcol, dim3(kColThreads), 0, st, *p, rh, grid_wh, s, dproj, proj, trans, tzf, tz, dT, ds_part, dsmall, cg_count, dgrid_extra, la); done = true; } \
+    else if (p->D == 64) { DPC_LAUNCH("k_zcol_bwd", dpc_kid("k_zcol_bwd", 64, RB), (k_zcol_bwd<64, RB>), gcol, dim3(kColThreads), 0, st, *p, rh, grid_wh, s, dproj, proj, trans, tzf, tz, dT, ds_part, dsmall, cg_count, dgrid_extra, la); done = true; } \
+    else if (p->D == 128) { DPC_LAUNCH("k_zcol_bwd", dpc_kid("k_zcol_bwd", 128, RB), (k_zcol_bwd<128, RB>), gcol, dim3(kColThreads), 0, st, *p, rh, grid_wh, s, dproj, proj, trans, tzf, tz, dT, ds_part, dsmall, cg_count, dgrid_extra, la); done = true; } \
   }
   if (pz.bucket >= 0) { DPC_FOR_BUCKET(pz.bucket, DPC_ZBWD) }
 #undef DPC_ZBWD
   if (rc != DPC_OK) return rc;
   if (!done) {
-    DPC_LAUNCH("k_zcol_bwd", k_zcol_bwd_dyn, gcol, dim3(kColThreads), 0, st, *p, rh, grid_wh, s, dproj, proj, trans,
+    DPC_LAUNCH("k_zcol_bwd", dpc_kid("k_zcol_bwd_dyn"), k_zcol_bwd_dyn, gcol, dim3(kColThreads), 0, st, *p, rh, grid_wh, s, dproj, proj, trans,
                make_taps_dyn(host_kern_z, p->taps_z, false), make_taps_dyn(host_kern_z, p->taps_z, true), dT, ds_part,
                dsmall, cg_count, dgrid_extra, la);
   }
@@ -626,7 +626,7 @@ int launch_zcol_bwd(const DpcParams* p, const float* host_kern_z, const TapPlan&
 
 int launch_loss_finalize(const float* sse_tiles, int ntile, float* sse, int S, int K, float inv_S, float* loss, int32_t* winner,
                          hipStream_t st) {
-  DPC_LAUNCH("k_loss_finalize", k_loss_finalize, dim3(1), dim3(256), 0, st, sse_tiles, ntile, sse, S, K, inv_S, loss, winner);
+  DPC_LAUNCH("k_loss_finalize", dpc_kid("k_loss_finalize"), k_loss_finalize, dim3(1), dim3(256), 0, st, sse_tiles, ntile, sse, S, K, inv_S, loss, winner);
   return launch_ok();
 }
 

@@ -127,8 +127,9 @@ int nearest_impl(const T* vs, const T* vt, int ns, int nt, T* proj, T* min_dist,
   T* part_dist = static_cast<T*>(workspace);
   int* part_idx = reinterpret_cast<int*>(part_dist + (size_t)nslice * ns);
   const dim3 grid((ns + kNnThreads - 1) / kNnThreads, nslice);
-  DPC_LAUNCH("k_nearest_partial", k_nearest_partial<T>, grid, dim3(kNnThreads), 0, st, vs, vt, ns, nt, slice, part_dist, part_idx);
-  DPC_LAUNCH("k_nearest_merge", k_nearest_merge<T>, dim3(grid.x), dim3(kNnThreads), 0, st, vt, ns, nslice,
+  constexpr bool kIsF64 = sizeof(T) == sizeof(double);
+  DPC_LAUNCH("k_nearest_partial", dpc_kid(kIsF64 ? "k_nearest_partial<double>" : "k_nearest_partial<float>"), k_nearest_partial<T>, grid, dim3(kNnThreads), 0, st, vs, vt, ns, nt, slice, part_dist, part_idx);
+  DPC_LAUNCH("k_nearest_merge", dpc_kid(kIsF64 ? "k_nearest_merge<double>" : "k_nearest_merge<float>"), k_nearest_merge<T>, dim3(grid.x), dim3(kNnThreads), 0, st, vt, ns, nslice,
              (const T*)part_dist, (const int*)part_idx, proj, min_dist, idx);
   return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
 }

@@ -2,6 +2,7 @@
 // an explicit enable call, never touched otherwise.
 #include "dpc_profile.h"
 
+#include <cstdio>
 #include <mutex>
 #include <vector>
 
@@ -10,6 +11,7 @@
 namespace {
 struct Slot {
   const char* name;
+  DpcKernelId id;
   hipEvent_t a, b;
 };
 std::mutex g_mu;  // launches may come from torch's autograd thread while the caller reads results
@@ -19,11 +21,12 @@ size_t g_used = 0;
 bool g_open = false;
 }  // namespace
 
-void dpc_prof_before(const char* name, hipStream_t st) {
+void dpc_prof_before(const char* name, const DpcKernelId& id, hipStream_t st) {
   if (!g_on) return;  // the common case takes no lock
   std::lock_guard<std::mutex> lock(g_mu);
   if (!g_on || g_used >= g_slots.size()) return;
   g_slots[g_used].name = name;
+  g_slots[g_used].id = id;
   (void)hipEventRecord(g_slots[g_used].a, st);
   g_open = true;
 }
@@ -43,7 +46,7 @@ int dpc_profile_enable(int capacity) {
   if (capacity < 0) return DPC_ERR_SHAPE;
   std::lock_guard<std::mutex> lock(g_mu);
   while ((int)g_slots.size() < capacity) {
-    Slot s{nullptr, nullptr, nullptr};
+    Slot s{nullptr, DpcKernelId{nullptr, 0, {0, 0, 0}}, nullptr, nullptr};
     if (hipEventCreate(&s.a) != hipSuccess || hipEventCreate(&s.b) != hipSuccess) return DPC_ERR_LAUNCH;
     g_slots.push_back(s);
   }
@@ -87,6 +90,18 @@ int dpc_profile_get(int i, const char** name, float* ms) {
   if (i < 0 || (size_t)i >= g_used || !name || !ms) return DPC_ERR_SHAPE;
   *name = g_slots[i].name;
   return hipEventElapsedTime(ms, g_slots[i].a, g_slots[i].b) == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+}
+
+// ABI 14: the instantiation entry i ran, "k_gather_hw<64, 8, 3>", NUL-terminated into id[cap]
+int dpc_profile_get_id(int i, char* id, int cap) {
+  if (i < 0 || (size_t)i >= g_used || !id || cap < 1) return DPC_ERR_SHAPE;
+  const DpcKernelId& k = g_slots[i].id;
+  int n = 0;
+  if (k.nargs == 0) n = snprintf(id, cap, "%s", k.kernel);
+  else if (k.nargs == 1) n = snprintf(id, cap, "%s<%d>", k.kernel, k.args[0]);
+  else if (k.nargs == 2) n = snprintf(id, cap, "%s<%d, %d>", k.kernel, k.args[0], k.args[1]);
+  else n = snprintf(id, cap, "%s<%d, %d, %d>", k.kernel, k.args[0], k.args[1], k.args[2]);
+  return n >= 0 && n < cap ? DPC_OK : DPC_ERR_SHAPE;
 }
 
 }  // extern "C"

@@ -392,7 +392,7 @@ int launch_gather_fast(const DpcParams* p, Cells cells, const float* pc, const f
     for (int c = 2; c <= 16; c *= 2)
       if (p->D % c == 0 && (size_t)(p->D / c) * clouds >= (size_t)kNumCUs) roll = c;
   const int nslab = (p->D + ZS - 1) / ZS;
-  DPC_LAUNCH("k_gather_hw", kern, dim3(((nslab + roll - 1) / roll) * clouds), dim3(Geo::NT), lds, st, *p, cells, pc, q, t, f,
+  DPC_LAUNCH("k_gather_hw", dpc_kid("k_gather_hw", GS, ZS, RB), kern, dim3(((nslab + roll - 1) / roll) * clouds), dim3(Geo::NT), lds, st, *p, cells, pc, q, t, f,
              make_taps<RB>(kxy, pxy, true), ZS == 1 ? roll : ZS, dT, mask, ds_part, ntile, dpc, dsmall, cg_part, cg_count, la, dpc_fixed);
   return launch_ok();
 }
@@ -428,7 +428,7 @@ int launch_gather_rb(const DpcParams* p, Cells cells, const float* pc, const flo
   int rc = set_lds(kern, lds, limit);
   if (rc != DPC_OK) return rc;
   const bool wo = winners_only(la) && (p->point_replicas > 1 || p->point_index != nullptr);  // the kernel's own test
-  DPC_LAUNCH("k_gather_hw", kern, dim3(((p->D + Zs - 1) / Zs) * (wo ? p->B / la.K : p->B)), dim3(slab_threads(p)), lds, st, *p, cells, pc, q, t, f,
+  DPC_LAUNCH("k_gather_hw", dpc_kid("k_gather_hw", 0, 0, RB), kern, dim3(((p->D + Zs - 1) / Zs) * (wo ? p->B / la.K : p->B)), dim3(slab_threads(p)), lds, st, *p, cells, pc, q, t, f,
              make_taps<RB>(kxy, pxy, true), Zs, dT, mask, ds_part, ntile, dpc, dsmall, cg_part, cg_count, la, dpc_fixed);
   return launch_ok();
 }
@@ -452,7 +452,7 @@ int launch_gather(int bucket, const DpcParams* p, Cells cells, const float* pc, 
   DPC_FOR_BUCKET(bucket, DPC_GATHER)
 #undef DPC_GATHER
   if (rc != DPC_OK || !fixed) return rc;
-  DPC_LAUNCH("k_fixed_to_dpc", k_fixed_to_dpc, dim3((unsigned)std::min<size_t>((nfix + 255) / 256, 2048)), dim3(256), 0, st, dpc_fixed, dpc, nfix, (size_t)points_per_set(*p) * 3);
+  DPC_LAUNCH("k_fixed_to_dpc", dpc_kid("k_fixed_to_dpc"), k_fixed_to_dpc, dim3((unsigned)std::min<size_t>((nfix + 255) / 256, 2048)), dim3(256), 0, st, dpc_fixed, dpc, nfix, (size_t)points_per_set(*p) * 3);
   return launch_ok();
 }
 

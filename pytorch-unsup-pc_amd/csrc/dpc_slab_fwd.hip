@@ -458,7 +458,7 @@ int launch_splat_fast(const DpcParams* p, Cells cells, const float* kxy, const T
     for (int c = 2; c <= 16; c *= 2)
       if (nslab % c == 0 && (size_t)(nslab / c) * p->B >= (size_t)kNumCUs) nround = c;
 #endif
-  DPC_LAUNCH("k_splat_hw", kern, dim3((nslab / nround) * p->B), dim3(Geo::NT), lds, st, *p, cells,
+  DPC_LAUNCH("k_splat_hw", dpc_kid("k_splat_hw", GS, ZS, RB), kern, dim3((nslab / nround) * p->B), dim3(Geo::NT), lds, st, *p, cells,
              make_taps<RB>(kxy, pxy, false), nround, raw, Tbuf, mask, sse, loss_zero, winner_zero, ticket_zero);
   return launch_ok();
 }
@@ -493,7 +493,7 @@ int launch_splat_rb(const DpcParams* p, Cells cells, const float* kxy, const Tap
   static LdsLimit limit;
   int rc = set_lds(kern, lds, limit);
   if (rc != DPC_OK) return rc;
-  DPC_LAUNCH("k_splat_hw", kern, dim3(((p->D + Zs - 1) / Zs) * p->B), dim3(slab_threads(p)), lds, st, *p, cells,
+  DPC_LAUNCH("k_splat_hw", dpc_kid("k_splat_hw", 0, 0, RB), kern, dim3(((p->D + Zs - 1) / Zs) * p->B), dim3(slab_threads(p)), lds, st, *p, cells,
              make_taps<RB>(kxy, pxy, false), acc64 ? Zs : -Zs, raw, Tbuf, mask, sse, loss_zero, winner_zero, ticket_zero);
   return launch_ok();
 }
@@ -519,9 +519,9 @@ int launch_locate(const DpcParams* p, int src, const void* pts, const float* q, 
   dim3 g(num_chunks(p->N) * p->B), blk(kLocThreads);
   uint8_t* out = static_cast<uint8_t*>(cells);
   const size_t lds = (size_t)(p->D + 1) * (kLocThreads / DPC_WAVE) * sizeof(int);  // group sizes / start positions per wave and bin
-  if (src == 0) DPC_LAUNCH("k_locate", k_locate<0>, g, blk, lds, st, *p, pts, q, t, f, tr_pc, out);
-  else if (src == 1) DPC_LAUNCH("k_locate", k_locate<1>, g, blk, lds, st, *p, pts, q, t, f, tr_pc, out);
-  else DPC_LAUNCH("k_locate", k_locate<2>, g, blk, lds, st, *p, pts, q, t, f, tr_pc, out);
+  if (src == 0) DPC_LAUNCH("k_locate", dpc_kid("k_locate", 0), k_locate<0>, g, blk, lds, st, *p, pts, q, t, f, tr_pc, out);
+  else if (src == 1) DPC_LAUNCH("k_locate", dpc_kid("k_locate", 1), k_locate<1>, g, blk, lds, st, *p, pts, q, t, f, tr_pc, out);
+  else DPC_LAUNCH("k_locate", dpc_kid("k_locate", 2), k_locate<2>, g, blk, lds, st, *p, pts, q, t, f, tr_pc, out);
   return launch_ok();
 }
 

@@ -296,7 +296,7 @@ int launch_splat_xl_zr(const DpcParams* p, Cells cells, const float* kxy, const 
   const TapsT<RB> tw = make_taps<RB>(kxy, pxy, false);
   int symmetric = p->dev_taps_xy == nullptr;
   for (int k = 1; k <= RB; ++k) symmetric = symmetric && memcmp(&tw.w[RB - k], &tw.w[RB + k], sizeof(float)) == 0;
-  DPC_LAUNCH("k_splat_xl", kern, dim3((nslab / nround) * p->B), dim3(ZS * kXWavesPerPlane * 64), lds, st, *p, cells,
+  DPC_LAUNCH("k_splat_xl", dpc_kid("k_splat_xl", ZS, RB), kern, dim3((nslab / nround) * p->B), dim3(ZS * kXWavesPerPlane * 64), lds, st, *p, cells,
              tw, nround, Tbuf, mask, sse, loss_zero, winner_zero, ticket_zero, symmetric);
   return launch_ok();
 }

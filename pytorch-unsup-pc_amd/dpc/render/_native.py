@@ -14,7 +14,7 @@ _CSRC = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__))
 # other implementation to fall back to either way
 LIB_PATH = os.environ.get("DPC_RENDER_LIB") or os.path.join(_CSRC, "libdpc_render.so")
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 DPC_MAX_TAPS = 63
 DPC_MAX_POINTS = (1 << 20) - 1
 DPC_SMALL_COLS = 12
@@ -31,7 +31,7 @@ SYMBOLS = (
     "dpc_splat_fwd", "dpc_splat_bwd", "dpc_smooth", "dpc_drc_fwd", "dpc_drc_bwd",
     "dpc_silhouette_loss", "dpc_point_dropout_indices", "dpc_point_dropout_indices_live", "dpc_schedule_update", "dpc_taps_bucket",
     "dpc_project_loss_step",
-    "dpc_nearest_workspace_bytes", "dpc_point_cloud_distance", "dpc_profile_enable", "dpc_profile_disable", "dpc_profile_count", "dpc_profile_get", "dpc_profile_pair_overhead",
+    "dpc_nearest_workspace_bytes", "dpc_point_cloud_distance", "dpc_profile_enable", "dpc_profile_disable", "dpc_profile_count", "dpc_profile_get", "dpc_profile_get_id", "dpc_profile_pair_overhead",
 )
 
 
@@ -94,6 +94,8 @@ def lib():
         L.dpc_profile_count.restype = ctypes.c_int
         L.dpc_profile_get.restype = ctypes.c_int
         L.dpc_profile_get.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float)]
+        L.dpc_profile_get_id.restype = ctypes.c_int
+        L.dpc_profile_get_id.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.dpc_profile_pair_overhead.restype = ctypes.c_int
         L.dpc_profile_pair_overhead.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
         L.dpc_silhouette_loss.restype = ctypes.c_int
@@ -184,4 +186,25 @@ def profile_kernels(fn, device, capacity=4096):
     for i in range(L.dpc_profile_count()):
         check(L.dpc_profile_get(i, ctypes.byref(name), ctypes.byref(ms)), "dpc_profile_get")
         out.setdefault(name.value.decode(), []).append(ms.value)
+    return out
+
+
+def launched_instantiations(fn, device, capacity=4096):
+    """Run fn() with the launch record on; returns the set of kernel template instantiations it launched, named like the
+    demangled device symbols ("k_gather_hw<64, 8, 3>", "k_zcol_fwd_dyn")."""
+    L = lib()
+    check(L.dpc_profile_enable(capacity), "dpc_profile_enable")
+    try:
+        fn()
+        torch.cuda.synchronize(device)
+    finally:
+        L.dpc_profile_disable()
+    count = L.dpc_profile_count()
+    if count >= capacity:
+        raise RuntimeError("launched_instantiations: more than %d launches, the record is incomplete" % capacity)
+    buf = ctypes.create_string_buffer(128)
+    out = set()
+    for i in range(count):
+        check(L.dpc_profile_get_id(i, buf, len(buf)), "dpc_profile_get_id")
+        out.add(buf.value.decode())
     return out

@@ -225,21 +225,29 @@ def test_camera_gradient_hand_off_carries_sc1_in_the_isa():
     assert any("s_waitcnt vmcnt(0)" in l for l in lines[first_store:ticket]), "no vmcnt(0) between the hand-off stores and the ticket"
 
 
-def _device_asm(obj_name):
+LLVM_BIN = "/opt/rocm/lib/llvm/bin/"
+
+
+def device_object_output(obj_name, tool_args):
+    """Unbundle the gfx950 device object of csrc/<obj_name> and return the stdout of LLVM_BIN + tool_args + [device object]."""
     import subprocess
     import tempfile
 
     obj = os.path.join(ROOT, "pytorch-unsup-pc_amd", "csrc", obj_name)
-    objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-    if not (os.path.exists(obj) and os.path.exists(objdump)):
-        pytest.skip("needs the built object file and llvm-objdump")
+    if not (os.path.exists(obj) and os.path.exists(LLVM_BIN + tool_args[0])):
+        pytest.skip("needs the built object file and " + tool_args[0])
     with tempfile.TemporaryDirectory() as tmp:
-        subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objcopy", "--dump-section", ".hip_fatbin=" + tmp + "/fb.bin", obj],
+        subprocess.run([LLVM_BIN + "llvm-objcopy", "--dump-section", ".hip_fatbin=" + tmp + "/fb.bin", obj],
                        check=True, capture_output=True)
-        subprocess.run(["/opt/rocm/lib/llvm/bin/clang-offload-bundler", "--type=o", "--unbundle",
+        subprocess.run([LLVM_BIN + "clang-offload-bundler", "--type=o", "--unbundle",
                         "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + tmp + "/fb.bin", "--output=" + tmp + "/dev.o"],
                        check=True, capture_output=True)
-        return subprocess.run([objdump, "-d", tmp + "/dev.o"], check=True, capture_output=True, text=True).stdout
+        return subprocess.run([LLVM_BIN + tool_args[0]] + list(tool_args[1:]) + [tmp + "/dev.o"], check=True,
+                              capture_output=True, text=True).stdout
+
+
+def _device_asm(obj_name):
+    return device_object_output(obj_name, ["llvm-objdump", "-d"])
 
 
 def _kernel_body(asm, mangled_fragment):
