@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define DPC_ABI_VERSION 14
+#define DPC_ABI_VERSION 15
 #define DPC_MAX_TAPS 63 /* longest 1-D smoothing kernel accepted (pc_gauss_kernel_size) */
 /* Size limits, checked by every entry point (DPC_ERR_SHAPE): grid sides <= 1024 (10-bit cell indices in a point record),
  * B <= 65535, and N <= DPC_MAX_POINTS points per cloud: a voxel's splat weights are summed in 64-bit fixed point with 44
@@ -171,12 +171,26 @@ int dpc_project_bwd(const DpcParams* p, const float* pc, const float* q, const f
                     const float* grid_wh, const uint64_t* mask, const float* trans /* from fwd, or NULL */,
                     const float* dproj, const float* dgrid_wh, float* dpc, float* dsmall, void* workspace, void* stream);
 
-/* The same chain with the caller's silhouette loss fused in: add_proj_loss /
- * proj_loss_pose_candidates (dpc/models/model_pc_to.py:339-385, 410-440).  Cloud b is pose candidate b % K of
- * sample b / K; gt [B/K, H, W] is the mask already pooled to the silhouette size.  The ray-march kernel
- * accumulates each cloud's sum of squared differences, a one-block finalize picks argmin over K (first minimum)
- * and writes loss = sum_s min_k sse / S.  In the backward dproj = 2 (proj - gt) / S * dloss is formed on the fly
- * (never stored) and losing candidates skip all work -- their gradients are exact zeros.
+/* The same chain with the caller's silhouette loss fused in: the whole of add_proj_loss /
+ * proj_loss_pose_candidates (dpc/models/model_pc_to.py:339-385, 410-440), mask pooling and per-view weights included.
+ * Cloud b is pose candidate b % K of sample b / K, S = B / K.
+ *   gt        [S, f*H, f*W]: the masks (the reference's inputs["masks"], [S,1,Hm,Wm] or [S,Hm,Wm,1]), f = gt_factor >= 1,
+ *             f*H and f*W <= 1024 (DPC_ERR_SHAPE otherwise, before any launch).  The kernels pool them where they read a
+ *             pixel: gt[s,y,x] = (sum_{i<f} sum_{j<f} masks[s, f*y+i, f*x+j]) / (f*f), summed in fp32 in row-major window
+ *             order and divided (not multiplied by the reciprocal) -- ATen's avg_pool2d order, so the pooled values are the
+ *             bits of F.avg_pool2d(masks, f) (nn.AvgPool2d(gt_size // pred_size), :346-354).  f = 1: masks already pooled
+ *             to the silhouette size (ABI 14's gt).  No pooled copy is ever written.
+ *   weights   [S] | NULL: w_s, the reference's inputs["valid_samples"] (cfg.variable_num_views, :432-436); NULL = all ones.
+ * Formulas (sse is UNWEIGHTED, as in ABI 14; the selection is unweighted, like the reference's all_loss.argmin):
+ *   sse[c]    = sum_pix (gt[c/K] - proj[c])^2
+ *   winner[s] = first argmin_k sse[s*K + k]
+ *   loss      = sum_s w_s^2 sse[s*K + winner[s]] / S          (w squared: the reference weights the residual, then squares)
+ *   d loss / d proj[c] = 2 w_s^2 (proj[c] - gt[s]) / S * dloss for the winner c of sample s, 0 for the others
+ * K = 1 is the min-of-1 case of the same formula.  The ray-march kernel accumulates each cloud's sse, a one-block finalize
+ * picks the winners and writes the loss.  In the backward d loss / d proj is formed on the fly (never stored) and losing
+ * candidates skip all work -- their gradients are exact zeros.  With the column backward fused in (below) the loss is summed
+ * in fixed point, so it is the same bits on every run; all-one weights give the bits of weights = NULL, and the weights
+ * have no bound (a NaN weight makes the loss NaN).
  *   fwd outputs: proj [B,H,W], trans [B,H,W], sse [B], loss [1], winner [B/K] int32 (+ tr_pc|NULL, cells, grid_wh, mask);
  *                sse_tiles [B, ceil(H*W/256)] scratch: the ray tiles' squared errors, added in tile order by the finalize
  *                launch (no float atomics: sums, winners and loss are the same bits on every run); may be NULL only when
@@ -193,14 +207,14 @@ int dpc_project_bwd(const DpcParams* p, const float* pc, const float* q, const f
  * the backward may be called again on the same forward.  Pass NULLs / 0 to keep the two halves apart. */
 int dpc_project_loss_fwd(const DpcParams* p, const float* pc, const float* q, const float* t, const float* f,
                          const float* s, const float* host_kern_xy, const float* host_kern_z, const float* gt,
-                         int num_candidates, float* tr_pc, void* cells, float* grid_wh, uint64_t* mask, float* proj,
-                         float* trans, float* sse, float* sse_tiles, float* loss, int32_t* winner, void* bwd_workspace,
-                         float* bwd_dsmall, int* column_backward_done, void* stream);
+                         int gt_factor, const float* weights, int num_candidates, float* tr_pc, void* cells, float* grid_wh,
+                         uint64_t* mask, float* proj, float* trans, float* sse, float* sse_tiles, float* loss, int32_t* winner,
+                         void* bwd_workspace, float* bwd_dsmall, int* column_backward_done, void* stream);
 int dpc_project_loss_bwd(const DpcParams* p, const float* pc, const float* q, const float* t, const float* f,
                          const float* s, const float* host_kern_xy, const float* host_kern_z, const void* cells,
                          const float* grid_wh, const uint64_t* mask, const float* proj, const float* trans,
-                         const float* gt, int num_candidates, const int32_t* winner, const float* dloss,
-                         int column_backward_done, float* dpc, float* dsmall, void* workspace, void* stream);
+                         const float* gt, int gt_factor, const float* weights, int num_candidates, const int32_t* winner,
+                         const float* dloss, int column_backward_done, float* dpc, float* dsmall, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * The whole step in ONE call: dpc_project_loss_fwd followed by dpc_project_loss_bwd -- four launches (one pose candidate per
@@ -209,15 +223,16 @@ int dpc_project_loss_bwd(const DpcParams* p, const float* pc, const float* q, co
  * per step instead of replaying a captured HIP graph of the two calls: the same kernels, the same results bit for bit, and
  * no graph (on MI355X / ROCm 7.2 the eager native sequence is 2-3 us per step FASTER than the replayed graph: 55.3 against
  * 57.2-58.2 us at B = 32, N = 8000, 64^3; host cost of the call 18 us, well under the GPU time).
- *   num_candidates, trans, sse_tiles, fwd_dsmall, dsmall, workspace, dloss: as in the two calls above (trans and sse_tiles
+ *   gt, gt_factor, weights, num_candidates, trans, sse_tiles, fwd_dsmall, dsmall, workspace, dloss: as in the two calls above
+ *   (masks at f times the silhouette's size are pooled inside the kernels: no pooling launch in front of the step; trans and sse_tiles
  *   are needed when the column backward is not fused into the forward, i.e. always for K > 1; may be NULL for K = 1 on the
  *   32/64/128-deep grids).
  * ------------------------------------------------------------------------------------------------- */
 int dpc_project_loss_step(const DpcParams* p, const float* pc, const float* q, const float* t, const float* f,
                           const float* s, const float* host_kern_xy, const float* host_kern_z, const float* gt,
-                          int num_candidates, void* cells, float* grid_wh, uint64_t* mask, float* proj, float* trans,
-                          float* sse, float* sse_tiles, float* loss, int32_t* winner, void* workspace, float* fwd_dsmall,
-                          const float* dloss, float* dpc, float* dsmall, void* stream);
+                          int gt_factor, const float* weights, int num_candidates, void* cells, float* grid_wh, uint64_t* mask,
+                          float* proj, float* trans, float* sse, float* sse_tiles, float* loss, int32_t* winner, void* workspace,
+                          float* fwd_dsmall, const float* dloss, float* dpc, float* dsmall, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Stage-level entry points (one per reference function), used for the sub-stage API and to cross-check the
@@ -277,13 +292,15 @@ int dpc_drc_bwd(const DpcParams* p, const float* vox, const float* dproj, const 
                 const float* ddepth, float* dvox, void* stream);
 
 /* Caller-side silhouette loss fused with its gradient: add_proj_loss /
- * proj_loss_pose_candidates (dpc/models/model_pc_to.py:339-385, 410-440).  gt [S, n_pix] is the ground-truth
- * mask already pooled to the silhouette size, pred [S*K, n_pix] the K candidate silhouettes per sample.
- * Per sample the candidate with the smallest sum of squared differences wins (first minimum, like
- * torch.argmin); loss = sum over winners (gt-pred)^2 / S.  Outputs: loss_part [S] (sum them for the loss),
- * winner [S], dpred [S*K, n_pix] = d loss / d pred (zero for losing candidates). */
-int dpc_silhouette_loss(const float* gt, const float* pred, int S, int K, int n_pix, float* loss_part, int32_t* winner,
-                        float* dpred, void* stream);
+ * proj_loss_pose_candidates (dpc/models/model_pc_to.py:339-385, 410-440), the formulas of dpc_project_loss_fwd.
+ * gt [S, f*H, f*W] the masks, pooled f x f inside the kernel like there (f = gt_factor >= 1; f > 1 needs f*H, f*W <= 1024;
+ * f = 1 reads any [S, H*W]), weights [S] | NULL (= 1), pred [S*K, H*W] the K candidate silhouettes per sample.
+ * Per sample the candidate with the smallest (unweighted) sum of squared differences wins (first minimum, like
+ * torch.argmin); loss = sum over winners w_s^2 (gt-pred)^2 / S.  Outputs: loss_part [S] (sum them for the loss),
+ * winner [S], dpred [S*K, H*W] = d loss / d pred (zero for losing candidates).  ABI 15: gt_factor, weights, and H, W in
+ * place of n_pix. */
+int dpc_silhouette_loss(const float* gt, int gt_factor, const float* weights, const float* pred, int S, int K, int H, int W,
+                        float* loss_part, int32_t* winner, float* dpred, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Evaluation side: point_cloud_distance (dpc/util/point_cloud_distance.py:25-40), the kernel of

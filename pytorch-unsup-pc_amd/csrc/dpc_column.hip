@@ -11,10 +11,11 @@ namespace {
 
 // The unfused ray march leaves one squared-error partial per (cloud, ray tile); here they are added in tile order (so the
 // clouds' sums, the winners and the loss are the same bits on every run), the best pose candidate of every sample is
-// picked and the loss formed.  One block.
+// picked (unweighted, like the reference's argmin) and the loss formed: sum_s w_s^2 min_k sse / S.  One block.
 // (as a device function: k_zcol_bwd's first workgroup runs the same code when the selection is folded into the backward)
 __device__ inline void loss_finalize_block(const float* __restrict__ sse_tiles, int ntile, float* __restrict__ sse, int S, int K,
-                                           float inv_S, float* __restrict__ loss, int* __restrict__ winner, float* red) {
+                                           float inv_S, const float* __restrict__ weights, float* __restrict__ loss,
+                                           int* __restrict__ winner, float* red) {
   // one thread per cloud adds its tiles (independent loads, tile order), then one thread per sample picks the winner
   for (int cloud = threadIdx.x; cloud < S * K; cloud += blockDim.x) {
     float v = 0.f;
@@ -31,6 +32,10 @@ __device__ inline void loss_finalize_block(const float* __restrict__ sse_tiles, 
       if (k == 0 || v < best) { best = v; bk = k; }  // first minimum wins, like torch.argmin
     }
     winner[smp] = bk;
+    if (weights != nullptr) {
+      const float w = weights[smp];
+      best *= w * w;
+    }
     acc += best;
   }
   acc = wave_sum(acc);
@@ -44,10 +49,10 @@ __device__ inline void loss_finalize_block(const float* __restrict__ sse_tiles, 
 }
 
 __global__ __launch_bounds__(256) void k_loss_finalize(const float* __restrict__ sse_tiles, int ntile, float* __restrict__ sse,
-                                                       int S, int K, float inv_S, float* __restrict__ loss,
-                                                       int* __restrict__ winner) {
+                                                       int S, int K, float inv_S, const float* __restrict__ weights,
+                                                       float* __restrict__ loss, int* __restrict__ winner) {
   __shared__ float red[256 / DPC_WAVE];
-  loss_finalize_block(sse_tiles, ntile, sse, S, K, inv_S, loss, winner, red);
+  loss_finalize_block(sse_tiles, ntile, sse, S, K, inv_S, weights, loss, winner, red);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -68,7 +73,7 @@ __device__ inline void zcol_fwd_epilogue(const DpcParams& P, const RayConst& rc,
     proj[(size_t)b * HW + pix] = pr;
     if (trans_out != nullptr) trans_out[(size_t)b * HW + ray] = (float)trans;
     if (la.gt != nullptr) {
-      const float d = la.gt[(size_t)(b / la.K) * HW + pix] - pr;
+      const float d = gt_pixel(la, b / la.K, P.H, P.W, pix) - pr;
       sq = d * d;
     }
   }
@@ -137,6 +142,50 @@ __global__ __launch_bounds__(kColThreads, (DD <= 64 ? 4 : 2)) void k_zcol_fwd(Dp
 #ifndef DPC_ZFB_2WAVE_MAX
 #define DPC_ZFB_2WAVE_MAX 128  // deepest column that is compiled for two waves per SIMD (256 VGPRs per lane)
 #endif
+// The weighted batch loss of the fused K = 1 path, sum_b w_b^2 sse[b] / S, formed by the workgroup whose cloud completed the
+// batch: every cloud's word is final by then (each cloud's last tile added to it before it added to the batch word), and is
+// read back with agent-scope loads.  Each cloud's weighted share is rounded to the batch word's fixed point exactly as
+// sse_share rounds it and added as a 128-bit integer (two words, order-free), so w = 1 gives the bits of the unweighted loss;
+// shares beyond 2^62 units (large weights: there is no cap) and NaN go into a double added in a fixed order.
+__device__ inline void weighted_batch_loss(const unsigned long long* __restrict__ words, SseFormat cf, SseFormat bf,
+                                                 const float* __restrict__ weights, int B, float inv_S, float* loss) {
+  __shared__ unsigned long long part_lo[kColThreads], part_hi[kColThreads];
+  __shared__ double part_big[kColThreads];
+  const double unit = (double)(1ull << bf.frac);
+  unsigned long long lo = 0ull, hi = 0ull;
+  double big = 0.0;
+  for (int c = threadIdx.x; c < B; c += kColThreads) {
+    const unsigned long long word = __hip_atomic_load(words + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const double v = sse_total(cf, word) * (double)::sample_weight2(weights, c);
+    const double x = v * unit + 0.5;
+    if (v >= 0.0 && x < 4611686018427387904.0) {   // 2^62
+      const unsigned long long share = (unsigned long long)x;
+      lo += share;
+      hi += lo < share ? 1ull : 0ull;
+    } else {
+      big += v;   // huge, or NaN (a NaN weight or a poisoned cloud): the loss is NaN like the reference's
+    }
+  }
+  part_lo[threadIdx.x] = lo;
+  part_hi[threadIdx.x] = hi;
+  part_big[threadIdx.x] = big;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    lo = hi = 0ull;
+    big = 0.0;
+    const int n = B < kColThreads ? B : kColThreads;   // the threads that held clouds
+#pragma unroll 8
+    for (int i = 0; i < n; ++i) {
+      lo += part_lo[i];
+      hi += part_hi[i] + (lo < part_lo[i] ? 1ull : 0ull);
+      big += part_big[i];
+    }
+    double tot = (double)lo * (1.0 / unit);   // hi == 0, big == 0: the expression of sse_total
+    if (hi != 0ull) tot += (double)hi * (18446744073709551616.0 / unit);
+    *loss = (float)((tot + big) * (double)inv_S);
+  }
+}
+
 template <int DD, int RB, int RPL>
 __global__ __launch_bounds__(kColThreads, (RPL * DD <= DPC_ZFB_2WAVE_MAX ? 2 : 1))
 void k_zcol_fwdbwd(DpcParams P, RayHost rh, const float* __restrict__ Tbuf, const float* __restrict__ s, TapsT<RB> taps_arg,
@@ -153,6 +202,29 @@ void k_zcol_fwdbwd(DpcParams P, RayHost rh, const float* __restrict__ Tbuf, cons
   const RayConst rc = ray_const(rh, s, b);
   float sq = 0.f, ds_acc = 0.f;
   float y[DD][RPL], g[RPL], gT[RPL];
+  // The ground truth is read HERE, before the column is loaded: one vec load at the silhouette's size (gt_factor 1), or the
+  // f x f windows of the masks, each window row added into the RPL accumulators as it arrives, in row-major window order,
+  // and divided by f*f: the bits of F.avg_pool2d (pooled_mask, dpc_common.h).  A conditional load or the window loop next to
+  // the live y column, where the f = 1 load used to sit, cost ~65 VGPRs.
+  // w_b^2 (K == 1: sample == cloud), read up front as well: block-uniform, a scalar load (loaded next to the live column it
+  // cost as many VGPRs as the pooling loop)
+  const float w2 = sample_weight2(la, b);
+  vec gpool;
+  if (live && la.gt_factor == 1) {
+    gpool = *reinterpret_cast<const vec*>(la.gt + (size_t)b * HW + (P.H - 1 - ray / P.W) * P.W + (ray - (ray / P.W) * P.W));
+  } else if (live) {
+    const int f = la.gt_factor, Wm = f * P.W, prow = P.H - 1 - ray / P.W, pcol = ray - (ray / P.W) * P.W;
+    const float* m = la.gt + ((size_t)b * P.H + prow) * f * Wm + (size_t)pcol * f;
+#pragma unroll
+    for (int r = 0; r < RPL; ++r) gpool[r] = 0.f;
+    for (int i = 0; i < f; ++i)
+#pragma unroll
+      for (int r = 0; r < RPL; ++r)
+        for (int j = 0; j < f; ++j) gpool[r] += m[(size_t)i * Wm + r * f + j];
+    const float area = (float)(f * f);
+#pragma unroll
+    for (int r = 0; r < RPL; ++r) gpool[r] = gpool[r] / area;
+  }
   if (live) {
     // Column loads and dT stores go through buffer descriptors of this cloud's two grids: ONE 32-bit lane offset (the ray)
     // for all of them, the plane offsets z*HW*4 in SGPRs -- the flat form cost a 64-bit vector add per access (135 of the
@@ -214,12 +286,13 @@ void k_zcol_fwdbwd(DpcParams P, RayHost rh, const float* __restrict__ Tbuf, cons
       for (int r = 0; r < RPL; ++r) pr[r] = __builtin_nanf("");
     *reinterpret_cast<vec*>(proj + (size_t)b * HW + pix) = pr;
     if (DPC_ABL(17)) return;  // diagnostic: forward only
-    const vec gtv = *reinterpret_cast<const vec*>(la.gt + (size_t)b * HW + pix);  // K == 1: sample == cloud
+    const vec gtv = gpool;   // K == 1: sample == cloud; read at the top of the kernel
+    const float gscale = 2.0f * la.inv_S * w2;
 #pragma unroll
     for (int r = 0; r < RPL; ++r) {
       const float diff = pr[r] - gtv[r];
       sq = fmaf(diff, diff, sq);
-      g[r] = 2.0f * la.inv_S * diff;
+      g[r] = gscale * diff;
       gT[r] = g[r] * (float)tr[r];
     }
   }
@@ -293,7 +366,9 @@ void k_zcol_fwdbwd(DpcParams P, RayHost rh, const float* __restrict__ Tbuf, cons
   ds_acc = wave_sum(ds_acc);
   if ((threadIdx.x & 63) == 0) red[1][threadIdx.x >> 6] = ds_acc;
   __syncthreads();
+  __shared__ int s_last;   // weighted loss: this block's cloud completed the batch
   if (threadIdx.x == 0) {
+    s_last = 0;
     float dst = 0.f;
     for (int i = 0; i < kColThreads / DPC_WAVE; ++i) dst += red[1][i];
     // k_gather_hw sums n_ds_part partials per cloud (one per kColThreads rays); with RPL > 1 this grid has fewer blocks
@@ -304,10 +379,19 @@ void k_zcol_fwdbwd(DpcParams P, RayHost rh, const float* __restrict__ Tbuf, cons
       // The batch loss the same way, one level up: the clouds' exact sums go into one more 64-bit word and the cloud that
       // arrives last writes the loss -- integer adds again, so the loss is bit-identical from run to run (float atomics
       // here differed in the last bits with the arrival order).
+      // With weights the word carries the unweighted sums all the same (they always fit its field) and counts the clouds;
+      // the block that arrives last forms the weighted loss below.
       const unsigned long long cmine = sse_share(bf, tot, (double)kTileSseCap * bk.nx);
       const unsigned long long cbefore = __hip_atomic_fetch_add(tickets + bk.ny, cmine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (sse_complete(bf, cbefore, bk.ny)) *la.loss_direct = (float)(sse_total(bf, cbefore + cmine) * (double)la.inv_S);
+      if (sse_complete(bf, cbefore, bk.ny)) {
+        if (la.weights == nullptr) *la.loss_direct = (float)(sse_total(bf, cbefore + cmine) * (double)la.inv_S);
+        else s_last = 1;
+      }
     }
+  }
+  if (la.weights != nullptr) {   // block-uniform
+    __syncthreads();
+    if (s_last) weighted_batch_loss(tickets, cf, bf, la.weights, bk.ny, la.inv_S, la.loss_direct);
   }
   if (bk.x == 0 && threadIdx.x < DPC_SMALL_COLS) dsmall[(size_t)threadIdx.x * bk.ny + b] = 0.f;  // [col][B]
   if (bk.x == 0 && threadIdx.x == 0) cg_count[b] = 0u;  // k_gather_hw's arrival counter of this cloud
@@ -361,8 +445,9 @@ __device__ inline float ray_grad(const DpcParams& P, const LossArgs& la, const f
   const int yrow = ray / P.W, x = ray - yrow * P.W;
   const int pix = (P.H - 1 - yrow) * P.W + x;
   if (la.gt == nullptr) return dproj[(size_t)b * HW + pix];
+  const int smp = b / la.K;
   const float up = la.dloss ? *la.dloss : 1.0f;
-  return 2.0f * la.inv_S * up * (proj[(size_t)b * HW + pix] - la.gt[(size_t)(b / la.K) * HW + pix]);
+  return 2.0f * la.inv_S * up * sample_weight2(la, smp) * (proj[(size_t)b * HW + pix] - gt_pixel(la, smp, P.H, P.W, pix));
 }
 
 // b: the cloud of this workgroup; the small gradients of clouds [zero_lo, zero_lo + zero_n) are zeroed by part 0
@@ -426,7 +511,7 @@ __global__ __launch_bounds__(kColThreads, 2) void k_zcol_bwd(DpcParams P, RayHos
     __syncthreads();
     win = s_win;
     if (blockIdx.x == 0)   // ... and ONE workgroup leaves sse, winner and the loss behind, bit for bit what the separate launch would
-      loss_finalize_block(la.sse_tiles, la.ntile, la.sse, bk.ny, la.K, la.inv_S, la.loss_write, la.winner_write, fin_red);
+      loss_finalize_block(la.sse_tiles, la.ntile, la.sse, bk.ny, la.K, la.inv_S, la.weights, la.loss_write, la.winner_write, fin_red);
   } else if (wo) {
     win = la.winner[bk.y];
   }
@@ -434,6 +519,7 @@ __global__ __launch_bounds__(kColThreads, 2) void k_zcol_bwd(DpcParams P, RayHos
   float ds_acc = 0.f;
   if (ray < HW && (wo || !cloud_loses(la, b))) {
     const RayConst rc = ray_const(rh, s, b);
+    const float g = ray_grad(P, la, dproj, proj, b, ray);   // before the column is loaded: the pooling loop keeps no column live
     float c[DD], d[DD];
     const __amdgpu_buffer_rsrc_t src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Tin + (size_t)b * DD * HW), 0, DD * HW * 4, 0x00020000);
 #pragma unroll
@@ -456,7 +542,6 @@ __global__ __launch_bounds__(kColThreads, 2) void k_zcol_bwd(DpcParams P, RayHos
       }
       Tf = (float)trans;
     }
-    const float g = ray_grad(P, la, dproj, proj, b, ray);
     const __amdgpu_buffer_rsrc_t dst = __builtin_amdgcn_make_buffer_rsrc(dT + (size_t)b * DD * HW, 0, DD * HW * 4, 0x00020000);
     const float* extra = dgrid_extra ? dgrid_extra + (size_t)b * DD * HW + ray : nullptr;  // gradient arriving at grid_wh itself
     // streaming over z: forward taps -> d(v2) -> adjoint taps, RB voxels behind
@@ -624,9 +709,9 @@ int launch_zcol_bwd(const DpcParams* p, const float* host_kern_z, const TapPlan&
   return launch_ok();
 }
 
-int launch_loss_finalize(const float* sse_tiles, int ntile, float* sse, int S, int K, float inv_S, float* loss, int32_t* winner,
-                         hipStream_t st) {
-  DPC_LAUNCH("k_loss_finalize", dpc_kid("k_loss_finalize"), k_loss_finalize, dim3(1), dim3(256), 0, st, sse_tiles, ntile, sse, S, K, inv_S, loss, winner);
+int launch_loss_finalize(const float* sse_tiles, int ntile, float* sse, int S, int K, float inv_S, const float* weights, float* loss,
+                         int32_t* winner, hipStream_t st) {
+  DPC_LAUNCH("k_loss_finalize", dpc_kid("k_loss_finalize"), k_loss_finalize, dim3(1), dim3(256), 0, st, sse_tiles, ntile, sse, S, K, inv_S, weights, loss, winner);
   return launch_ok();
 }
 

@@ -370,6 +370,27 @@ __device__ inline float dpp_move(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
 }
 
+// Ground truth of silhouette pixel `pix` (= row * W + x) of sample `smp` from masks [S, f*H, f*W].  f > 1: the mean of the
+// pixel's f x f window, summed in fp32 in row-major window order and divided by f*f -- the order of ATen's avg_pool2d on CPU
+// and GPU, so the same bits as F.avg_pool2d(masks, f).  f = 1: the mask as it is.
+__device__ inline float pooled_mask(const float* __restrict__ masks, int f, int smp, int H, int W, int pix) {
+  if (f == 1) return masks[(size_t)smp * H * W + pix];
+  const int py = pix / W, px = pix - py * W, Wm = f * W;
+  const float* m = masks + ((size_t)smp * H + py) * f * Wm + (size_t)px * f;
+  float acc = 0.f;
+  for (int i = 0; i < f; ++i)
+    for (int j = 0; j < f; ++j) acc += m[(size_t)i * Wm + j];
+  return acc / (float)(f * f);
+}
+
+// w^2 of sample `smp` (weights [S] | nullptr = 1): the reference weights the residual before squaring it
+// (dpc/models/model_pc_to.py:432-436)
+__device__ inline float sample_weight2(const float* __restrict__ weights, int smp) {
+  if (weights == nullptr) return 1.0f;
+  const float w = weights[smp];
+  return w * w;
+}
+
 __device__ inline float wave_sum(float v) {
   v += dpp_move<0xb1>(v);   // quad_perm:[1,0,3,2]
   v += dpp_move<0x4e>(v);   // quad_perm:[2,3,0,1]

@@ -132,6 +132,12 @@ int project_bwd_impl(const DpcParams* p, const float* pc, const float* q, const 
 
 const LossArgs kNoLoss{nullptr, nullptr, nullptr, nullptr, 1, 1.0f, nullptr, nullptr, 0, nullptr};
 
+// The masks of the fused loss are gt_factor times the silhouette's size on each side, within the 1024 limit of the grid sides.
+// Checked before anything is launched.
+bool gt_factor_ok(const DpcParams* p, int gt_factor) {
+  return gt_factor >= 1 && (long long)gt_factor * p->H <= 1024 && (long long)gt_factor * p->W <= 1024;
+}
+
 }  // namespace
 
 extern "C" {
@@ -154,11 +160,11 @@ int dpc_project_bwd(const DpcParams* p, const float* pc, const float* q, const f
 
 int dpc_project_loss_fwd(const DpcParams* p, const float* pc, const float* q, const float* t, const float* f,
                          const float* s, const float* host_kern_xy, const float* host_kern_z, const float* gt,
-                         int num_candidates, float* tr_pc, void* cells, float* grid_wh, uint64_t* mask, float* proj,
-                         float* trans, float* sse, float* sse_tiles, float* loss, int32_t* winner, void* bwd_workspace,
-                         float* bwd_dsmall, int* column_backward_done, void* stream) {
+                         int gt_factor, const float* weights, int num_candidates, float* tr_pc, void* cells, float* grid_wh,
+                         uint64_t* mask, float* proj, float* trans, float* sse, float* sse_tiles, float* loss, int32_t* winner,
+                         void* bwd_workspace, float* bwd_dsmall, int* column_backward_done, void* stream) {
   if (!p || !loss) return DPC_ERR_NULL;
-  if (num_candidates < 1 || p->B % num_candidates != 0) return DPC_ERR_SHAPE;
+  if (num_candidates < 1 || p->B % num_candidates != 0 || !gt_factor_ok(p, gt_factor)) return DPC_ERR_SHAPE;
   if (p->B == 0)   // no clouds (an empty shard): the loss of nothing is 0
     return zero_words_async(loss, 1, (hipStream_t)stream) ? DPC_OK : DPC_ERR_LAUNCH;
   if (!gt || !sse || !winner) return DPC_ERR_NULL;
@@ -169,21 +175,23 @@ int dpc_project_loss_fwd(const DpcParams* p, const float* pc, const float* q, co
                     can_fuse_column_backward(p, pz, num_candidates, grid_wh, proj, gt, bwd_workspace);
   if (!fuse && !sse_tiles) return DPC_ERR_NULL;  // the unfused ray march leaves per-tile partials for the finalize launch
   const LossArgs la{gt, sse, nullptr, nullptr, num_candidates, S > 0 ? 1.0f / (float)S : 0.f,
-                    fuse ? loss : nullptr, fuse ? winner : nullptr, 0, fuse ? nullptr : sse_tiles};
+                    fuse ? loss : nullptr, fuse ? winner : nullptr, 0, fuse ? nullptr : sse_tiles, nullptr, nullptr, 0,
+                    gt_factor, weights};
   if (column_backward_done) *column_backward_done = fuse ? 1 : 0;
   int rc = project_fwd_impl(p, pc, q, t, f, s, host_kern_xy, host_kern_z, tr_pc, cells, nullptr, grid_wh, nullptr, mask,
                             proj, trans, la, fuse ? bwd_workspace : nullptr, fuse ? bwd_dsmall : nullptr,
                             (hipStream_t)stream);
   if (rc != DPC_OK || p->B == 0 || fuse) return rc;
-  return launch_loss_finalize(sse_tiles, col_tiles(p), sse, S, num_candidates, la.inv_S, loss, winner, (hipStream_t)stream);
+  return launch_loss_finalize(sse_tiles, col_tiles(p), sse, S, num_candidates, la.inv_S, weights, loss, winner, (hipStream_t)stream);
 }
 
 int dpc_project_loss_step(const DpcParams* p, const float* pc, const float* q, const float* t, const float* f,
                           const float* s, const float* host_kern_xy, const float* host_kern_z, const float* gt,
-                          int num_candidates, void* cells, float* grid_wh, uint64_t* mask, float* proj, float* trans,
-                          float* sse, float* sse_tiles, float* loss, int32_t* winner, void* workspace, float* fwd_dsmall,
-                          const float* dloss, float* dpc, float* dsmall, void* stream) {
-  if (!workspace || !fwd_dsmall) return (p && p->B == 0) ? dpc_project_loss_fwd(p, pc, q, t, f, s, host_kern_xy, host_kern_z, gt, num_candidates, nullptr, cells, grid_wh, mask, proj, trans, sse, sse_tiles, loss, winner, nullptr, nullptr, nullptr, stream) : DPC_ERR_NULL;
+                          int gt_factor, const float* weights, int num_candidates, void* cells, float* grid_wh, uint64_t* mask,
+                          float* proj, float* trans, float* sse, float* sse_tiles, float* loss, int32_t* winner, void* workspace,
+                          float* fwd_dsmall, const float* dloss, float* dpc, float* dsmall, void* stream) {
+  if (p && !gt_factor_ok(p, gt_factor)) return DPC_ERR_SHAPE;
+  if (!workspace || !fwd_dsmall) return (p && p->B == 0) ? dpc_project_loss_fwd(p, pc, q, t, f, s, host_kern_xy, host_kern_z, gt, gt_factor, weights, num_candidates, nullptr, cells, grid_wh, mask, proj, trans, sse, sse_tiles, loss, winner, nullptr, nullptr, nullptr, stream) : DPC_ERR_NULL;
   const int K = num_candidates;
   // K candidates, a column depth and a z kernel the specialised column backward covers: the min-of-K selection rides in
   // that launch (k_zcol_bwd) instead of taking one of its own between forward and backward
@@ -191,34 +199,35 @@ int dpc_project_loss_step(const DpcParams* p, const float* pc, const float* q, c
       (p->D == 32 || p->D == 64 || p->D == 128) && plan_taps(host_kern_z, p->taps_z).bucket >= 0) {
     const int S = p->B / K;
     const float inv_S = 1.0f / (float)S;
-    const LossArgs lf{gt, sse, nullptr, nullptr, K, inv_S, nullptr, nullptr, 0, sse_tiles, nullptr, nullptr, 0};
+    const LossArgs lf{gt, sse, nullptr, nullptr, K, inv_S, nullptr, nullptr, 0, sse_tiles, nullptr, nullptr, 0, gt_factor, weights};
     int rc = project_fwd_impl(p, pc, q, t, f, s, host_kern_xy, host_kern_z, nullptr, cells, nullptr, grid_wh, nullptr, mask, proj,
                               trans, lf, nullptr, nullptr, (hipStream_t)stream);
     if (rc != DPC_OK) return rc;
-    const LossArgs lb{gt, sse, winner, dloss, K, inv_S, nullptr, nullptr, 0, sse_tiles, winner, loss, col_tiles(p)};
+    const LossArgs lb{gt, sse, winner, dloss, K, inv_S, nullptr, nullptr, 0, sse_tiles, winner, loss, col_tiles(p), gt_factor, weights};
     return project_bwd_impl(p, pc, q, t, f, s, host_kern_xy, host_kern_z, cells, grid_wh, mask, nullptr, proj, trans, lb, dpc,
                             dsmall, workspace, nullptr, (hipStream_t)stream);
   }
   int column_done = 0;
-  int rc = dpc_project_loss_fwd(p, pc, q, t, f, s, host_kern_xy, host_kern_z, gt, num_candidates, nullptr, cells, grid_wh, mask,
-                                proj, trans, sse, sse_tiles, loss, winner, workspace, fwd_dsmall, &column_done, stream);
+  int rc = dpc_project_loss_fwd(p, pc, q, t, f, s, host_kern_xy, host_kern_z, gt, gt_factor, weights, num_candidates, nullptr,
+                                cells, grid_wh, mask, proj, trans, sse, sse_tiles, loss, winner, workspace, fwd_dsmall, &column_done,
+                                stream);
   if (rc != DPC_OK || p->B == 0) return rc;
-  return dpc_project_loss_bwd(p, pc, q, t, f, s, host_kern_xy, host_kern_z, cells, grid_wh, mask, proj, trans, gt, num_candidates,
-                              winner, dloss, column_done, dpc, dsmall, workspace, stream);
+  return dpc_project_loss_bwd(p, pc, q, t, f, s, host_kern_xy, host_kern_z, cells, grid_wh, mask, proj, trans, gt, gt_factor,
+                              weights, num_candidates, winner, dloss, column_done, dpc, dsmall, workspace, stream);
 }
 
 int dpc_project_loss_bwd(const DpcParams* p, const float* pc, const float* q, const float* t, const float* f,
                          const float* s, const float* host_kern_xy, const float* host_kern_z, const void* cells,
                          const float* grid_wh, const uint64_t* mask, const float* proj, const float* trans,
-                         const float* gt, int num_candidates, const int32_t* winner, const float* dloss,
-                         int column_backward_done, float* dpc, float* dsmall, void* workspace, void* stream) {
+                         const float* gt, int gt_factor, const float* weights, int num_candidates, const int32_t* winner,
+                         const float* dloss, int column_backward_done, float* dpc, float* dsmall, void* workspace, void* stream) {
   if (!p) return DPC_ERR_NULL;
-  if (num_candidates < 1 || p->B % num_candidates != 0) return DPC_ERR_SHAPE;
+  if (num_candidates < 1 || p->B % num_candidates != 0 || !gt_factor_ok(p, gt_factor)) return DPC_ERR_SHAPE;
   if (p->B == 0) return DPC_OK;  // no clouds: nothing to write
   if (!gt || !winner || !proj) return DPC_ERR_NULL;
   const int S = p->B / num_candidates;
   const LossArgs la{gt, nullptr, winner, dloss, num_candidates, S > 0 ? 1.0f / (float)S : 0.f, nullptr, nullptr,
-                    column_backward_done ? 1 : 0, nullptr};
+                    column_backward_done ? 1 : 0, nullptr, nullptr, nullptr, 0, gt_factor, weights};
   return project_bwd_impl(p, pc, q, t, f, s, host_kern_xy, host_kern_z, cells, grid_wh, mask, nullptr, proj, trans, la,
                           dpc, dsmall, workspace, nullptr, (hipStream_t)stream);
 }

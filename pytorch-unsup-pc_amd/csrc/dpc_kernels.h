@@ -592,11 +592,13 @@ __device__ inline float drc_voxel_bwd(const RayConst& r, float v2, float g, floa
 }
 
 // Fused silhouette loss (dpc/models/model_pc_to.py:339-385, 410-440): cloud b is candidate b % K of sample b / K.
-//   forward : sse[b] += sum_pixels (gt - proj)^2            (k_zcol_fwd epilogue; zeroed by k_splat_hw)
-//   finalize: winner[s] = argmin_k sse[s*K+k], loss = sum_s min_k sse / S      (k_loss_finalize)
-//   backward: dproj = winner ? 2 (proj - gt) / S * dloss : 0, formed on the fly; losing candidates do nothing
+//   forward : sse[b] += sum_pixels (gt - proj)^2            (k_zcol_fwd epilogue; zeroed by k_splat_hw; never weighted)
+//   finalize: winner[s] = argmin_k sse[s*K+k], loss = sum_s w_s^2 min_k sse / S      (k_loss_finalize)
+//   backward: dproj = winner ? 2 w_s^2 (proj - gt) / S * dloss : 0, formed on the fly; losing candidates do nothing
+// gt is the masks at gt_factor times the silhouette's size, average-pooled on the fly where a kernel reads a pixel (gt_pixel);
+// w_s = weights[s] (the reference's valid_samples), 1 when weights is nullptr.  Both are run-time values, uniform per launch.
 struct LossArgs {
-  const float* gt;      // [S, H*W] in image orientation (rows already flipped like proj); nullptr = no fused loss
+  const float* gt;      // [S, f*H, f*W] in image orientation (rows already flipped like proj); nullptr = no fused loss
   float* sse;           // [B]
   const int* winner;    // [S] (backward)
   const float* dloss;   // device scalar, gradient arriving at the loss (backward); nullptr = 1
@@ -612,7 +614,15 @@ struct LossArgs {
   int* winner_write;    // [S] | nullptr
   float* loss_write;    // [1]
   int ntile;            // ray tiles per cloud in sse_tiles
+  int gt_factor = 1;    // f >= 1: gt holds [S, f*H, f*W] masks, pooled f x f on the fly (1 = already the silhouette's size)
+  const float* weights = nullptr;  // [S] per-sample weights (valid_samples) | nullptr = all ones
 };
+
+// the loss's ground truth and weight of a sample (pooled_mask, sample_weight2: dpc_common.h)
+__device__ inline float gt_pixel(const LossArgs& la, int smp, int H, int W, int pix) {
+  return pooled_mask(la.gt, la.gt_factor, smp, H, W, pix);
+}
+__device__ inline float sample_weight2(const LossArgs& la, int smp) { return ::sample_weight2(la.weights, smp); }
 
 // ------------------------------------------------------------------------------------------------------
 // Host side
@@ -898,8 +908,8 @@ int launch_zcol_fwdbwd(const DpcParams* p, const float* host_kern_z, const TapPl
 int launch_zcol_bwd(const DpcParams* p, const float* host_kern_z, const TapPlan& pz, const float* grid_wh, const float* s,
                     const float* dproj, const float* proj, const float* trans, float* dT, float* ds_part, float* dsmall,
                     unsigned int* cg_count, const float* dgrid_extra, const LossArgs& la, hipStream_t st);
-int launch_loss_finalize(const float* sse_tiles, int ntile, float* sse, int S, int K, float inv_S, float* loss, int32_t* winner,
-                         hipStream_t st);
+int launch_loss_finalize(const float* sse_tiles, int ntile, float* sse, int S, int K, float inv_S, const float* weights, float* loss,
+                         int32_t* winner, hipStream_t st);
 // dpc_slab_xl.hip: the x-in-lanes slab kernels (64 x 64 planes, radius bucket 1..6); DPC_NO_XL builds keep the older kernels
 bool xl_applies(const DpcParams* p, int bucket);
 int launch_splat_xl(int bucket, const DpcParams* p, Cells cells, const float* kxy, const TapPlan& pxy, float* Tbuf, uint64_t* mask,

@@ -219,27 +219,28 @@ __global__ __launch_bounds__(kThreads) void k_drc_bwd(DpcParams P, const float* 
 
 // ------------------------------------------------------------------------------------------------------
 // Silhouette loss of the caller (dpc/models/model_pc_to.py:339-385,410-440), fused with its gradient:
-//   K == 1: loss = sum (gt - pred)^2 / S
-//   K  > 1: per sample pick the candidate with the smallest sum of squared differences (argmin over K),
-//           loss = sum over winners (gt - pred)^2 / S; losing candidates get zero gradient.
-// gt [S, n_pix] (already pooled to the silhouette size), pred [S*K, n_pix].  One block per sample.
-//   out: loss_part [S] (this sample's winning sum / S), winner [S] (int32), dpred [S*K, n_pix] (d loss / d pred)
+//   K == 1: loss = sum w^2 (gt - pred)^2 / S
+//   K  > 1: per sample pick the candidate with the smallest sum of squared differences (argmin over K, unweighted),
+//           loss = sum over winners w^2 (gt - pred)^2 / S; losing candidates get zero gradient.
+// gt [S, f*H, f*W]: the masks, average-pooled f x f on the fly (pooled_mask, dpc_common.h: the bits of F.avg_pool2d; f = 1 reads
+// them as they are), pred [S*K, H*W], weights [S] | nullptr (= 1).  One block per sample.
+//   out: loss_part [S] (this sample's weighted winning sum / S), winner [S] (int32), dpred [S*K, H*W] (d loss / d pred)
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void k_silhouette_loss(const float* __restrict__ gt, const float* __restrict__ pred,
-                                                              int K, int n_pix, float inv_S,
+__global__ __launch_bounds__(kThreads) void k_silhouette_loss(const float* __restrict__ gt, int gt_factor,
+                                                              const float* __restrict__ weights, const float* __restrict__ pred,
+                                                              int K, int H, int W, float inv_S,
                                                               float* __restrict__ loss_part, int* __restrict__ winner,
                                                               float* __restrict__ dpred) {
   __shared__ float red[kThreads / DPC_WAVE];
   __shared__ float best_val;
   __shared__ int best_k;
-  const int smp = blockIdx.x;
-  const float* g = gt + (size_t)smp * n_pix;
+  const int smp = blockIdx.x, n_pix = H * W;
   if (threadIdx.x == 0) { best_val = 0.f; best_k = 0; }
   for (int k = 0; k < K; ++k) {
     const float* p = pred + ((size_t)smp * K + k) * n_pix;
     float acc = 0.f;
     for (int i = threadIdx.x; i < n_pix; i += blockDim.x) {
-      const float d = g[i] - p[i];
+      const float d = pooled_mask(gt, gt_factor, smp, H, W, i) - p[i];
       acc = fmaf(d, d, acc);
     }
     acc = wave_sum(acc);
@@ -254,15 +255,16 @@ __global__ __launch_bounds__(kThreads) void k_silhouette_loss(const float* __res
   }
   __syncthreads();
   const int win = best_k;
+  const float w2 = sample_weight2(weights, smp);
   if (threadIdx.x == 0) {
-    loss_part[smp] = best_val * inv_S;
+    loss_part[smp] = w2 * best_val * inv_S;
     winner[smp] = win;
   }
   for (int k = 0; k < K; ++k) {
     const float* p = pred + ((size_t)smp * K + k) * n_pix;
     float* d = dpred + ((size_t)smp * K + k) * n_pix;
-    const float scale = k == win ? 2.f * inv_S : 0.f;
-    for (int i = threadIdx.x; i < n_pix; i += blockDim.x) d[i] = scale * (p[i] - g[i]);
+    const float scale = k == win ? 2.f * inv_S * w2 : 0.f;
+    for (int i = threadIdx.x; i < n_pix; i += blockDim.x) d[i] = scale * (p[i] - pooled_mask(gt, gt_factor, smp, H, W, i));
   }
 }
 
@@ -489,12 +491,13 @@ int dpc_smooth(const DpcParams* p, const float* host_kern_xy, const float* host_
   return launch_ok();
 }
 
-int dpc_silhouette_loss(const float* gt, const float* pred, int S, int K, int n_pix, float* loss_part, int32_t* winner,
-                        float* dpred, void* stream) {
-  if (S < 0 || K < 1 || n_pix < 1) return DPC_ERR_SHAPE;
+int dpc_silhouette_loss(const float* gt, int gt_factor, const float* weights, const float* pred, int S, int K, int H, int W,
+                        float* loss_part, int32_t* winner, float* dpred, void* stream) {
+  if (S < 0 || K < 1 || H < 1 || W < 1 || gt_factor < 1) return DPC_ERR_SHAPE;
+  if (gt_factor > 1 && ((long long)gt_factor * H > 1024 || (long long)gt_factor * W > 1024)) return DPC_ERR_SHAPE;
   if (S == 0) return DPC_OK;
   if (!gt || !pred || !loss_part || !winner || !dpred) return DPC_ERR_NULL;
-  hipLaunchKernelGGL(k_silhouette_loss, dim3(S), dim3(kThreads), 0, (hipStream_t)stream, gt, pred, K, n_pix,
+  hipLaunchKernelGGL(k_silhouette_loss, dim3(S), dim3(kThreads), 0, (hipStream_t)stream, gt, gt_factor, weights, pred, K, H, W,
                      1.0f / (float)S, loss_part, winner, dpred);
   return launch_ok();
 }

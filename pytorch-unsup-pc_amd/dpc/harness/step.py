@@ -7,7 +7,8 @@ student, learned occupancy scale, no rgb / depth / drc losses, no translation, f
     images [B*V,3,S,S] -> encoder -> ids [B*V,z]; the first view's id of every object -> decoder -> points [B,N,3]
     pose FC of every image -> K candidate quaternions + 1 student quaternion per image
     points, scales repeated V*K times (candidate-minor), optional point dropout
-    renderer + min-of-K silhouette loss in ONE call (dpc.render.pointcloud_project_loss)
+    renderer + min-of-K silhouette loss in ONE call (dpc.render.pointcloud_project_loss), which also pools the masks and
+    applies the per-view weights (valid_samples, cfg.variable_num_views)
     student loss against the winning candidate, (proj + student) * proj_weight, backward, Adam
 """
 import numpy as np
@@ -28,8 +29,9 @@ def pooled_masks(masks, size):
     return masks.permute(0, 2, 3, 1).contiguous()
 
 
-def student_loss(poses, student, winner, num_candidates, weight):
-    """add_student_loss (model_pc_to.py:442-489), rotation-difference form: 1 - <teacher, student>_w^2, teachers detached.
+def student_loss(poses, student, winner, num_candidates, weight, weights=None):
+    """add_student_loss (model_pc_to.py:442-489), rotation-difference form: 1 - <teacher, student>_w^2, teachers detached;
+    `weights` [S] | None: the per-view weights (valid_samples) of cfg.variable_num_views, NOT squared (:461-464, 480).
 
     The reference builds diff = normalise(teacher * conj(student)) and reads its w component.  That component is
     <teacher, student> / (|teacher| |student|) (the Hamilton product's norm is the product of the norms), which is what is
@@ -40,7 +42,10 @@ def student_loss(poses, student, winner, num_candidates, weight):
     s = student.double()
     dot = (t * s).sum(-1)
     norm2 = (t * t).sum(-1) * (s * s).sum(-1)
-    return (1.0 - dot * dot / norm2).sum() / winner.shape[0] * weight
+    term = 1.0 - dot * dot / norm2
+    if weights is not None:
+        term = term * weights.double()
+    return term.sum() / winner.shape[0] * weight
 
 
 def device_point_dropout(points, keep_prob, generator=None):
@@ -51,6 +56,14 @@ def device_point_dropout(points, keep_prob, generator=None):
     B, N = points.shape[0], points.shape[1]
     idx = R.point_dropout_indices(B, N, keep_prob, points.device, generator)
     return points.gather(1, idx.long().unsqueeze(-1).expand(B, idx.shape[1], 3))
+
+
+def _copy_static(static, new):
+    """Refill a captured step's static weights; a step captured without weights takes none, one captured with them needs them."""
+    if (static is None) != (new is None):
+        raise ValueError("valid_samples: give them at every replay exactly when the step was captured with them")
+    if static is not None:
+        static.copy_(new)
 
 
 class TrainStep:
@@ -85,8 +98,10 @@ class TrainStep:
         out.update(n.poseNet(enc["poses"]))
         return out
 
-    def loss(self, images, masks, global_step=None):
-        """Forward of one step; returns (total loss, dict of the pieces the reference's outputs dict would hold)."""
+    def loss(self, images, masks, global_step=None, valid_samples=None):
+        """Forward of one step; returns (total loss, dict of the pieces the reference's outputs dict would hold).
+        masks [B*V,1,Hm,Wm] go to the renderer as they are (it pools them to the silhouette size inside its kernels);
+        valid_samples [B*V] | None weights every view's projection and student terms (cfg.variable_num_views)."""
         cfg = self.cfg
         step = self.global_step if global_step is None else global_step
         out = self.predict(images)
@@ -107,19 +122,21 @@ class TrainStep:
                 host = np.stack([np.random.choice(all_points.shape[1], n_out, replace=False) for _ in range(clouds)])
                 point_index = torch.from_numpy(host.astype(np.int32)).to(all_points.device)
         kernel = R.smoothing_kernel(cfg, R.get_smooth_sigma(cfg, step))
-        gt = pooled_masks(masks, cfg.vox_size)
         proj_loss, proj_out, winner = R.pointcloud_project_loss(cfg, all_points, out["poses"], None, None, kernel,
-                                                                scaling_factor=all_scales, gt=gt, num_candidates=K,
-                                                                point_index=point_index, schedule=sched)
+                                                                scaling_factor=all_scales, gt=masks, num_candidates=K,
+                                                                point_index=point_index, schedule=sched,
+                                                                valid_samples=valid_samples)
+        gt = pooled_masks(masks, cfg.vox_size)   # for the outputs dict only: the loss above pooled the masks itself
         total = proj_loss.double()
         if K > 1 and cfg.pose_predictor_student:
-            out["student_loss"] = student_loss(out["poses"], out["pose_student"], winner, K, cfg.pose_predictor_student_loss_weight)
+            out["student_loss"] = student_loss(out["poses"], out["pose_student"], winner, K, cfg.pose_predictor_student_loss_weight,
+                                               valid_samples)
             total = total + out["student_loss"]
         total = total * cfg.proj_weight
         out.update(projs=proj_out["proj"], min_loss=winner, proj_loss=proj_loss, pooled_masks=gt)
         return total, out
 
-    def __call__(self, images, masks):
+    def __call__(self, images, masks, valid_samples=None):
         """zero_grad, forward, loss, backward, Adam step (train_to.py:112-131).  Returns the loss tensor (no host sync).
         With `grad_sync` set (dpc.render.parallel.OverlappedGradAllReduce) the ranks' gradients are summed while the
         backward runs; `sync_samples` = (objects of this rank, objects of all ranks)."""
@@ -127,7 +144,7 @@ class TrainStep:
             self.grad_sync.prepare(*self.sync_samples)
         else:
             self.optimizer.zero_grad(set_to_none=True)
-        total, _ = self.loss(images, masks)
+        total, _ = self.loss(images, masks, valid_samples=valid_samples)
         total.backward()
         if self.grad_sync is not None:
             self.grad_sync.finish()
@@ -162,13 +179,14 @@ class TrainStep:
         else:
             self._captured_schedule.update(kxy, kz, n_live)
 
-    def capture_compute(self, images, masks, warmup=2):
+    def capture_compute(self, images, masks, warmup=2, valid_samples=None):
         """The multi-rank variant of capture(): forward, loss and backward as ONE HIP graph whose backward accumulates
         straight into the flat buckets of `grad_sync` (every .grad is a view into them); the gradient exchange and Adam run
         eagerly after each replay (OverlappedGradAllReduce.reduce_now -- collectives are not captured).  The eager step
         hides the exchange under a launch-bound 4 ms backward; this one has a 2 ms step and exposes the exchange.
         `warmup` eager steps run first: the first one fixes which parameters take part in the exchange.
-        Returns replay(images, masks) -> loss tensor."""
+        Returns replay(images, masks[, valid_samples]) -> loss tensor (valid_samples: a static input like the masks, given
+        at every replay when the capture had it)."""
         sync = self.grad_sync
         if sync is None:
             raise RuntimeError("capture_compute() is the step with a gradient exchange (set grad_sync); use capture() without")
@@ -176,11 +194,12 @@ class TrainStep:
             raise RuntimeError("the reference's host-RNG point dropout uploads indices every step: not capturable; "
                                "use device_dropout=True")
         static_images, static_masks = images.clone(), masks.clone()
+        static_valid = None if valid_samples is None else valid_samples.clone()
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
-                self(static_images, static_masks)
+                self(static_images, static_masks, static_valid)
         torch.cuda.current_stream(self.device).wait_stream(side)
         for p in sync.params:                 # what finish() left: views into the buckets
             p.grad = sync.views[id(p)]
@@ -193,7 +212,7 @@ class TrainStep:
                 with torch.cuda.graph(graph):
                     for flat in sync.flat:
                         flat.zero_()
-                    total, _ = self.loss(static_images, static_masks)
+                    total, _ = self.loss(static_images, static_masks, valid_samples=static_valid)
                     total.backward()              # the hooks are disarmed: gradients simply land in the buckets
             finally:
                 self._schedule = None             # the captured kernels keep the pointers; eager calls do not see it
@@ -201,9 +220,10 @@ class TrainStep:
 
         record()
 
-        def replay(new_images, new_masks):
+        def replay(new_images, new_masks, new_valid_samples=None):
             static_images.copy_(new_images)
             static_masks.copy_(new_masks)
+            _copy_static(static_valid, new_valid_samples)
             self._follow_schedule(record)
             state["graph"].replay()
             sync.reduce_now(*self.sync_samples)
@@ -213,7 +233,7 @@ class TrainStep:
 
         return replay
 
-    def capture(self, images, masks, warmup=3):
+    def capture(self, images, masks, warmup=3, valid_samples=None):
         """Capture forward + loss + backward + Adam into one HIP graph (the standard whole-step recipe of
         torch.cuda.graphs: warm up on a side stream, capture with gradients set to None, replay on static inputs).
 
@@ -224,7 +244,8 @@ class TrainStep:
         get_smooth_sigma / get_dropout_prob of the CURRENT global_step, like the reference recomputes them every step
         (model_pc_to.py:59-87, 171-179, 254-258); the graph is captured again, automatically, only when sigma crosses into
         another compiled tap window or the kept points outgrow the captured rows (`recaptures` counts).  Returns
-        replay(images, masks) -> loss tensor (static memory, overwritten by the next replay)."""
+        replay(images, masks[, valid_samples]) -> loss tensor (static memory, overwritten by the next replay); valid_samples
+        is a static input like the masks, given at every replay when the capture had it."""
         if self.grad_sync is not None:
             raise RuntimeError("capture() covers the single-process step; the overlapped gradient exchange runs eagerly")
         if self.cfg.pc_point_dropout != 1 and not self.device_dropout:
@@ -233,11 +254,12 @@ class TrainStep:
         if not all(g["capturable"] for g in self.optimizer.param_groups):
             raise RuntimeError("build the TrainStep with capturable=True")
         static_images, static_masks = images.clone(), masks.clone()
+        static_valid = None if valid_samples is None else valid_samples.clone()
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
             for _ in range(warmup):          # lazy initialisations (Adam state, allocator, kernel attributes) happen here
-                self(static_images, static_masks)
+                self(static_images, static_masks, static_valid)
         torch.cuda.current_stream(self.device).wait_stream(side)
         state = {}
 
@@ -247,7 +269,7 @@ class TrainStep:
             graph = torch.cuda.CUDAGraph()
             try:
                 with torch.cuda.graph(graph):
-                    total, _ = self.loss(static_images, static_masks)
+                    total, _ = self.loss(static_images, static_masks, valid_samples=static_valid)
                     total.backward()
                     self.optimizer.step()
             finally:
@@ -256,9 +278,10 @@ class TrainStep:
 
         record()
 
-        def replay(new_images, new_masks):
+        def replay(new_images, new_masks, new_valid_samples=None):
             static_images.copy_(new_images)
             static_masks.copy_(new_masks)
+            _copy_static(static_valid, new_valid_samples)
             self._follow_schedule(record)
             state["graph"].replay()
             self.global_step += 1

@@ -485,21 +485,24 @@ pointcloud_project = pointcloud_project_fast
 
 def pointcloud_project_loss(cfg, point_cloud, transform, predicted_translation, all_rgb, kernel=None,
                             scaling_factor=None, focal_length=None, gt=None, num_candidates=1, smooth=True, point_index=None,
-                            schedule=None):
+                            schedule=None, valid_samples=None):
     """pointcloud_project_fast followed by the model's projection loss, as ONE autograd node.
 
     What ModelPointCloud does in two steps -- compute_projection (dpc/models/model_pc_to.py:239-282) then
     add_proj_loss / proj_loss_pose_candidates (:339-385, 410-440) -- with the loss folded into the ray-march
-    kernels: `gt` [S,H,W,1] is the mask already pooled to the silhouette size, `point_cloud` holds
-    S*num_candidates clouds (candidate-minor, like tf_repeat_0).  Returns (loss, outputs, winner): the scalar
-    loss sum_s min_k sum (gt-pred)^2 / S, the usual output dict (`proj` from this pass, the rest lazy), and the
+    kernels: `gt` is the reference's inputs["masks"] as it is, [S,1,Hm,Wm] (or [S,Hm,Wm,1]) with Hm = f*H, Wm = f*W
+    -- the kernels average-pool it f x f where they read a pixel, the bits of nn.AvgPool2d(f) (model_pc_to.py:346-354) --
+    or [S,H,W,1] already pooled; `valid_samples` [S] | None is inputs["valid_samples"] (cfg.variable_num_views,
+    :432-436).  `point_cloud` holds S*num_candidates clouds (candidate-minor, like tf_repeat_0).  Returns (loss, outputs,
+    winner): the scalar loss sum_s w_s^2 min_k sum (gt-pred)^2 / S (w = valid_samples, 1 when None; the selection is
+    unweighted), the usual output dict (`proj` from this pass, the rest lazy), and the
     winning candidate per sample.  Falls back to pointcloud_project_fast + silhouette_loss when the Gaussian is
     too long for the fused kernels.  `point_cloud` may hold shared point sets ([B/R,N,3]) and `point_index` per-cloud
     subsets of them (see pointcloud_project_fast)."""
     if all_rgb is not None:
         raise NotImplementedError("all_rgb: the rgb branch of the reference is dead (point_cloud_to.py:64 AttributeError)")
     if gt is None:
-        raise ValueError("gt (pooled masks [S,H,W,1]) is required")
+        raise ValueError("gt (masks [S,1,Hm,Wm], or pooled [S,H,W,1]) is required")
     _check_live_branches(cfg)
     _validate_point_index(point_index, point_cloud)
     geom = _geometry(cfg, kernel if smooth else None, schedule if smooth else None)
@@ -508,13 +511,13 @@ def pointcloud_project_loss(cfg, point_cloud, transform, predicted_translation, 
     try:
         loss, proj, winner = ProjectLossFused.apply(point_cloud, transform, predicted_translation, focal_length,
                                                     scaling_factor, gt, geom, num_candidates, point_index,
-                                                    torch.is_grad_enabled())
+                                                    torch.is_grad_enabled(), valid_samples)
     except _native.DpcError as e:
         if e.code != _native.DPC_ERR_TAPS:
             raise
         out = pointcloud_project_fast(cfg, point_cloud, transform, predicted_translation, None, kernel, scaling_factor,
                                       focal_length, smooth, point_index, schedule)
-        loss, winner = silhouette_loss(out["proj"], gt, num_candidates)
+        loss, winner = silhouette_loss(out["proj"], gt, num_candidates, valid_samples)
         return loss, out, winner
     return loss, ProjectionOutputs(proj, staged), winner
 
@@ -611,14 +614,15 @@ def point_dropout_indices(num_clouds, num_points, keep_prob, device, generator=N
 # ------------------------------------------------------------------------------------------------------
 # The caller's silhouette loss                       reference: dpc/models/model_pc_to.py:339-385, 410-440
 # ------------------------------------------------------------------------------------------------------
-def silhouette_loss(pred, gt, num_candidates=1):
+def silhouette_loss(pred, gt, num_candidates=1, valid_samples=None):
     """Projection loss of ModelPointCloud.add_proj_loss, fused with its gradient in one kernel.
 
-    pred [S*K,H,W,1] candidate silhouettes, gt [S,H,W,1] masks already pooled to H x W (the reference pools with
-    AvgPool2d and permutes first, model_pc_to.py:348-369).  K = 1: sum (gt-pred)^2 / S.  K > 1
-    (proj_loss_pose_candidates): per sample the candidate with the smallest sum of squared differences wins
-    and only winners contribute.  Returns (loss, winner [S] int32)."""
-    return SilhouetteLoss.apply(pred, gt, num_candidates)
+    pred [S*K,H,W,1] candidate silhouettes; gt the masks [S,1,f*H,f*W] (or [S,f*H,f*W,1]), average-pooled f x f inside the
+    kernel like the reference's AvgPool2d (model_pc_to.py:348-369, the same bits), or [S,H,W,1] already pooled;
+    valid_samples [S] | None the per-sample weights w (:432-436).  K = 1: sum w^2 (gt-pred)^2 / S.  K > 1
+    (proj_loss_pose_candidates): per sample the candidate with the smallest (unweighted) sum of squared differences wins
+    and only winners contribute, w^2-weighted.  Returns (loss, winner [S] int32)."""
+    return SilhouetteLoss.apply(pred, gt, num_candidates, valid_samples)
 
 
 # ------------------------------------------------------------------------------------------------------

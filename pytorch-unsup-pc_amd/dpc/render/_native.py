@@ -14,7 +14,7 @@ _CSRC = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__))
 # other implementation to fall back to either way
 LIB_PATH = os.environ.get("DPC_RENDER_LIB") or os.path.join(_CSRC, "libdpc_render.so")
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 DPC_MAX_TAPS = 63
 DPC_MAX_POINTS = (1 << 20) - 1
 DPC_SMALL_COLS = 12
@@ -81,9 +81,10 @@ def lib():
             fn.restype = ctypes.c_int
             fn.argtypes = [pp] + [vp] * nptr
         L.dpc_project_loss_fwd.restype = ctypes.c_int
-        L.dpc_project_loss_fwd.argtypes = [pp] + [vp] * 8 + [ctypes.c_int] + [vp] * 12 + [ctypes.POINTER(ctypes.c_int), vp]
+        # ABI 15: (gt, gt_factor, weights) in every fused-loss call
+        L.dpc_project_loss_fwd.argtypes = [pp] + [vp] * 8 + [ctypes.c_int, vp, ctypes.c_int] + [vp] * 12 + [ctypes.POINTER(ctypes.c_int), vp]
         L.dpc_project_loss_bwd.restype = ctypes.c_int
-        L.dpc_project_loss_bwd.argtypes = [pp] + [vp] * 13 + [ctypes.c_int] + [vp] * 2 + [ctypes.c_int] + [vp] * 4
+        L.dpc_project_loss_bwd.argtypes = [pp] + [vp] * 13 + [ctypes.c_int, vp, ctypes.c_int] + [vp] * 2 + [ctypes.c_int] + [vp] * 4
         L.dpc_splat_fwd.restype = ctypes.c_int
         L.dpc_splat_fwd.argtypes = [pp, vp, ctypes.c_int, vp, vp, vp]
         L.dpc_splat_bwd.restype = ctypes.c_int
@@ -99,7 +100,7 @@ def lib():
         L.dpc_profile_pair_overhead.restype = ctypes.c_int
         L.dpc_profile_pair_overhead.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
         L.dpc_silhouette_loss.restype = ctypes.c_int
-        L.dpc_silhouette_loss.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+        L.dpc_silhouette_loss.argtypes = [vp, ctypes.c_int, vp, vp] + [ctypes.c_int] * 4 + [vp, vp, vp, vp]
         L.dpc_nearest_workspace_bytes.restype = ctypes.c_size_t
         L.dpc_nearest_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.dpc_point_cloud_distance.restype = ctypes.c_int
@@ -115,7 +116,7 @@ def lib():
         L.dpc_taps_bucket.restype = ctypes.c_int
         L.dpc_taps_bucket.argtypes = [vp, ctypes.c_int]
         L.dpc_project_loss_step.restype = ctypes.c_int
-        L.dpc_project_loss_step.argtypes = [pp] + [vp] * 8 + [ctypes.c_int] + [vp] * 15
+        L.dpc_project_loss_step.argtypes = [pp] + [vp] * 8 + [ctypes.c_int, vp, ctypes.c_int] + [vp] * 15
         if L.dpc_abi_version() != ABI_VERSION:
             raise RuntimeError("dpc.render: libdpc_render.so ABI %d, expected %d -- rebuild it (make -C %s)"
                                % (L.dpc_abi_version(), ABI_VERSION, _CSRC))

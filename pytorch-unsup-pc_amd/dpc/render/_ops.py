@@ -232,6 +232,53 @@ def _index32(point_index, pc, q):
     return point_index.detach().to(torch.int32).contiguous()
 
 
+def _plane(shape):
+    """(rows, cols) of a stack of single-channel images: [n,1,h,w] (NCHW, the reference's inputs["masks"]), [n,h,w,1] (its
+    permuted masks and silhouettes) or [n,h,w]; None for any other layout."""
+    if len(shape) == 4 and shape[3] == 1:
+        return shape[1], shape[2]
+    if len(shape) == 4 and shape[1] == 1:
+        return shape[2], shape[3]
+    if len(shape) == 3:
+        return shape[1], shape[2]
+    return None
+
+
+def mask_factor(gt, S, H, W):
+    """Pooling factor f of the ground truth of the fused loss (add_proj_loss, model_pc_to.py:346-354): 1 when `gt` holds
+    S x H x W values (masks already pooled to the silhouette size, any [S, ...] layout), otherwise f = Hm / H = Wm / W for
+    masks [S,1,Hm,Wm] or [S,Hm,Wm,1] -- the kernels pool them like nn.AvgPool2d(f), bit for bit.  Checked on the host:
+    ValueError for a mask side below the silhouette's (the reference asserts) or not an integer multiple of it."""
+    shape = tuple(gt.shape)
+    if not shape or shape[0] != S:
+        raise ValueError("gt must hold the masks of %d samples ([%d,1,Hm,Wm] or [%d,Hm,Wm,1]), got %s" % (S, S, S, shape))
+    if gt.numel() == S * H * W:
+        return 1
+    plane = _plane(shape)
+    if plane is None:
+        raise ValueError("gt must be masks [%d,1,Hm,Wm] or [%d,Hm,Wm,1], got %s" % (S, S, shape))
+    Hm, Wm = plane
+    if Hm < H or Wm < W:
+        raise ValueError("GT size should not be smaller than the prediction size: masks %dx%d, silhouettes %dx%d"
+                         % (Hm, Wm, H, W))
+    if Hm % H or Wm % W or Hm // H != Wm // W:
+        raise ValueError("masks %dx%d are not an integer multiple of the %dx%d silhouettes (AvgPool2d(gt_size // pred_size))"
+                         % (Hm, Wm, H, W))
+    f = Hm // H
+    if f * H > 1024 or f * W > 1024:
+        raise ValueError("masks %dx%d: sides above 1024 are not supported" % (Hm, Wm))
+    return f
+
+
+def _weights32(weights, S):
+    """Per-sample loss weights (the reference's inputs["valid_samples"]) -> contiguous fp32 [S]; None passes through."""
+    if weights is None:
+        return None
+    if tuple(weights.shape) != (S,):
+        raise ValueError("valid_samples must be [%d] (one weight per sample), got %s" % (S, tuple(weights.shape)))
+    return _f32(weights)
+
+
 def _meta(t):
     """(dtype, shape) of an input -- kept on ctx instead of the tensor itself (no reference cycles)."""
     return None if t is None else (t.dtype, tuple(t.shape))
@@ -390,24 +437,31 @@ class ProjectLossFused(torch.autograd.Function):
     forward + 1 backward; otherwise 3 (+ finalize) forward + 2 backward.  The silhouette gradient is never
     materialised; losing pose candidates skip their backward.
 
-    forward(pc, q, t, f, s, gt [S,H,W,1], geom, K) -> (loss [], proj [B,H,W,1], winner [S] int32)
+    forward(pc, q, t, f, s, gt, geom, K, point_index, want_grad, weights) -> (loss [], proj [B,H,W,1], winner [S] int32)
+    gt: masks [S,1,f*H,f*W] or [S,f*H,f*W,1] (pooled f x f inside the kernels, mask_factor), or [S,H,W,1] already pooled;
+    weights: [S] | None, the reference's valid_samples (loss = sum_s w_s^2 min_k sse / S).  gt and weights get no gradient.
     """
 
     @staticmethod
-    def forward(ctx, pc, q, t, f, s, gt, geom, num_candidates, point_index=None, want_grad=True):
-        dev = N.require_device(pc, q, t, f, s, gt)
-        L = N.lib()
-        pc32, q32, t32, f32, s32, gt32 = _f32(pc), _f32(q), _f32(t), _f32(f), _f32(s), _f32(gt)
-        idx = _index32(point_index, pc32, q32)
-        B, reps = q32.shape[0], _replicas(pc32, q32)
-        Npts = pc32.shape[1] if idx is None else idx.shape[1]
-        K = int(num_candidates)
+    def forward(ctx, pc, q, t, f, s, gt, geom, num_candidates, point_index=None, want_grad=True, weights=None):
+        # shapes of the ground truth and the weights first: refused before anything touches the device
+        B, K = q.shape[0], int(num_candidates)
         if K < 1 or B % K:
             raise ValueError("%d clouds is not a multiple of %d pose candidates" % (B, K))
         S = B // K
-        if gt32.shape[0] != S or gt32.numel() != S * geom.H * geom.W:
-            raise ValueError("gt must be [%d,%d,%d,1] (masks pooled to the silhouette size), got %s"
-                             % (S, geom.H, geom.W, tuple(gt32.shape)))
+        if gt.dim() == 0 or gt.shape[0] != S:
+            raise ValueError("gt must be [%d,%d,%d,1] (masks pooled to the silhouette size) or masks [%d,1,f*%d,f*%d], got %s"
+                             % (S, geom.H, geom.W, S, geom.H, geom.W, tuple(gt.shape)))
+        gf = mask_factor(gt, S, geom.H, geom.W)
+        if weights is not None and tuple(weights.shape) != (S,):
+            raise ValueError("valid_samples must be [%d] (one weight per sample), got %s" % (S, tuple(weights.shape)))
+        dev = N.require_device(pc, q, t, f, s, gt, weights)
+        L = N.lib()
+        pc32, q32, t32, f32, s32, gt32 = _f32(pc), _f32(q), _f32(t), _f32(f), _f32(s), _f32(gt)
+        w32 = _weights32(weights, S)
+        idx = _index32(point_index, pc32, q32)
+        reps = _replicas(pc32, q32)
+        Npts = pc32.shape[1] if idx is None else idx.shape[1]
         if B == 0:   # an empty shard (more ranks than samples): nothing to launch, loss 0, zero gradients
             ctx.empty, ctx.dev = True, dev
             ctx.inputs = tuple(_meta(x) for x in (pc, q, t, f, s))
@@ -438,17 +492,17 @@ class ProjectLossFused(torch.autograd.Function):
         kxy, kz = geom.kern_ptrs()
         with _on(dev):
             rc = L.dpc_project_loss_fwd(Z.ref, _dp(pc32), _dp(q32), _dp(t32), _dp(f32), _dp(s32), kxy, kz,
-                                        _dp(gt32), K, None, _dp(cells), _dp(grid_wh), _dp(mask), _dp(proj),
+                                        _dp(gt32), gf, _dp(w32), K, None, _dp(cells), _dp(grid_wh), _dp(mask), _dp(proj),
                                         _dp(trans), _dp(sse), _dp(sse_tiles), _dp(loss), _dp(winner), _dp(ws), _dp(dsmall),
                                         ctypes.byref(fused), _stream(dev))
         if rc != 0:
             N.check(rc, "dpc_project_loss_fwd")
-        ctx.geom, ctx.K, ctx.fused = geom, K, bool(fused.value)
+        ctx.geom, ctx.K, ctx.fused, ctx.gf, ctx.weighted = geom, K, bool(fused.value), gf, w32 is not None
         ctx.inputs = tuple(_meta(x) for x in (pc, q, t, f, s))
         empty = pc32.new_empty(0)
         ctx.save_for_backward(pc32, q32, t32 if t32 is not None else empty, f32 if f32 is not None else empty,
                               s32 if s32 is not None else empty, gt32, grid_wh, mask, cells, proj, trans, winner,
-                              ws if ctx.fused else empty, dsmall if ctx.fused else empty)
+                              ws if ctx.fused else empty, dsmall if ctx.fused else empty, w32 if w32 is not None else empty)
         ctx.has = (t is not None, f is not None, s is not None)
         ctx.npts, ctx.indexed = Npts, idx is not None
         ctx.set_materialize_grads(False)
@@ -458,10 +512,11 @@ class ProjectLossFused(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dproj, _dwinner):
         if dloss is None:
-            return (None,) * 10
+            return (None,) * 11
         if ctx.empty:
-            return _zero_grads(ctx.inputs, ctx.dev) + (None,) * 5
-        pc32, q32, t32, f32, s32, gt32, grid_wh, mask, cells, proj, trans, winner, ws, dsmall = ctx.saved_tensors
+            return _zero_grads(ctx.inputs, ctx.dev) + (None,) * 6
+        pc32, q32, t32, f32, s32, gt32, grid_wh, mask, cells, proj, trans, winner, ws, dsmall, w32 = ctx.saved_tensors
+        w32 = w32 if ctx.weighted else None
         has_t, has_f, has_s = ctx.has
         t32, f32, s32 = (t32 if has_t else None), (f32 if has_f else None), (s32 if has_s else None)
         geom, dev, L = ctx.geom, pc32.device, N.lib()
@@ -478,7 +533,7 @@ class ProjectLossFused(torch.autograd.Function):
         with _on(dev):
             rc = L.dpc_project_loss_bwd(Z.ref, _dp(pc32), _dp(q32), _dp(t32), _dp(f32), _dp(s32), kxy, kz,
                                         _dp(cells), _dp(grid_wh), _dp(mask), _dp(proj), _dp(trans), _dp(gt32),
-                                        ctx.K, _dp(winner), _dp(dl), int(ctx.fused), _dp(dpc), _dp(out_small),
+                                        ctx.gf, _dp(w32), ctx.K, _dp(winner), _dp(dl), int(ctx.fused), _dp(dpc), _dp(out_small),
                                         _dp(ws), _stream(dev))
         if rc != 0:
             N.check(rc, "dpc_project_loss_bwd")
@@ -486,7 +541,7 @@ class ProjectLossFused(torch.autograd.Function):
         return (_like_input(dpc, pc), _like_input(_small(out_small, N.COL_DQ, 4, B), q),
                 _like_input(_small(out_small, N.COL_DT, 3, B), t) if has_t else None,
                 _like_input(_small(out_small, N.COL_DF, 1, B), f) if has_f else None,
-                _like_input(_small(out_small, N.COL_DS, 1, B), s) if has_s else None, None, None, None, None, None)
+                _like_input(_small(out_small, N.COL_DS, 1, B), s) if has_s else None, None, None, None, None, None, None)
 
 
 class ProjectLossStep:
@@ -498,6 +553,8 @@ class ProjectLossStep:
 
         plan = ProjectLossStep(geom, B, N, device)           # geom: dpc.render._geometry(cfg, kernel)
         loss = plan.run(pc, q, s, gt)                         # fp32 contiguous device tensors [B/R,N,3], [B,4], [B,1]|None, [B/K,H,W,1]
+        loss = plan.run(pc, q, s, masks, valid_samples=w)     # or the raw masks [B/K,1,f*H,f*W] (pooled in the kernels) and
+                                                              # per-sample weights [B/K] (loss = sum_s w_s^2 min_k sse / S)
         plan.dpc, plan.dq, plan.ds (plan.dt, plan.df)         # d loss / d input, overwritten by every run; plan.proj, plan.winner
 
     num_candidates = K pose candidates per sample (min-of-K loss); point_replicas = R clouds share a point set (pc is
@@ -542,21 +599,29 @@ class ProjectLossStep:
                              % (name, shape, t.dtype, tuple(t.shape)))
         return ctypes.c_void_p(t.data_ptr())
 
-    def bind(self, pc, q, s, gt, t=None, f=None, dloss=None):
+    def bind(self, pc, q, s, gt, t=None, f=None, dloss=None, valid_samples=None):
         """Fix the input tensors (static buffers that are refilled in place): run() without arguments then skips the
-        per-call checks and pointer conversions."""
-        B, g = self.B, self.geom
+        per-call checks and pointer conversions.  gt: [B/K,H,W,1] pooled masks, or the masks [B/K,1,f*H,f*W] /
+        [B/K,f*H,f*W,1] themselves (the pooling factor f is fixed here); valid_samples: [B/K] weights | None."""
+        B, g, S = self.B, self.geom, self.B // self.K
+        gf = 1
+        if gt is not None and gt.numel() != S * g.H * g.W:
+            gf = mask_factor(gt, S, g.H, g.W)
+            gptr = self._arg(gt, tuple(gt.shape), "gt")
+        else:
+            gptr = self._arg(gt, (S, g.H, g.W, 1), "gt")
         self._bound = (self._pref, self._arg(pc, (B // self.R, self.N, 3), "pc"), self._arg(q, (B, 4), "q"),
                        self._arg(t, (B, 3), "t"), self._arg(f, (B, 1), "f"), self._arg(s, (B, 1), "s"), self._kxy, self._kz,
-                       self._arg(gt, (B // self.K, g.H, g.W, 1), "gt"), self.K) + self._fixed \
+                       gptr, gf, self._arg(valid_samples, (S,), "valid_samples"), self.K) + self._fixed \
             + (None if dloss is None else ctypes.c_void_p(dloss.data_ptr()),) + self._tail
-        self._keep = (pc, q, s, gt, t, f, dloss)
+        self.gt_factor = gf
+        self._keep = (pc, q, s, gt, t, f, dloss, valid_samples)
         return self
 
-    def run(self, pc=None, q=None, s=None, gt=None, t=None, f=None, dloss=None):
+    def run(self, pc=None, q=None, s=None, gt=None, t=None, f=None, dloss=None, valid_samples=None):
         """Enqueue forward + backward on torch's current stream; returns the loss tensor (static, no sync)."""
         if pc is not None:
-            self.bind(pc, q, s, gt, t, f, dloss)
+            self.bind(pc, q, s, gt, t, f, dloss, valid_samples)
         if self.R > 1:
             self.dpc.zero_()    # the replicas ADD into the shared gradient (include/dpc_render.h, point_replicas)
         rc = self._fn(*self._bound, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
@@ -701,25 +766,34 @@ class Drc(torch.autograd.Function):
 
 class SilhouetteLoss(torch.autograd.Function):
     """add_proj_loss / proj_loss_pose_candidates fused with its gradient (one launch, gradient precomputed in
-    the forward; backward scales it by the incoming scalar)."""
+    the forward; backward scales it by the incoming scalar).  gt: pooled masks (as many values per sample as pred has per
+    silhouette) or the masks at f times pred's [H,W] (pooled f x f in the kernel); weights [S] | None."""
 
     @staticmethod
-    def forward(ctx, pred, gt, num_candidates):
-        dev = N.require_device(pred, gt)
-        p32, g32 = _f32(pred), _f32(gt)
-        S = g32.shape[0]
+    def forward(ctx, pred, gt, num_candidates, weights=None):
+        S = gt.shape[0]
         K = int(num_candidates)
-        if p32.shape[0] != S * K:
-            raise ValueError("pred has %d silhouettes, expected %d samples x %d candidates" % (p32.shape[0], S, K))
-        n_pix = g32[0].numel() if S else 1
-        if S and p32[0].numel() != n_pix:
-            raise ValueError("gt and pred silhouettes differ in size: %s vs %s" % (tuple(g32.shape), tuple(p32.shape)))
+        if pred.shape[0] != S * K:
+            raise ValueError("pred has %d silhouettes, expected %d samples x %d candidates" % (pred.shape[0], S, K))
+        n_pix = pred[0].numel() if S else 1
+        H, W, gf = 1, n_pix, 1     # f = 1: any layout of n_pix values per sample, read as they are
+        if S and gt[0].numel() != n_pix:
+            plane = _plane(tuple(pred.shape))
+            if plane is None or plane[0] * plane[1] != n_pix:
+                raise ValueError("gt and pred silhouettes differ in size: %s vs %s" % (tuple(gt.shape), tuple(pred.shape)))
+            H, W = plane
+            gf = mask_factor(gt, S, H, W)
+        if weights is not None and tuple(weights.shape) != (S,):
+            raise ValueError("valid_samples must be [%d] (one weight per sample), got %s" % (S, tuple(weights.shape)))
+        dev = N.require_device(pred, gt, weights)
+        p32, g32 = _f32(pred), _f32(gt)
+        w32 = _weights32(weights, S)
         part = torch.empty((S,), dtype=torch.float32, device=dev)
         winner = torch.empty((S,), dtype=torch.int32, device=dev)
         dpred = torch.empty_like(p32)
         with torch.cuda.device(dev):
-            rc = N.lib().dpc_silhouette_loss(N.ptr(g32), N.ptr(p32), S, K, n_pix, N.ptr(part), N.ptr(winner), N.ptr(dpred),
-                                             N.stream_ptr(dev))
+            rc = N.lib().dpc_silhouette_loss(N.ptr(g32), gf, N.ptr(w32), N.ptr(p32), S, K, H, W, N.ptr(part), N.ptr(winner),
+                                             N.ptr(dpred), N.stream_ptr(dev))
         N.check(rc, "dpc_silhouette_loss")
         ctx.dpred, ctx.meta = dpred, _meta(pred)
         ctx.mark_non_differentiable(winner)
@@ -727,4 +801,4 @@ class SilhouetteLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, _dwinner):
-        return _like_input(ctx.dpred * dloss, ctx.meta), None, None
+        return _like_input(ctx.dpred * dloss, ctx.meta), None, None, None
