@@ -314,6 +314,38 @@ int dpc_point_cloud_distance(const void* vs, const void* vt, int ns, int nt, int
                              int64_t* idx, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Alignment of unsupervised predictions to the ground truth (dpc/run/compute_alignment.py:28-127: open3d_icp,
+ * alignment_to_ground_truth, compute_alignment_candidates): a batched point-to-point ICP with the semantics of open3d
+ * 0.9's registration_icp(source, target, max_dist, init, TransformationEstimationPointToPoint(with_scaling=False),
+ * ICPConvergenceCriteria(rel_fitness, rel_rmse, max_iter)), all in fp64 (open3d runs in double).
+ * src [n_src,3], tgt [n_tgt,3] packed clouds; pair p is (src_start, src_count, tgt_start, tgt_count) = pair_desc[p]
+ * (DEVICE) = host_pair_desc[p] (HOST, the same values: the launch geometry is built from it), so pairs may share a target.
+ *   start:      the source is transformed by init[p] ([P,4,4] row-major, bottom row taken as 0 0 0 1); T = init; evaluate.
+ *   iteration:  estimate update; T = update * T; the stored source points are transformed by update in place and
+ *               cumulatively (open3d's pcd.Transform(update)); evaluate.  Stop when |d fitness| < rel_fitness and
+ *               |d inlier_rmse| < rel_rmse (strict), or after max_iter updates; the result is the last evaluation and its T.
+ *   evaluation: for each source point the nearest target by d2 = (d0*d0 + d1*d1) + d2*d2 (no FMA contraction; exact ties
+ *               to the lower index); an inlier when d2 < tau2 (strict), tau2 = max_dist * max_dist formed in fp64 (whether
+ *               open3d's FLANN call rounds it to float32 is not checkable here); fitness = n_in / n_src,
+ *               inlier_rmse = sqrt(sum d2 / n_in); n_in = 0 gives 0, 0 and the identity update, as open3d does.
+ *   estimation: Umeyama without scaling on the inlier pairs (centroids, Sigma = 1/n sum (q-mu_q)(p-mu_p)^T,
+ *               R = U diag(1,1,det(U)det(V)) V^T, t = mu_q - R mu_p), solved as Horn's 4x4 quaternion eigenproblem: the
+ *               same proper rotation when the singular values are distinct, and finite with det +1 for any n >= 1.
+ *   points are moved as x' = ((R00 x + R01 y) + R02 z) + t0 per row, without FMA contraction.
+ * Outputs: transform [P,4,4], fitness [P], inlier_rmse [P], iterations [P] (the number of updates applied).  Results are
+ * bit-identical from run to run (fixed reduction order, no atomics).  max_iter + 1 rounds are enqueued without any host
+ * synchronisation; pairs that have stopped skip their work.  DPC_ERR_SHAPE, before any launch, for max_dist <= 0 or not
+ * finite, max_iter < 0, a negative start or count, a range outside [0, n_src) / [0, n_tgt), tgt_count == 0 with
+ * src_count > 0.  workspace: dpc_icp_workspace_bytes(pairs, host src counts, host tgt counts) bytes (0 when an argument is
+ * invalid).  Added without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_icp_workspace_bytes(int pairs, const int32_t* src_count, const int32_t* tgt_count);
+int dpc_icp_point_to_point(const double* src, int n_src, const double* tgt, int n_tgt, const int32_t* pair_desc,
+                           const int32_t* host_pair_desc, int pairs, const double* init, double max_dist, int max_iter,
+                           double rel_fitness, double rel_rmse, double* transform, double* fitness, double* inlier_rmse,
+                           int32_t* iterations, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Opt-in measurement aid (nothing in the reference corresponds to it).  After dpc_profile_enable(capacity)
  * every launch of the fused path is bracketed by hipEvents on its stream; synchronise the stream, then read
  * dpc_profile_count() entries with dpc_profile_get(i, &kernel_name, &milliseconds) and dpc_profile_get_id.  Off by default; the only

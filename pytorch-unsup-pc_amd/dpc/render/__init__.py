@@ -20,6 +20,8 @@ from . import _native
 from ._ops import (DeviceSchedule, Drc, Geometry, ProjectFused, ProjectLossFused, ProjectLossStep, SilhouetteLoss, Smooth, Splat,
                    Transform, status_word, taps_bucket)
 from .predictions import chamfer_of_predictions, load_predictions, save_predictions  # noqa: F401
+from .alignment import (alignment_candidates, alignment_to_ground_truth, as_rotation_matrix, from_rotation_matrix,  # noqa: F401
+                        icp_point_to_point, pose_errors, quat_w_avg_markley, quaternion_from_campos, reference_rotation)
 
 __all__ = [
     "pointcloud_project_fast", "pointcloud_project", "pc_perspective_transform", "pointcloud2voxels3d_fast",
@@ -29,6 +31,8 @@ __all__ = [
     "get_smooth_sigma", "get_dropout_prob", "ProjectionOutputs", "silhouette_loss", "pointcloud_project_loss",
     "point_cloud_distance", "compute_distance", "chamfer_distances", "graphed_project_loss", "prefer_direct_graph_launch", "point_dropout_indices", "save_predictions", "load_predictions", "chamfer_of_predictions",
     "DeviceSchedule", "check_status", "set_debug_checks", "taps_bucket", "project_loss_step",
+    "icp_point_to_point", "alignment_to_ground_truth", "alignment_candidates", "reference_rotation", "quat_w_avg_markley",
+    "quaternion_from_campos", "as_rotation_matrix", "from_rotation_matrix", "pose_errors",
 ]
 
 

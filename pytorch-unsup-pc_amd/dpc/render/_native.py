@@ -31,7 +31,8 @@ SYMBOLS = (
     "dpc_splat_fwd", "dpc_splat_bwd", "dpc_smooth", "dpc_drc_fwd", "dpc_drc_bwd",
     "dpc_silhouette_loss", "dpc_point_dropout_indices", "dpc_point_dropout_indices_live", "dpc_schedule_update", "dpc_taps_bucket",
     "dpc_project_loss_step",
-    "dpc_nearest_workspace_bytes", "dpc_point_cloud_distance", "dpc_profile_enable", "dpc_profile_disable", "dpc_profile_count", "dpc_profile_get", "dpc_profile_get_id", "dpc_profile_pair_overhead",
+    "dpc_nearest_workspace_bytes", "dpc_point_cloud_distance", "dpc_icp_workspace_bytes", "dpc_icp_point_to_point",
+    "dpc_profile_enable", "dpc_profile_disable", "dpc_profile_count", "dpc_profile_get", "dpc_profile_get_id", "dpc_profile_pair_overhead",
 )
 
 
@@ -105,6 +106,11 @@ def lib():
         L.dpc_nearest_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.dpc_point_cloud_distance.restype = ctypes.c_int
         L.dpc_point_cloud_distance.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]
+        L.dpc_icp_workspace_bytes.restype = ctypes.c_size_t
+        L.dpc_icp_workspace_bytes.argtypes = [ctypes.c_int, vp, vp]
+        L.dpc_icp_point_to_point.restype = ctypes.c_int
+        L.dpc_icp_point_to_point.argtypes = ([vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_double,
+                                              ctypes.c_int, ctypes.c_double, ctypes.c_double] + [vp] * 6)
         L.dpc_smooth.restype = ctypes.c_int
         L.dpc_smooth.argtypes = [pp, vp, vp, ctypes.c_int, vp, vp, vp, vp]
         L.dpc_point_dropout_indices.restype = ctypes.c_int
