@@ -346,6 +346,31 @@ int dpc_icp_point_to_point(const double* src, int n_src, const double* tgt, int 
                            int32_t* iterations, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Batched Chamfer evaluation (dpc/run/eval_chamfer_to.py:88-145: compute_distance in both directions per view, then
+ * np.mean of the float64 distances): P directed nearest-distance problems and their means in one call.
+ * pts [n_pts,3] is one packed buffer of all clouds, fp32, or fp64 when is_f64; pair p is (src_start, src_count, tgt_start,
+ * tgt_count) = pair_desc[p] (DEVICE) = host_pair_desc[p] (HOST, the same values: the launch geometry is built from it).
+ * Sources and targets index the same buffer, so "pred -> GT" and "GT -> pred" are two pairs and views share one GT copy.
+ *   distances:  per source point exactly dpc_point_cloud_distance's min_dist and idx (the same scan, the same first-minimum
+ *               rule; idx relative to tgt_start, int64);
+ *   means:      mean[p] = np.mean of the pair's distances cast to float64, bit for bit: buffers of 8192 elements, each
+ *               summed in numpy's pairwise_sum order, the buffer sums added left to right onto 0.0, then an IEEE fp64
+ *               divide by src_count; src_count == 0 gives NaN, as np.mean of an empty array does.
+ * Outputs: mean [P] float64; min_dist (in the compute type) and idx, each [sum src_count] | NULL, packed in pair order:
+ * pair p's points start at sum_{q<p} src_count[q].  No atomics: results are bit-identical from run to run and do not
+ * depend on how pairs are batched.  The per-pair prefixes are built on the device from pair_desc: the call copies nothing
+ * from the host and can be captured into a hipGraph.  DPC_ERR_SHAPE, before any launch, for pairs < 0, n_pts < 0, a negative
+ * start or count, a range outside [0, n_pts), tgt_count == 0 with src_count > 0 (the reference's argmin over an empty set
+ * raises), or more than 2^31 - 1 output points.  With valid arguments and NULL device pointers the call returns
+ * DPC_ERR_NULL without touching a device, so a binding can validate a table on the host first.  workspace:
+ * dpc_chamfer_workspace_bytes(pairs, host_pair_desc, is_f64) bytes (0 when the table is invalid or pairs <= 0).
+ * Added without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_chamfer_workspace_bytes(int pairs, const int32_t* host_pair_desc, int is_f64);
+int dpc_nearest_batched(const void* pts, int n_pts, int is_f64, const int32_t* pair_desc, const int32_t* host_pair_desc,
+                        int pairs, double* mean, void* min_dist, int64_t* idx, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Opt-in measurement aid (nothing in the reference corresponds to it).  After dpc_profile_enable(capacity)
  * every launch of the fused path is bracketed by hipEvents on its stream; synchronise the stream, then read
  * dpc_profile_count() entries with dpc_profile_get(i, &kernel_name, &milliseconds) and dpc_profile_get_id.  Off by default; the only

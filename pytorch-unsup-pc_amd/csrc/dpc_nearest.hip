@@ -4,18 +4,16 @@
 // The reference materialises [Ns,Nt,3] differences, takes sqrt(sum(diff^2, 2)) and torch.argmin (first minimum) over
 // the targets.  Here nothing is materialised: one lane owns one source point, the targets stream through LDS, and the
 // targets are also split over blockIdx.y so that small source clouds still fill the chip; a second, tiny kernel merges
-// the per-slice winners in slice order.  Arithmetic follows the reference op for op, in the input's precision:
-//   d = Vt - Vs;  d2 = (d0*d0 + d1*d1) + d2*d2 (no FMA contraction);  dist = sqrt(d2) correctly rounded.
-// "First minimum of dist" is not the same as "first minimum of d2" when two different d2 round to one sqrt, so near
-// ties are decided on the sqrt values themselves (see `consider` below); everything else is decided on d2, sqrt being
-// monotone.
+// the per-slice winners in slice order.  The scan itself -- the reference's arithmetic op for op in the input's precision,
+// and its first-minimum rule including near ties -- is nearest_scan in dpc_nearest.h, shared with the batched Chamfer
+// kernels of dpc_chamfer.hip.
 // Compute-bound on the fp32 / fp64 vector pipe (about a dozen instructions per pair); HBM traffic is negligible.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <limits>
 
 #include "../../include/dpc_render.h"
+#include "dpc_nearest.h"
 #include "dpc_profile.h"
 
 namespace {
@@ -27,7 +25,6 @@ template <class T>
 __global__ __launch_bounds__(kNnThreads) void k_nearest_partial(const T* __restrict__ vs, const T* __restrict__ vt, int ns,
                                                                 int nt, int slice, T* __restrict__ part_dist,
                                                                 int* __restrict__ part_idx) {
-#pragma clang fp contract(off)
   __shared__ T tx[kNnTile], ty[kNnTile], tz[kNnTile];
   const int i = blockIdx.x * kNnThreads + threadIdx.x;
   const bool live = i < ns;
@@ -36,47 +33,9 @@ __global__ __launch_bounds__(kNnThreads) void k_nearest_partial(const T* __restr
   if (live) {
     sx = vs[3 * (size_t)i + 0]; sy = vs[3 * (size_t)i + 1]; sz = vs[3 * (size_t)i + 2];
   }
-  const T kNearTie = (T)1 - (T)16 * std::numeric_limits<T>::epsilon();
-  T best_d2 = std::numeric_limits<T>::infinity();
-  int best = j0;
-  for (int base = j0; base < j1; base += kNnTile) {
-    const int n = min(kNnTile, j1 - base);
-    __syncthreads();
-    for (int k = threadIdx.x; k < n; k += kNnThreads) {
-      const T* p = vt + 3 * (size_t)(base + k);
-      tx[k] = p[0]; ty[k] = p[1]; tz[k] = p[2];
-    }
-    __syncthreads();
-    // Four candidates per step; the sqrt-and-compare runs only when some lane of the wave has a candidate below its
-    // incumbent (a wave-uniform branch: left as a per-lane condition the compiler evaluates the sqrt for every pair).
-    auto pair_d2 = [&](int k) {
-      const T d0 = tx[k] - sx, d1 = ty[k] - sy, d2c = tz[k] - sz;
-      return (d0 * d0 + d1 * d1) + d2c * d2c;
-    };
-    // A candidate whose d2 is below the incumbent's by more than a few ulps has a strictly smaller sqrt: taken without
-    // evaluating it.  Within that margin (a near tie, ~1e-6 of the improvements) both square roots are evaluated,
-    // correctly rounded, and the candidate wins only if its distance is strictly smaller -- the incumbent, which has the
-    // smaller index, keeps ties, exactly like argmin over the sqrt values.
-    auto consider = [&](T d2, int j) {
-      const bool better = d2 < best_d2;
-      const bool near_tie = better && d2 >= best_d2 * kNearTie;
-      if (__builtin_amdgcn_ballot_w64(near_tie) != 0ull) {
-        const bool wins = better && (!near_tie || sqrt(d2) < sqrt(best_d2));
-        if (wins) { best_d2 = d2; best = j; }
-      } else if (better) {
-        best_d2 = d2; best = j;
-      }
-    };
-    int k = 0;
-    for (; k + 4 <= n; k += 4) {
-      const T a = pair_d2(k), b = pair_d2(k + 1), c = pair_d2(k + 2), d = pair_d2(k + 3);
-      const T m = fmin(fmin(a, b), fmin(c, d));
-      if (__builtin_amdgcn_ballot_w64(m < best_d2) != 0ull) {
-        consider(a, base + k); consider(b, base + k + 1); consider(c, base + k + 2); consider(d, base + k + 3);
-      }
-    }
-    for (; k < n; ++k) consider(pair_d2(k), base + k);
-  }
+  T best_d2;
+  int best;
+  nearest_scan<T, kNnThreads, kNnTile>(vt, j0, j1, sx, sy, sz, tx, ty, tz, best_d2, best);
   if (live) {
     part_dist[(size_t)blockIdx.y * ns + i] = sqrt(best_d2);
     part_idx[(size_t)blockIdx.y * ns + i] = best;

@@ -19,6 +19,7 @@ DPC_MAX_TAPS = 63
 DPC_MAX_POINTS = (1 << 20) - 1
 DPC_SMALL_COLS = 12
 COL_DQ, COL_DS, COL_DT, COL_DF = 0, 4, 5, 8
+DPC_ERR_NULL = -1
 DPC_ERR_SHAPE = -2
 DPC_ERR_TAPS = -3
 DPC_ERR_LDS = -4
@@ -32,6 +33,7 @@ SYMBOLS = (
     "dpc_silhouette_loss", "dpc_point_dropout_indices", "dpc_point_dropout_indices_live", "dpc_schedule_update", "dpc_taps_bucket",
     "dpc_project_loss_step",
     "dpc_nearest_workspace_bytes", "dpc_point_cloud_distance", "dpc_icp_workspace_bytes", "dpc_icp_point_to_point",
+    "dpc_chamfer_workspace_bytes", "dpc_nearest_batched",
     "dpc_profile_enable", "dpc_profile_disable", "dpc_profile_count", "dpc_profile_get", "dpc_profile_get_id", "dpc_profile_pair_overhead",
 )
 
@@ -111,6 +113,10 @@ def lib():
         L.dpc_icp_point_to_point.restype = ctypes.c_int
         L.dpc_icp_point_to_point.argtypes = ([vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_double,
                                               ctypes.c_int, ctypes.c_double, ctypes.c_double] + [vp] * 6)
+        L.dpc_chamfer_workspace_bytes.restype = ctypes.c_size_t
+        L.dpc_chamfer_workspace_bytes.argtypes = [ctypes.c_int, vp, ctypes.c_int]
+        L.dpc_nearest_batched.restype = ctypes.c_int
+        L.dpc_nearest_batched.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int] + [vp] * 5
         L.dpc_smooth.restype = ctypes.c_int
         L.dpc_smooth.argtypes = [pp, vp, vp, ctypes.c_int, vp, vp, vp, vp]
         L.dpc_point_dropout_indices.restype = ctypes.c_int

@@ -1,0 +1,279 @@
+"""The Chamfer half of the evaluation for a whole split in batched GPU calls (dpc/run/eval_chamfer_to.py:88-145).
+
+The reference walks models and views one at a time: per view two compute_distance calls (pred -> GT, GT -> pred) and
+np.mean of each float64 result.  Here every directed pair of a group of models goes into one dpc_nearest_batched call
+(csrc/dpc_chamfer.hip): the nearest search is dpc_point_cloud_distance's, and the per-pair means are summed on the device
+in numpy's float64 order, so every number equals the reference's own compute_distance + np.mean bit for bit.
+
+    nearest_batched   the thin wrapper over the C ABI: packed points, a [P,4] pair table, [P] float64 means
+    chamfer_batched   (mean pred -> gt, mean gt -> pred) for lists of clouds, [P,2] float64
+    chamfer_of_split  the reference's chamfer_dists [M,V,2] for loaded predictions and GT clouds
+    eval_chamfer      run_eval's file loop: <save_dir>/<model>_pc.pkl plus a caller-supplied GT loader
+
+Reading .mat files stays with the caller (load_gt), as everywhere in this package.
+"""
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from . import _native
+from .predictions import load_predictions
+
+
+def _device(*groups):
+    for g in groups:
+        for x in g:
+            if isinstance(x, torch.Tensor) and x.is_cuda:
+                return x.device
+    if not torch.cuda.is_available():
+        raise RuntimeError("dpc.render Chamfer evaluation runs on MI355X only: no HIP device (there is no CPU path)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _pair_table(pairs):
+    desc = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
+    if desc.ndim != 2 or desc.shape[1] != 4:
+        raise ValueError("nearest_batched: pairs must be [P,4] (src_start, src_count, tgt_start, tgt_count), got %s"
+                         % (tuple(desc.shape),))
+    if desc.size and (desc.min() < np.iinfo(np.int32).min or desc.max() > np.iinfo(np.int32).max):
+        raise ValueError("nearest_batched: pair table entries must fit int32")
+    return np.ascontiguousarray(desc, dtype=np.int32)
+
+
+def nearest_batched(points, pairs, return_distances=False):
+    """Nearest-target distances of P directed pairs over one packed cloud buffer, with per-pair float64 means.
+
+    points: [n,3] tensor (or array) holding every cloud; pairs: [P,4] rows (src_start, src_count, tgt_start, tgt_count)
+    indexing it.  Pair p's distances are exactly point_cloud_distance(points[src], points[tgt])[1] and its mean is
+    np.mean of them as float64, bit for bit (NaN when src_count == 0).  fp64 arithmetic when points is fp64, fp32
+    otherwise (as point_cloud_distance).  Returns means [P] float64 on the device, or (means, min_dist [sum src_count],
+    idx [sum src_count] int64) with return_distances, the distances packed in pair order.  A bad table raises ValueError
+    before anything is launched."""
+    desc = _pair_table(pairs)
+    P = desc.shape[0]
+    L = _native.lib()
+    pts = points if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points))
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError("nearest_batched: points must be [n,3], got %s" % (tuple(pts.shape),))
+    n_pts = int(pts.shape[0])
+    if n_pts > np.iinfo(np.int32).max:
+        raise ValueError("nearest_batched: more than 2^31 - 1 points")
+    host_desc = desc.ctypes.data_as(ctypes.c_void_p)
+    # the library's own checks (DPC_ERR_SHAPE, before any launch), asked of it without touching the device
+    rc = L.dpc_nearest_batched(None, n_pts, 0, None, host_desc, P, None, None, None, None, None)
+    if rc == _native.DPC_ERR_SHAPE:
+        raise ValueError("nearest_batched: invalid pair table (a negative start or count, a range outside the %d points, "
+                         "an empty target for a non-empty source, or more than 2^31 - 1 output points)" % n_pts)
+    dev = _device([pts])
+    dtype = torch.float64 if pts.dtype == torch.float64 else torch.float32
+    pts = pts.detach().to(device=dev, dtype=dtype).contiguous()
+    is64 = int(dtype == torch.float64)
+    total = int(desc[:, 1].astype(np.int64).sum()) if P else 0
+    mean = torch.empty((P,), dtype=torch.float64, device=dev)
+    dist = torch.empty((total,), dtype=dtype, device=dev) if return_distances else None
+    idx = torch.empty((total,), dtype=torch.int64, device=dev) if return_distances else None
+    if P:
+        desc_d = torch.from_numpy(desc).to(dev)
+        ws = torch.empty((max(L.dpc_chamfer_workspace_bytes(P, host_desc, is64), 16),), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = L.dpc_nearest_batched(_native.ptr(pts), n_pts, is64, _native.ptr(desc_d), host_desc, P, _native.ptr(mean),
+                                       _native.ptr(dist), _native.ptr(idx), _native.ptr(ws), _native.stream_ptr(dev))
+        _native.check(rc, "dpc_nearest_batched")
+    return (mean, dist, idx) if return_distances else mean
+
+
+def _cloud(x, what, i):
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError("%s[%d] must be [n,3], got %s" % (what, i, tuple(t.shape)))
+    if t.dtype not in (torch.float32, torch.float64):
+        t = t.float()
+    return t.detach()
+
+
+def chamfer_batched(preds, gts, gt_of=None):
+    """(mean_i min_j |pred_i - gt_j|, mean_j min_i |gt_j - pred_i|) for every prediction against its GT cloud: the
+    reference's chamfer_dists_current rows (eval_chamfer_to.py:119-123), [P,2] float64 on the device.
+
+    preds, gts: lists of [n,3] tensors or arrays; gt_of: the GT index of each prediction (default i -> i), so views of
+    one model share one GT copy.  A pair is computed in fp64 when its prediction or its GT is fp64, in fp32 otherwise
+    (point_cloud_distance's rule, per pair): all 2P directed pairs go into one native call, or two when fp32-only and
+    fp64 pairs are mixed.  NaN or inf coordinates raise ValueError naming the first bad input (one device reduction),
+    standing in for the reference's assert on NaN distances; an empty GT for a non-empty prediction raises too."""
+    P_list = [_cloud(p, "preds", i) for i, p in enumerate(preds)]
+    G_list = [_cloud(g, "gts", i) for i, g in enumerate(gts)]
+    P = len(P_list)
+    if gt_of is None:
+        if len(G_list) != P:
+            raise ValueError("chamfer_batched: %d predictions and %d GT clouds need gt_of" % (P, len(G_list)))
+        gt_of = range(P)
+    gt_of = list(gt_of)
+    if len(gt_of) != P or any(not isinstance(k, (int, np.integer)) or k < 0 or k >= len(G_list) for k in gt_of):
+        raise ValueError("chamfer_batched: gt_of must map each of the %d predictions to one of %d GT clouds" % (P, len(G_list)))
+    gt_of = [int(k) for k in gt_of]
+    for i, k in enumerate(gt_of):
+        if len(G_list[k]) == 0 and len(P_list[i]) > 0:
+            raise ValueError("chamfer_batched: GT cloud %d is empty but prediction %d is not (argmin of an empty set)" % (k, i))
+    dev = _device(P_list, G_list)
+    out = torch.empty((P, 2), dtype=torch.float64, device=dev)
+    if P == 0:
+        return out
+    f64 = [P_list[i].dtype == torch.float64 or G_list[k].dtype == torch.float64 for i, k in enumerate(gt_of)]
+    for want in (False, True):
+        sel = [i for i in range(P) if f64[i] == want]
+        if sel:
+            out[sel] = _chamfer_group([P_list[i] for i in sel], G_list, [gt_of[i] for i in sel], dev,
+                                      torch.float64 if want else torch.float32)
+    return out
+
+
+def _chamfer_group(preds, gts, gt_of, dev, dtype):
+    """One native call: the GT clouds used, then the predictions, packed into one buffer; pairs (p->g, g->p) interleaved."""
+    used = sorted(set(gt_of))
+    clouds = [gts[k] for k in used] + list(preds)
+    names = ["gts[%d]" % k for k in used] + ["preds[%d]" % i for i in range(len(preds))]
+    on_dev = any(c.is_cuda for c in clouds)
+    parts = [c.to(device=dev, dtype=dtype) for c in clouds] if on_dev else [c.to(dtype) for c in clouds]
+    packed = torch.cat(parts) if parts else torch.zeros((0, 3), dtype=dtype)
+    packed = packed.to(dev).contiguous()
+    if packed.numel() and not bool(torch.isfinite(packed).all()):
+        for name, c in zip(names, clouds):
+            if not bool(torch.isfinite(c).all()):
+                raise ValueError("chamfer_batched: %s holds a NaN or inf coordinate" % name)
+    start = np.cumsum([0] + [len(c) for c in clouds])
+    slot = {k: j for j, k in enumerate(used)}
+    desc = np.zeros((2 * len(preds), 4), dtype=np.int64)
+    for i, k in enumerate(gt_of):
+        ps, pn = start[len(used) + i], len(preds[i])
+        gs, gn = start[slot[k]], len(gts[k])
+        desc[2 * i] = (ps, pn, gs, gn)
+        desc[2 * i + 1] = (gs, gn, ps, pn)
+    if start[-1] > np.iinfo(np.int32).max:
+        raise ValueError("chamfer_batched: more than 2^31 - 1 points in one call")
+    return nearest_batched(packed, desc).view(len(preds), 2)
+
+
+def _host_unit_quaternion(q):
+    """The reference's q / |q| (util/quaternion.py quaternion_rotate), evaluated in CPU torch where its evaluation ran:
+    a device norm of four numbers is not guaranteed to round the same way."""
+    qt = q.detach().cpu() if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
+    if qt.dim() != 2 or qt.shape != (1, 4):
+        raise ValueError("reference_rotation must be a [1,4] quaternion, got %s" % (tuple(qt.shape),))
+    return torch.div(qt, qt.norm(p=2, dim=-1).reshape(qt.shape[0], 1))
+
+
+def _rotate(points, qn, dev):
+    """quaternion_rotate(points [V,N,3], q) with q already normalised: q * p * conj(q), the reference's products in its
+    order, in the promoted dtype (float64 for a float64 quaternion; no cast back, as eval_chamfer_to.py:116-120)."""
+    from . import quaternion_conjugate, quaternion_multiply
+
+    pc = points.to(dev).reshape(1, -1, 3)
+    q = qn.to(dev).reshape(1, 1, 4)
+    wxyz = quaternion_multiply(quaternion_multiply(q, pc), quaternion_conjugate(q))
+    return wxyz[:, :, 1:4].reshape(points.shape[0], points.shape[1], 3)
+
+
+def _prediction(entry, m):
+    if not isinstance(entry, (tuple, list)) or len(entry) not in (2, 3):
+        raise ValueError("predictions[%d] must be (points, num_points) or load_predictions' (points, camera_pose, num_points)" % m)
+    pts, nums = entry[0], entry[-1]
+    pts = pts if isinstance(pts, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pts))
+    if pts.dim() != 3 or pts.shape[2] != 3:
+        raise ValueError("predictions[%d] points must be [V,N,3], got %s" % (m, tuple(pts.shape)))
+    if nums is not None:
+        nums = np.asarray(nums.detach().cpu() if isinstance(nums, torch.Tensor) else nums).reshape(-1)
+        if (len(nums) != pts.shape[0] or not np.issubdtype(nums.dtype, np.integer) or (nums < 0).any()
+                or (nums > pts.shape[1]).any()):
+            raise ValueError("predictions[%d] num_points must be %d integers in [0, %d], got %r"
+                             % (m, pts.shape[0], pts.shape[1], nums))
+    return pts, nums
+
+
+def chamfer_of_split(predictions, gt_clouds, reference_rotation=None, models_per_call=256):
+    """The reference's chamfer_dists (eval_chamfer_to.py:95-136) for M models: [M,V,2] float64 numpy, bit for bit.
+
+    predictions: per model (points [V,N,3], num_points [V] | None) -- or load_predictions' (points, camera_pose,
+    num_points); view i is truncated to its first num_points[i] points (:111-113).  gt_clouds: per model [n,3].
+    reference_rotation: a [1,4] quaternion (float64 as loadmat gives it) applied to every view first, the result kept in the
+    promoted dtype (:116-120).  Models go through in groups of models_per_call (bounding device memory); the result does
+    not depend on the grouping.  Every argument is checked before anything is launched."""
+    if len(predictions) != len(gt_clouds):
+        raise ValueError("chamfer_of_split: %d predictions and %d GT clouds" % (len(predictions), len(gt_clouds)))
+    if int(models_per_call) < 1:
+        raise ValueError("chamfer_of_split: models_per_call must be >= 1")
+    preds = [_prediction(e, m) for m, e in enumerate(predictions)]
+    gts = [_cloud(g, "gt_clouds", m) for m, g in enumerate(gt_clouds)]
+    views = {p.shape[0] for p, _ in preds}
+    if len(views) > 1:
+        raise ValueError("chamfer_of_split: every model needs the same number of views, got %s" % sorted(views))
+    V = views.pop() if views else 0
+    for m, ((p, nums), g) in enumerate(zip(preds, gts)):
+        if len(g) == 0 and (p.shape[1] if nums is None else nums.max(initial=0)) > 0:
+            raise ValueError("chamfer_of_split: GT cloud %d is empty" % m)
+    qn = None if reference_rotation is None else _host_unit_quaternion(reference_rotation)
+    M = len(preds)
+    out = np.zeros((M, V, 2), dtype=np.float64)
+    if M == 0 or V == 0:
+        return out
+    dev = _device([p for p, _ in preds], gts)
+    step = int(models_per_call)
+    for a in range(0, M, step):
+        group = range(a, min(M, a + step))
+        views_list, gt_of = [], []
+        for j, m in enumerate(group):
+            pts, nums = preds[m]
+            if qn is not None:
+                pts = _rotate(pts, qn, dev)
+            for i in range(V):
+                views_list.append(pts[i] if nums is None else pts[i, :int(nums[i])])
+                gt_of.append(j)
+        res = chamfer_batched(views_list, [gts[m] for m in group], gt_of)
+        out[a:a + len(group)] = res.cpu().numpy().reshape(len(group), V, 2)
+    return out
+
+
+def eval_chamfer(save_dir, model_names, load_gt, num_views=None, reference_rotation=None, out_name=None, out_dir=None,
+                 models_per_call=256):
+    """run_eval's loop (eval_chamfer_to.py:88-145) over <save_dir>/<model>_pc.pkl.
+
+    load_gt(model) -> [n,3] GT cloud, or None when it has none (e.g. scipy.io.loadmat(path)["points"]); a model whose
+    pickle or GT is missing is skipped, as the reference does.  num_views: views per model (default: all in the pickle).
+    Returns {"chamfer": [M',V,2], "model_names": the M' evaluated models, "final": np.mean(chamfer, axis=(0, 1)) * 100}.
+    With out_name, writes "chamfer_<out_name>.txt" ("{} {}\\n" of final) into out_dir (default: save_dir's parent, the
+    reference's experiment directory).  Models are read and evaluated models_per_call at a time."""
+    names, chamfer = [], []
+    pending, pending_gt, pending_names = [], [], []
+
+    def flush():
+        if pending:
+            chamfer.append(chamfer_of_split(pending, pending_gt, reference_rotation, models_per_call))
+            names.extend(pending_names)
+            del pending[:], pending_gt[:], pending_names[:]
+
+    for name in model_names:
+        path = os.path.join(save_dir, "%s_pc.pkl" % name)
+        if not os.path.isfile(path):
+            continue
+        gt = load_gt(name)
+        if gt is None:
+            continue
+        points, _, nums = load_predictions(path)
+        if num_views is not None:
+            points = points[:num_views]
+            nums = None if nums is None else nums[:num_views]
+        pending.append((points, nums))
+        pending_gt.append(gt)
+        pending_names.append(name)
+        if len(pending) >= models_per_call:
+            flush()
+    flush()
+    V = num_views if num_views is not None else (chamfer[0].shape[1] if chamfer else 0)
+    dists = np.concatenate(chamfer) if chamfer else np.zeros((0, V, 2), dtype=np.float64)
+    final = np.mean(dists, axis=(0, 1)) * 100
+    if out_name is not None:
+        out_dir = os.path.dirname(os.path.normpath(save_dir)) if out_dir is None else out_dir
+        with open(os.path.join(out_dir, "chamfer_{}.txt".format(out_name)), "w") as f:
+            f.write("{} {}\n".format(final[0], final[1]))
+    return {"chamfer": dists, "model_names": names, "final": final}
