@@ -55,8 +55,11 @@ enum {
 
 /* Bits of the optional device status word (DpcParams.status). */
 enum {
-  DPC_STATUS_BAD_INDEX = 1    /* a point_index entry was outside [0, N_src): the point was dropped (the reference's fancy
+  DPC_STATUS_BAD_INDEX = 1,   /* a point_index entry was outside [0, N_src): the point was dropped (the reference's fancy
                                * indexing raises IndexError there, dpc/util/point_cloud_to.py:266-295)                   */
+  DPC_STATUS_VOXEL_TOO_SMALL = 2, /* dpc_voxel_downsample: open3d's "voxel_size is too small" (nothing was computed)    */
+  DPC_STATUS_KEY_OVERFLOW = 4,    /* dpc_voxel_downsample: the batch's voxel keys need more than 64 bits (nothing computed) */
+  DPC_STATUS_NONFINITE = 8        /* dpc_voxel_downsample: a NaN or infinite coordinate (nothing was computed)          */
 };
 
 /* Geometry and camera constants of one call (dpc/resources/default_config.yaml:77-89 and the cfg fields
@@ -369,6 +372,44 @@ int dpc_icp_point_to_point(const double* src, int n_src, const double* tgt, int 
 size_t dpc_chamfer_workspace_bytes(int pairs, const int32_t* host_pair_desc, int is_f64);
 int dpc_nearest_batched(const void* pts, int n_pts, int is_f64, const int32_t* pair_desc, const int32_t* host_pair_desc,
                         int pairs, double* mean, void* min_dist, int64_t* idx, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Voxel-grid downsampling of ground-truth clouds (densify/downsample_gt.py:47-57: open3d.voxel_down_sample(pcd,
+ * voxel_size) per model) for C clouds in one call.  open3d's PointCloud::VoxelDownSample (0.7 - 0.9, the same body in each),
+ * restated from its C++ source for one cloud p[0..n), all in fp64 (float32 input is widened exactly first):
+ *
+ *   vs3  = (vs, vs, vs)
+ *   lo   = min_i p[i] - vs3 * 0.5          per component; the min bound of an empty cloud is 0
+ *   hi   = max_i p[i] + vs3 * 0.5
+ *   refuse if vs <= 0, or vs * 2147483647 < max_c (hi - lo)_c        open3d's two LogError cases
+ *   key_i = (int(floor((p[i].x - lo.x) / vs)), ... y ..., ... z ...) subtract, then an IEEE division
+ *   for i in input order: acc[key_i] += p[i]; cnt[key_i] += 1      one fp64 add at a time, in input order, from 0.0
+ *   out  = { acc[k] / double(cnt[k]) }                             an IEEE division, not a multiply by a reciprocal
+ *
+ * Output order: open3d emits voxels in its std::unordered_map's iteration order, which is implementation-defined; here
+ * it is ascending (kx, ky, kz), lexicographic.  The set of output points is open3d's bit for bit; anything that sums over
+ * the points in file order (a Chamfer mean GT -> prediction) can differ in the last bits from an open3d-written file.
+ *
+ * pts [n_pts,3] is one packed buffer, fp32, or fp64 when is_f64; cloud c is (start, count) = cloud_desc[c] (DEVICE) =
+ * host_cloud_desc[c] (HOST, the same values); clouds may share or skip rows.  With M = sum of counts:
+ *   out        [M,3] float64 capacity (an upper bound): the voxels of all clouds, packed in cloud order;
+ *   out_count  [C] int32, voxels of cloud c; out_offset [C] int32, its first row in out (the exclusive prefix of out_count);
+ *   status     one int32 (DEVICE): DPC_STATUS_VOXEL_TOO_SMALL (open3d's refusal, for any cloud), DPC_STATUS_KEY_OVERFLOW
+ *              (the keys slot | kx | ky | kz, field widths from the batch's largest cloud index and keys, need more than 64
+ *              bits, or a key exceeds 2^31 - 1), DPC_STATUS_NONFINITE (open3d's behaviour for them is undefined) are OR-ed in,
+ *              never cleared (the caller zeroes it, as DpcParams.status); when one is set nothing else is computed and
+ *              out_count, out_offset are 0.  Read it after a synchronisation of the caller's own.
+ * No floating-point atomics: results are bit-identical from run to run and do not depend on how clouds are batched.
+ * No host synchronisation and no host -> device copy: the call can be captured into a hipGraph.  DPC_ERR_SHAPE, before
+ * any launch, for voxel_size <= 0 or not finite, clouds < 0, n_pts < 0, a negative start or count, a range outside
+ * [0, n_pts), or M > 2^31 - 2.  With valid arguments and NULL device pointers the call returns DPC_ERR_NULL without touching
+ * a device.  workspace: dpc_downsample_workspace_bytes(C, M) bytes, at most 28 M + 2056 ceil(M / 4096) + 56 C + 2048 (0
+ * when an argument is invalid).  Added without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_downsample_workspace_bytes(int clouds, int members);
+int dpc_voxel_downsample(const void* pts, int n_pts, int is_f64, const int32_t* cloud_desc, const int32_t* host_cloud_desc,
+                         int clouds, double voxel_size, double* out, int32_t* out_count, int32_t* out_offset,
+                         int32_t* status, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Opt-in measurement aid (nothing in the reference corresponds to it).  After dpc_profile_enable(capacity)

@@ -24,6 +24,9 @@ DPC_ERR_SHAPE = -2
 DPC_ERR_TAPS = -3
 DPC_ERR_LDS = -4
 DPC_STATUS_BAD_INDEX = 1
+DPC_STATUS_VOXEL_TOO_SMALL = 2
+DPC_STATUS_KEY_OVERFLOW = 4
+DPC_STATUS_NONFINITE = 8
 
 # every symbol include/dpc_render.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = (
@@ -33,7 +36,7 @@ SYMBOLS = (
     "dpc_silhouette_loss", "dpc_point_dropout_indices", "dpc_point_dropout_indices_live", "dpc_schedule_update", "dpc_taps_bucket",
     "dpc_project_loss_step",
     "dpc_nearest_workspace_bytes", "dpc_point_cloud_distance", "dpc_icp_workspace_bytes", "dpc_icp_point_to_point",
-    "dpc_chamfer_workspace_bytes", "dpc_nearest_batched",
+    "dpc_chamfer_workspace_bytes", "dpc_nearest_batched", "dpc_downsample_workspace_bytes", "dpc_voxel_downsample",
     "dpc_profile_enable", "dpc_profile_disable", "dpc_profile_count", "dpc_profile_get", "dpc_profile_get_id", "dpc_profile_pair_overhead",
 )
 
@@ -117,6 +120,10 @@ def lib():
         L.dpc_chamfer_workspace_bytes.argtypes = [ctypes.c_int, vp, ctypes.c_int]
         L.dpc_nearest_batched.restype = ctypes.c_int
         L.dpc_nearest_batched.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int] + [vp] * 5
+        L.dpc_downsample_workspace_bytes.restype = ctypes.c_size_t
+        L.dpc_downsample_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+        L.dpc_voxel_downsample.restype = ctypes.c_int
+        L.dpc_voxel_downsample.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_double] + [vp] * 6
         L.dpc_smooth.restype = ctypes.c_int
         L.dpc_smooth.argtypes = [pp, vp, vp, ctypes.c_int, vp, vp, vp, vp]
         L.dpc_point_dropout_indices.restype = ctypes.c_int

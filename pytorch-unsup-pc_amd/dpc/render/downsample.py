@@ -1,0 +1,151 @@
+"""Voxel-grid downsampling of ground-truth clouds on the GPU (densify/downsample_gt.py:47-57, open3d.voxel_down_sample).
+
+The reference reads each dense model, calls open3d's VoxelDownSample and writes the result.  Here a whole group of
+models goes into one dpc_voxel_downsample call (csrc/dpc_downsample.hip): the same fp64 keys and the same per-voxel sums
+in input order, so every output point equals open3d's bit for bit.  Voxels come out in ascending (kx, ky, kz) order
+rather than open3d's hash-map order (include/dpc_render.h states the semantics).
+
+    voxel_down_sample  the thin wrapper over the C ABI: clouds in, [m_i,3] float64 device tensors out
+    downsample_split   downsample_gt.py's file loop, batched: names, a loader and an optional writer
+
+Reading and writing .mat files stays with the caller (load_dense, save), as everywhere in this package.
+"""
+import ctypes
+import math
+import numbers
+
+import numpy as np
+import torch
+
+from . import _native
+
+
+def _voxel_size(voxel_size):
+    if isinstance(voxel_size, bool) or not isinstance(voxel_size, numbers.Real):
+        raise ValueError("voxel_down_sample: voxel_size must be a real number, got %r" % (voxel_size,))
+    vs = float(voxel_size)
+    if not math.isfinite(vs) or vs <= 0.0:
+        raise ValueError("voxel_down_sample: voxel_size must be finite and > 0 (open3d refuses voxel_size <= 0), got %r"
+                         % (voxel_size,))
+    return vs
+
+
+def _cloud(x, i):
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError("voxel_down_sample: cloud %d must be [n,3], got %s" % (i, tuple(t.shape)))
+    if t.dtype not in (torch.float32, torch.float64):
+        raise ValueError("voxel_down_sample: cloud %d must be float32 or float64, got %s" % (i, t.dtype))
+    return t.detach()
+
+
+def _device(clouds):
+    for c in clouds:
+        if c.is_cuda:
+            return c.device
+    if not torch.cuda.is_available():
+        raise RuntimeError("dpc.render voxel downsampling runs on MI355X only: no HIP device (there is no CPU path)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _downsample_packed(clouds, vs):
+    """One native call.  Returns (voxels [V,3] float64 on the device, counts [C] int64, offsets [C] int64) with cloud c's
+    voxels at rows offsets[c] .. offsets[c] + counts[c]."""
+    C = len(clouds)
+    counts = np.array([len(c) for c in clouds], dtype=np.int64)
+    M = int(counts.sum())
+    desc = np.zeros((C, 2), dtype=np.int32)
+    if M > np.iinfo(np.int32).max - 1:
+        raise ValueError("voxel_down_sample: more than 2^31 - 2 points in one call")
+    desc[:, 0] = np.cumsum(counts) - counts
+    desc[:, 1] = counts
+    L = _native.lib()
+    host_desc = desc.ctypes.data_as(ctypes.c_void_p)
+    # the library's own checks (DPC_ERR_SHAPE, before any launch), asked of it without touching the device
+    rc = L.dpc_voxel_downsample(None, M, 0, None, host_desc, C, vs, None, None, None, None, None, None)
+    if rc == _native.DPC_ERR_SHAPE:
+        raise ValueError("voxel_down_sample: refused by dpc_voxel_downsample (voxel_size %r, %d points)" % (vs, M))
+    dev = _device(clouds)
+    dtype = torch.float64 if any(c.dtype == torch.float64 for c in clouds) else torch.float32  # widening is exact
+    if any(c.is_cuda for c in clouds):
+        pts = torch.cat([c.to(device=dev, dtype=dtype) for c in clouds])
+    else:  # one host -> device copy
+        pts = torch.from_numpy(np.concatenate([c.numpy() for c in clouds])).to(dev)
+    pts = pts.contiguous()
+    out = torch.empty((max(M, 1), 3), dtype=torch.float64, device=dev)
+    info = torch.zeros((1 + 2 * C,), dtype=torch.int32, device=dev)  # status, out_count [C], out_offset [C]
+    desc_d = torch.from_numpy(desc).to(dev)
+    ws = torch.empty((max(L.dpc_downsample_workspace_bytes(C, M), 16),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.dpc_voxel_downsample(_native.ptr(pts), M, int(dtype == torch.float64), _native.ptr(desc_d), host_desc, C, vs,
+                                    _native.ptr(out), _native.ptr(info[1:1 + C]), _native.ptr(info[1 + C:]),
+                                    _native.ptr(info[:1]), _native.ptr(ws), _native.stream_ptr(dev))
+    _native.check(rc, "dpc_voxel_downsample")
+    info = info.cpu().numpy().astype(np.int64)  # the call's one synchronisation
+    status = int(info[0])
+    if status & _native.DPC_STATUS_NONFINITE:
+        bad = next(i for i, c in enumerate(clouds) if not bool(torch.isfinite(c).all()))
+        raise ValueError("voxel_down_sample: cloud %d holds a NaN or inf coordinate" % bad)
+    if status & _native.DPC_STATUS_VOXEL_TOO_SMALL:
+        raise ValueError("voxel_down_sample: voxel_size %r is too small for a cloud's extent (open3d: voxel_size * "
+                         "2147483647 < the padded bounding box's largest side)" % vs)
+    if status & _native.DPC_STATUS_KEY_OVERFLOW:
+        raise ValueError("voxel_down_sample: the batch's voxel keys need more than 64 bits at voxel_size %r (%d clouds); "
+                         "pass fewer clouds per call or a larger voxel" % (vs, C))
+    counts, offsets = info[1:1 + C], info[1 + C:]
+    V = int(counts.sum())
+    return out[:V].clone(), counts, offsets
+
+
+def voxel_down_sample(clouds, voxel_size):
+    """open3d.voxel_down_sample(pcd, voxel_size) for every cloud, in one call and one synchronisation.
+
+    clouds: a list of [n_i,3] float32 / float64 arrays or tensors, or a single [n,3] cloud.  Returns a list of [m_i,3]
+    float64 tensors on the device (a single tensor for a single cloud): each voxel's points averaged in fp64, summed one
+    at a time in input order, voxels in ascending (kx, ky, kz) order.  ValueError, before anything touches a device, for a
+    voxel_size that is not finite and > 0 or a cloud that is not [n,3] float; after the call for NaN or inf coordinates,
+    open3d's "voxel_size is too small" rule, or a batch whose voxel keys need more than 64 bits."""
+    vs = _voxel_size(voxel_size)
+    single = isinstance(clouds, (torch.Tensor, np.ndarray))
+    items = [_cloud(c, i) for i, c in enumerate([clouds] if single else list(clouds))]
+    if not items:
+        return []
+    voxels, counts, offsets = _downsample_packed(items, vs)
+    res = [voxels[int(o):int(o) + int(n)] for o, n in zip(offsets, counts)]
+    return res[0] if single else res
+
+
+def downsample_split(model_names, load_dense, voxel_size=0.01, save=None, clouds_per_call=256):
+    """downsample_gt.py's loop (densify/downsample_gt.py:38-57) over model_names, clouds_per_call models per native call.
+
+    load_dense(name) -> [n,3] dense cloud, or None to skip the model (scipy.io.loadmat(path)["points"], say);
+    save(name, points) is called with each [m,3] float64 result (scipy.io.savemat(path, {"points": points}), say).
+    Returns {name: [m,3] float64 numpy}.  The result does not depend on clouds_per_call."""
+    vs = _voxel_size(voxel_size)
+    step = int(clouds_per_call)
+    if step < 1:
+        raise ValueError("downsample_split: clouds_per_call must be >= 1")
+    result, names, clouds = {}, [], []
+
+    def flush():
+        if not names:
+            return
+        voxels, counts, offsets = _downsample_packed(clouds, vs)
+        host = voxels.cpu().numpy()
+        for name, o, n in zip(names, offsets, counts):
+            pts = host[int(o):int(o) + int(n)]
+            result[name] = pts
+            if save is not None:
+                save(name, pts)
+        del names[:], clouds[:]
+
+    for name in model_names:
+        dense = load_dense(name)
+        if dense is None:
+            continue
+        clouds.append(_cloud(dense, len(clouds)))
+        names.append(name)
+        if len(names) >= step:
+            flush()
+    flush()
+    return result
