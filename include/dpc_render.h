@@ -56,10 +56,14 @@ enum {
 /* Bits of the optional device status word (DpcParams.status). */
 enum {
   DPC_STATUS_BAD_INDEX = 1,   /* a point_index entry was outside [0, N_src): the point was dropped (the reference's fancy
-                               * indexing raises IndexError there, dpc/util/point_cloud_to.py:266-295)                   */
+                               * indexing raises IndexError there, dpc/util/point_cloud_to.py:266-295); dpc_densify: a
+                               * mesh id out of range or inconsistent, or an edge on more than max_face_count faces    */
   DPC_STATUS_VOXEL_TOO_SMALL = 2, /* dpc_voxel_downsample: open3d's "voxel_size is too small" (nothing was computed)    */
   DPC_STATUS_KEY_OVERFLOW = 4,    /* dpc_voxel_downsample: the batch's voxel keys need more than 64 bits (nothing computed) */
-  DPC_STATUS_NONFINITE = 8        /* dpc_voxel_downsample: a NaN or infinite coordinate (nothing was computed)          */
+  DPC_STATUS_NONFINITE = 8,       /* dpc_voxel_downsample: a NaN or infinite coordinate (nothing was computed);
+                                   * dpc_densify: a non-finite vertex, edge length or midpoint (that model stops)       */
+  DPC_STATUS_DENSIFY_ORDER = 16   /* dpc_densify: a new edge longer than kDnBand x the round's longest edge: the
+                                   * round-ordering argument failed and the output may differ from the reference's      */
 };
 
 /* Geometry and camera constants of one call (dpc/resources/default_config.yaml:77-89 and the cfg fields
@@ -410,6 +414,43 @@ size_t dpc_downsample_workspace_bytes(int clouds, int members);
 int dpc_voxel_downsample(const void* pts, int n_pts, int is_f64, const int32_t* cloud_desc, const int32_t* host_cloud_desc,
                          int clouds, double voxel_size, double* out, int32_t* out_count, int32_t* out_offset,
                          int32_t* status, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Mesh densification of ground-truth models (densify/densify_single.py: parseObj, removeWeirdDuplicate, then densifyN
+ * times utils.densify) for `models` ragged meshes in one call, in fp64.  Per model, the reference repeats: pop the live
+ * edge e = (lo, hi) first by (length descending, edge index ascending); append the vertex (V[lo] + V[hi]) / 2; append the
+ * edges [lo, new] and [hi, new] (the parent's faces, in its slot order); for each face on e, in slot order, append the two
+ * sub-faces (hi -> new, then lo -> new) and the median edge [opposite vertex, new] (those two faces).  Lengths are
+ * sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) of V[E[0]] - V[E[1]]: np.linalg.norm with numpy's OpenBLAS dot.
+ *
+ * Inputs are packed; model m's row of model_desc (DEVICE) = host_model_desc (HOST) is 7 int32:
+ *   v_start, v_count   rows of verts [n_verts,3] float64 (the parsed vertices);
+ *   e_start, e_count   rows of edges [n_edges,2] int32: model-local vertex ids (lo, hi), in the reference's edge order;
+ *   f_start, f_count   rows of faces [n_faces,3] int32 (model-local vertex ids, after removeWeirdDuplicate) and of
+ *                      face_edges [n_faces,3] int32: the model-local edge opposite vertex j of the face;
+ *   budget             splits (the reference's densifyN), >= 0.
+ * out [sum(v_count + budget), 3] float64: model m's points start at the exclusive prefix of (v_count + budget): its vertices,
+ * then its midpoints in split order (the reference's "points").  max_face_count >= the most faces on any edge.
+ *
+ * The call enqueues `rounds` rounds (after the set-up when `begin` != 0; the first call of a job has begin = 1, later ones
+ * the same arguments with begin = 0).  A round splits, per model, every live edge longer than 0.87 x its longest live edge,
+ * in the order above, up to the budget (the new edges are never longer than that).  *active (DEVICE, zeroed by
+ * the caller before begin) counts the models with splits left: read it after a synchronisation of the caller's own and
+ * enqueue more rounds until it is 0.  status (DEVICE, zeroed by the caller; NULL allowed): DPC_STATUS_BAD_INDEX,
+ * DPC_STATUS_NONFINITE (that model is not densified), DPC_STATUS_DENSIFY_ORDER.  No floating-point atomics; results are
+ * bit-identical from run to run and do not depend on how models are batched or on the rounds per call.  No host
+ * synchronisation and no host -> device copy.  DPC_ERR_SHAPE, before any launch, for negative counts or rounds, a range
+ * outside its array, a budget > 0 with no edges, max_face_count outside [0, 2^20], or a model whose output rows, edges
+ * (e + n (2 + D)), 3 x faces (3 (f + 2 n D)) or slots (3 f + 4 n D) exceed 2^31 - 1, with D = max(2, max_face_count).  With
+ * valid arguments and NULL device pointers it returns DPC_ERR_NULL without touching a device.  workspace:
+ * dpc_densify_workspace_bytes(models, sum e_count, sum f_count, sum budget, max_face_count) bytes, at most
+ * 72 models + 68 (E + N (2 + D)) + 36 (F + 2 N D) + 4 (3 F + 4 N D) + 512.  Added without a new ABI number.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_densify_workspace_bytes(int models, int64_t edges, int64_t faces, int64_t splits, int max_face_count);
+int dpc_densify(const double* verts, int n_verts, const int32_t* edges, int n_edges, const int32_t* faces,
+                const int32_t* face_edges, int n_faces, const int32_t* model_desc, const int32_t* host_model_desc,
+                int models, int max_face_count, int begin, int rounds, double* out, int32_t* status, int32_t* active,
+                void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Opt-in measurement aid (nothing in the reference corresponds to it).  After dpc_profile_enable(capacity)

@@ -27,6 +27,7 @@ DPC_STATUS_BAD_INDEX = 1
 DPC_STATUS_VOXEL_TOO_SMALL = 2
 DPC_STATUS_KEY_OVERFLOW = 4
 DPC_STATUS_NONFINITE = 8
+DPC_STATUS_DENSIFY_ORDER = 16
 
 # every symbol include/dpc_render.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = (
@@ -37,6 +38,7 @@ SYMBOLS = (
     "dpc_project_loss_step",
     "dpc_nearest_workspace_bytes", "dpc_point_cloud_distance", "dpc_icp_workspace_bytes", "dpc_icp_point_to_point",
     "dpc_chamfer_workspace_bytes", "dpc_nearest_batched", "dpc_downsample_workspace_bytes", "dpc_voxel_downsample",
+    "dpc_densify_workspace_bytes", "dpc_densify",
     "dpc_profile_enable", "dpc_profile_disable", "dpc_profile_count", "dpc_profile_get", "dpc_profile_get_id", "dpc_profile_pair_overhead",
 )
 
@@ -124,6 +126,11 @@ def lib():
         L.dpc_downsample_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
         L.dpc_voxel_downsample.restype = ctypes.c_int
         L.dpc_voxel_downsample.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_double] + [vp] * 6
+        L.dpc_densify_workspace_bytes.restype = ctypes.c_size_t
+        L.dpc_densify_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
+        L.dpc_densify.restype = ctypes.c_int
+        L.dpc_densify.argtypes = ([vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp] + [ctypes.c_int] * 4
+                                  + [vp] * 5)
         L.dpc_smooth.restype = ctypes.c_int
         L.dpc_smooth.argtypes = [pp, vp, vp, ctypes.c_int, vp, vp, vp, vp]
         L.dpc_point_dropout_indices.restype = ctypes.c_int
