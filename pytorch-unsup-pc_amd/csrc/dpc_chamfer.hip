@@ -20,6 +20,7 @@
 #include <cstdint>
 
 #include "../../include/dpc_render.h"
+#include "dpc_batch.h"
 #include "dpc_nearest.h"
 #include "dpc_profile.h"
 
@@ -49,8 +50,8 @@ __host__ __device__ inline int ch_src_blocks(int ns) { return (ns + kChThreads -
 __host__ __device__ inline int ch_slices(int ns, int nt, int slice) { return ns > 0 ? (nt + slice - 1) / slice : 0; }
 __host__ __device__ inline int ch_chunks(int ns) { return (ns + kChChunk - 1) / kChChunk; }
 
-// Host side of the geometry, from a validated host table.  Target slices as nearest_slices: enough (block, slice) items
-// for about four workgroups per CU, slices of whole 256-target groups; a split-sized batch runs with one slice.
+// Host side of the geometry, from a validated host table.  Target slices by nearest_slice (dpc_nearest.h) over the
+// batch's source blocks and its largest target; a split-sized batch runs with one slice.
 ChGeom chamfer_geometry(int pairs, const int32_t* desc) {
   ChGeom g{0, 0, 0, 0, 256, 0};
   for (int p = 0; p < pairs; ++p) {
@@ -60,13 +61,7 @@ ChGeom chamfer_geometry(int pairs, const int32_t* desc) {
     g.chunks += ch_chunks(ns);
     if (ns > 0 && nt > g.max_nt) g.max_nt = nt;
   }
-  if (g.max_nt > 0) {
-    int64_t want = g.blocks > 0 ? (1024 + g.blocks - 1) / g.blocks : 1;
-    const int64_t max_slices = (g.max_nt + 255) / 256;
-    want = want < 1 ? 1 : (want > max_slices ? max_slices : want);
-    const int64_t slice = (g.max_nt + want - 1) / want;
-    g.slice = (int)(((slice + 255) / 256) * 256);
-  }
+  if (g.max_nt > 0) g.slice = (int)nearest_slice(g.blocks, g.max_nt);
   for (int p = 0; p < pairs; ++p)
     g.work += (int64_t)ch_src_blocks(desc[4 * p + 1]) * ch_slices(desc[4 * p + 1], desc[4 * p + 3], g.slice);
   return g;
@@ -80,43 +75,25 @@ struct ChWork {
   int* part_idx;      // [work * 256]
 };
 
-size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 size_t chamfer_carve(const ChGeom& g, int pairs, size_t tsize, char* base, ChWork* w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align16(bytes);
-    return p;
-  };
+  Carver c{base};
   ChWork t;
   const size_t np1 = (size_t)pairs + 1;
-  t.pre.blk = reinterpret_cast<int32_t*>(take(np1 * sizeof(int32_t)));
-  t.pre.work = reinterpret_cast<int32_t*>(take(np1 * sizeof(int32_t)));
-  t.pre.out = reinterpret_cast<int32_t*>(take(np1 * sizeof(int32_t)));
-  t.pre.chunk = reinterpret_cast<int32_t*>(take(np1 * sizeof(int32_t)));
-  t.chunk_sum = reinterpret_cast<double*>(take((size_t)g.chunks * sizeof(double)));
-  t.dist = take((size_t)g.points * tsize);
-  t.part_dist = take((size_t)g.work * kChThreads * tsize);
-  t.part_idx = reinterpret_cast<int*>(take((size_t)g.work * kChThreads * sizeof(int)));
+  t.pre.blk = c.take<int32_t>(np1);
+  t.pre.work = c.take<int32_t>(np1);
+  t.pre.out = c.take<int32_t>(np1);
+  t.pre.chunk = c.take<int32_t>(np1);
+  t.chunk_sum = c.take<double>(g.chunks);
+  t.dist = c.take<char>((size_t)g.points * tsize);
+  t.part_dist = c.take<char>((size_t)g.work * kChThreads * tsize);
+  t.part_idx = c.take<int>((size_t)g.work * kChThreads);
   if (w) *w = t;
-  return off + 16;
-}
-
-// The largest p < P with pre[p] <= x: pairs without items share their prefix with the next pair that has some, so the
-// search always lands on the pair that owns item x.
-__device__ inline int owner(const int32_t* __restrict__ pre, int pairs, int x) {
-  int lo = 0, hi = pairs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (pre[mid] <= x) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+  return c.off + 16;
 }
 
 __global__ __launch_bounds__(kChScanThreads) void k_chamfer_scan(const int32_t* __restrict__ desc, int pairs, int slice,
                                                                  ChPrefix pre) {
-  __shared__ int32_t sums[4][kChScanThreads];
+  __shared__ int32_t scratch[kChScanThreads / 64 + 1];
   const int t = threadIdx.x;
   const int seg = (pairs + kChScanThreads - 1) / kChScanThreads;
   const int p0 = min(pairs, t * seg), p1 = min(pairs, p0 + seg);
@@ -128,21 +105,9 @@ __global__ __launch_bounds__(kChScanThreads) void k_chamfer_scan(const int32_t* 
     loc[2] += ns;
     loc[3] += ch_chunks(ns);
   }
+  int32_t run[4], total[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) sums[k][t] = loc[k];
-  __syncthreads();
-  for (int off = 1; off < kChScanThreads; off <<= 1) {  // inclusive Hillis-Steele scan of the segment totals
-    int32_t v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = t >= off ? sums[k][t - off] : 0;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 4; ++k) sums[k][t] += v[k];
-    __syncthreads();
-  }
-  int32_t run[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) run[k] = sums[k][t] - loc[k];
+  for (int k = 0; k < 4; ++k) total[k] = block_scan<kChScanThreads>(loc[k], &run[k], scratch);
   for (int p = p0; p < p1; ++p) {
     const int ns = desc[4 * p + 1], nt = desc[4 * p + 3];
     pre.blk[p] = run[0]; pre.work[p] = run[1]; pre.out[p] = run[2]; pre.chunk[p] = run[3];
@@ -151,8 +116,8 @@ __global__ __launch_bounds__(kChScanThreads) void k_chamfer_scan(const int32_t* 
     run[2] += ns;
     run[3] += ch_chunks(ns);
   }
-  if (t == kChScanThreads - 1) {
-    pre.blk[pairs] = sums[0][t]; pre.work[pairs] = sums[1][t]; pre.out[pairs] = sums[2][t]; pre.chunk[pairs] = sums[3][t];
+  if (t == 0) {
+    pre.blk[pairs] = total[0]; pre.work[pairs] = total[1]; pre.out[pairs] = total[2]; pre.chunk[pairs] = total[3];
   }
 }
 
@@ -302,18 +267,12 @@ __global__ __launch_bounds__(64) void k_chamfer_mean(int pairs, ChPrefix pre, co
   mean[p] = s / (double)(pre.out[p + 1] - pre.out[p]);
 }
 
-// DPC_ERR_SHAPE for a table the reference could not evaluate or the kernels cannot index; DPC_OK otherwise.
+// DPC_ERR_SHAPE for a table the reference could not evaluate or the kernels cannot index (the output points, the sum of
+// src_count, are indexed by int32); DPC_OK otherwise.  n_pts < 0: the length is not known yet.
 int chamfer_check(int pairs, const int32_t* desc, int64_t n_pts) {
-  int64_t points = 0;
-  for (int p = 0; p < pairs; ++p) {
-    const int64_t s0 = desc[4 * p], ns = desc[4 * p + 1], t0 = desc[4 * p + 2], nt = desc[4 * p + 3];
-    if (s0 < 0 || ns < 0 || t0 < 0 || nt < 0) return DPC_ERR_SHAPE;
-    if (n_pts >= 0 && (s0 + ns > n_pts || t0 + nt > n_pts)) return DPC_ERR_SHAPE;
-    if (nt == 0 && ns > 0) return DPC_ERR_SHAPE;  // argmin over an empty set: the reference raises
-    points += ns;
-    if (points > INT32_MAX) return DPC_ERR_SHAPE;
-  }
-  return DPC_OK;
+  return check_desc<4>(desc, pairs, {n_pts, n_pts}, INT32_MAX, nullptr, [](const int32_t* d) {
+    return !(d[3] == 0 && d[1] > 0);  // argmin over an empty set: the reference raises
+  });
 }
 
 template <class T>

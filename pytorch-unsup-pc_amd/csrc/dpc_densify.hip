@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "../../include/dpc_render.h"
+#include "dpc_batch.h"
 #include "dpc_profile.h"
 
 namespace {
@@ -61,36 +62,29 @@ struct DnWork {
   int32_t* sp_sb;  // [Ecap] its first new slot (h1: sb, h2: sb + deg, median k: sb + 2 deg + 2k)
 };
 
-size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 size_t dn_carve(int models, int64_t ecap, int64_t fcap, int64_t scap, char* base, DnWork* w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align16(bytes);
-    return p;
-  };
+  Carver c{base};
   const size_t E = (size_t)ecap, F = (size_t)fcap, S = (size_t)scap;
   DnWork t;
-  t.model = reinterpret_cast<DnModel*>(take((size_t)models * sizeof(DnModel)));
-  t.lo = reinterpret_cast<int32_t*>(take(E * 4));
-  t.hi = reinterpret_cast<int32_t*>(take(E * 4));
-  t.len = reinterpret_cast<double*>(take(E * 8));
-  t.deg = reinterpret_cast<int32_t*>(take(E * 4));
-  t.soff = reinterpret_cast<int32_t*>(take(E * 4));
-  t.srank = reinterpret_cast<int32_t*>(take(E * 4));
-  t.fv = reinterpret_cast<int32_t*>(take(3 * F * 4));
-  t.fe = reinterpret_cast<int32_t*>(take(3 * F * 4));
-  t.fp = reinterpret_cast<int32_t*>(take(3 * F * 4));
-  t.slots = reinterpret_cast<int32_t*>(take(S * 4));
-  for (int k = 0; k < 2; ++k) t.keys[k] = reinterpret_cast<uint64_t*>(take(E * 8));
-  for (int k = 0; k < 2; ++k) t.rows[k] = reinterpret_cast<int32_t*>(take(E * 4));
-  t.sp_e = reinterpret_cast<int32_t*>(take(E * 4));
-  t.sp_eb = reinterpret_cast<int32_t*>(take(E * 4));
-  t.sp_fb = reinterpret_cast<int32_t*>(take(E * 4));
-  t.sp_sb = reinterpret_cast<int32_t*>(take(E * 4));
+  t.model = c.take<DnModel>(models);
+  t.lo = c.take<int32_t>(E);
+  t.hi = c.take<int32_t>(E);
+  t.len = c.take<double>(E);
+  t.deg = c.take<int32_t>(E);
+  t.soff = c.take<int32_t>(E);
+  t.srank = c.take<int32_t>(E);
+  t.fv = c.take<int32_t>(3 * F);
+  t.fe = c.take<int32_t>(3 * F);
+  t.fp = c.take<int32_t>(3 * F);
+  t.slots = c.take<int32_t>(S);
+  for (int k = 0; k < 2; ++k) t.keys[k] = c.take<uint64_t>(E);
+  for (int k = 0; k < 2; ++k) t.rows[k] = c.take<int32_t>(E);
+  t.sp_e = c.take<int32_t>(E);
+  t.sp_eb = c.take<int32_t>(E);
+  t.sp_fb = c.take<int32_t>(E);
+  t.sp_sb = c.take<int32_t>(E);
   if (w) *w = t;
-  return off;
+  return c.off;
 }
 
 // Per-model capacities: a split adds 2 + deg edges, 2 deg faces and 4 deg slots, deg <= D = max(2, max_face_count).
@@ -104,34 +98,11 @@ __device__ inline double dn_length(const double* a, const double* b) {
   return sqrt(fma(dz, dz, fma(dy, dy, dx * dx)));
 }
 
-// Exclusive scan of one int per thread over the kDnThreads of the block; returns the total.
-__device__ inline int dn_scan(int v, int* excl, int* scratch) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  int x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) scratch[wave] = x;
-  __syncthreads();
-  if (t == 0) {
-    int run = 0;
-    for (int w = 0; w < kDnWaves; ++w) { const int s = scratch[w]; scratch[w] = run; run += s; }
-    scratch[kDnWaves] = run;
-  }
-  __syncthreads();
-  *excl = scratch[wave] + x - v;
-  const int total = scratch[kDnWaves];
-  __syncthreads();
-  return total;
-}
-
 // desc row: v_start, v_count, e_start, e_count, f_start, f_count, budget
 constexpr int kDnDesc = 7;
 
 __global__ __launch_bounds__(kDnPlanThreads) void k_dn_plan(const int32_t* __restrict__ desc, int models, int D, DnWork w) {
-  __shared__ int64_t part[4][kDnPlanThreads];
+  __shared__ int64_t scratch[kDnPlanThreads / 64 + 1];
   const int t = threadIdx.x;
   const int seg = (models + kDnPlanThreads - 1) / kDnPlanThreads;
   const int m0 = min(models, t * seg), m1 = min(models, m0 + seg);
@@ -143,15 +114,8 @@ __global__ __launch_bounds__(kDnPlanThreads) void k_dn_plan(const int32_t* __res
     s[2] += dn_fcap(d[5], d[6], D);
     s[3] += dn_scap(d[5], d[6], D);
   }
-  for (int k = 0; k < 4; ++k) part[k][t] = s[k];
-  __syncthreads();
-  if (t == 0) {  // 1024 partial sums, serially: once per call
-    int64_t run[4] = {0, 0, 0, 0};
-    for (int i = 0; i < kDnPlanThreads; ++i)
-      for (int k = 0; k < 4; ++k) { const int64_t x = part[k][i]; part[k][i] = run[k]; run[k] += x; }
-  }
-  __syncthreads();
-  int64_t b[4] = {part[0][t], part[1][t], part[2][t], part[3][t]};
+  int64_t b[4];
+  for (int k = 0; k < 4; ++k) block_scan<kDnPlanThreads>(s[k], &b[k], scratch);
   for (int m = m0; m < m1; ++m) {
     const int32_t* d = desc + kDnDesc * m;
     DnModel& M = w.model[m];
@@ -235,7 +199,7 @@ __global__ __launch_bounds__(kDnThreads) void k_dn_init(const double* __restrict
     const int g = i < ne ? deg[i] : 0;
     if (g > D) flags |= DPC_STATUS_BAD_INDEX;  // more faces on an edge than the caller's max_face_count
     int excl;
-    const int total = dn_scan(g, &excl, scratch);
+    const int total = block_scan<kDnThreads>(g, &excl, scratch);
     if (i < ne) soff[i] = run + excl;
     run += total;
   }
@@ -329,7 +293,7 @@ __global__ __launch_bounds__(kDnThreads) void k_dn_round(DnWork w, double* __res
     const double L = i < M.nE ? len[i] : -1.0;
     const bool in = L > thr || (L >= lmax && L >= 0.0);
     int excl;
-    const int total = dn_scan(in ? 1 : 0, &excl, scratch);
+    const int total = block_scan<kDnThreads>(in ? 1 : 0, &excl, scratch);
     if (in) {
       const uint64_t key = lbits - dn_bits(L);  // both positive: descending length is ascending key
       kin[B + excl] = key;
@@ -358,7 +322,7 @@ __global__ __launch_bounds__(kDnThreads) void k_dn_round(DnWork w, double* __res
     for (int i = t; i < B; i += kDnThreads) atomicAdd(&hist[(int)((ks[i] >> (8 * pass)) & 0xff)], 1);
     __syncthreads();
     int base;
-    dn_scan(hist[t], &base, scratch);  // digit t starts at base
+    block_scan<kDnThreads>(hist[t], &base, scratch);  // digit t starts at base
     for (int c0 = 0; c0 < B; c0 += kDnThreads) {
       const int i = c0 + t;
       const bool live = i < B;
@@ -404,9 +368,9 @@ __global__ __launch_bounds__(kDnThreads) void k_dn_round(DnWork w, double* __res
     const int e = live ? order[r] : 0;
     const int g = live ? deg[e] : 0;
     int xe, xf, xs;
-    const int te = dn_scan(live ? 2 + g : 0, &xe, scratch);
-    const int tf = dn_scan(2 * g, &xf, scratch);
-    const int ts = dn_scan(4 * g, &xs, scratch);
+    const int te = block_scan<kDnThreads>(live ? 2 + g : 0, &xe, scratch);
+    const int tf = block_scan<kDnThreads>(2 * g, &xf, scratch);
+    const int ts = block_scan<kDnThreads>(4 * g, &xs, scratch);
     if (live) {
       const int eb = M.nE + re + xe, fb = M.nF + rf + xf, sb = M.nS + rs + xs;
       w.sp_e[M.ebase + r] = e;
@@ -542,28 +506,6 @@ struct DnTotals {
   int64_t rows, edges, faces, splits;
 };
 
-int dn_check(const int32_t* desc, int models, int n_verts, int n_edges, int n_faces, int D, DnTotals* tot) {
-  DnTotals s{0, 0, 0, 0};
-  for (int m = 0; m < models; ++m) {
-    const int32_t* d = desc + kDnDesc * m;
-    const int64_t v0 = d[0], nv = d[1], e0 = d[2], ne = d[3], f0 = d[4], nf = d[5], n = d[6];
-    if (v0 < 0 || nv < 0 || v0 + nv > n_verts || e0 < 0 || ne < 0 || e0 + ne > n_edges || f0 < 0 || nf < 0 ||
-        f0 + nf > n_faces || n < 0)
-      return DPC_ERR_SHAPE;
-    if (n > 0 && ne == 0) return DPC_ERR_SHAPE;  // nothing to split
-    // every model-local id (output rows, edges, 3 x faces, slots) must fit an int32
-    if (nv + n > INT32_MAX || dn_ecap(ne, n, D) > INT32_MAX || 3 * dn_fcap(nf, n, D) > INT32_MAX ||
-        dn_scap(nf, n, D) > INT32_MAX)
-      return DPC_ERR_SHAPE;
-    s.rows += nv + n;
-    s.edges += ne;
-    s.faces += nf;
-    s.splits += n;
-  }
-  *tot = s;
-  return DPC_OK;
-}
-
 inline int dn_maxdeg(int max_face_count) { return max_face_count > 2 ? max_face_count : 2; }
 
 }  // namespace
@@ -587,9 +529,24 @@ int dpc_densify(const double* verts, int n_verts, const int32_t* edges, int n_ed
   if (models == 0) return DPC_OK;
   if (!host_model_desc) return DPC_ERR_NULL;
   const int D = dn_maxdeg(max_face_count);
-  DnTotals tot;
-  const int rc = dn_check(host_model_desc, models, n_verts, n_edges, n_faces, D, &tot);
+  const int rc = check_desc<kDnDesc>(
+      host_model_desc, models, {(int64_t)n_verts, (int64_t)n_edges, (int64_t)n_faces}, INT64_MAX, nullptr,
+      [D](const int32_t* d) {
+        const int64_t nv = d[1], ne = d[3], nf = d[5], n = d[6];
+        if (n < 0 || (n > 0 && ne == 0)) return false;  // a budget, and with one something to split
+        // every model-local id (output rows, edges, 3 x faces, slots) must fit an int32
+        return nv + n <= INT32_MAX && dn_ecap(ne, n, D) <= INT32_MAX && 3 * dn_fcap(nf, n, D) <= INT32_MAX &&
+               dn_scap(nf, n, D) <= INT32_MAX;
+      });
   if (rc != DPC_OK) return rc;
+  DnTotals tot{0, 0, 0, 0};
+  for (int m = 0; m < models; ++m) {
+    const int32_t* d = host_model_desc + (int64_t)kDnDesc * m;
+    tot.rows += (int64_t)d[1] + d[6];
+    tot.edges += d[3];
+    tot.faces += d[5];
+    tot.splits += d[6];
+  }
   if (!model_desc || !out || !active || !workspace) return DPC_ERR_NULL;
   if (begin && ((tot.rows > 0 && !verts) || (tot.edges > 0 && !edges) || (tot.faces > 0 && (!faces || !face_edges))))
     return DPC_ERR_NULL;

@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "../../include/dpc_render.h"
+#include "dpc_batch.h"
 #include "dpc_profile.h"
 
 namespace {
@@ -61,74 +62,33 @@ struct DsWork {
   int32_t* vstart;       // [M + 1] first sorted position of each voxel, vstart[V] = M
 };
 
-size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 inline int64_t ds_tiles(int64_t members) { return (members + kDsTile - 1) / kDsTile; }
 
 size_t ds_carve(int clouds, int64_t members, char* base, DsWork* w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align16(bytes);
-    return p;
-  };
+  Carver c{base};
   const size_t C = (size_t)clouds, M = (size_t)members, T = (size_t)ds_tiles(members);
   DsWork t;
-  t.mpre = reinterpret_cast<int32_t*>(take((C + 1) * sizeof(int32_t)));
-  t.lo = reinterpret_cast<double*>(take(3 * C * sizeof(double)));
-  t.kmax = reinterpret_cast<double*>(take(3 * C * sizeof(double)));
-  t.flags = reinterpret_cast<int32_t*>(take(C * sizeof(int32_t)));
-  t.plan = reinterpret_cast<DsPlan*>(take(sizeof(DsPlan)));
-  for (int k = 0; k < 2; ++k) t.keys[k] = reinterpret_cast<uint64_t*>(take(M * sizeof(uint64_t)));
-  for (int k = 0; k < 2; ++k) t.rows[k] = reinterpret_cast<int32_t*>(take(M * sizeof(int32_t)));
-  t.hist = reinterpret_cast<int32_t*>(take((size_t)kDsRadix * T * sizeof(int32_t)));
-  t.hist_off = reinterpret_cast<int32_t*>(take((size_t)kDsRadix * T * sizeof(int32_t)));
-  t.digit_total = reinterpret_cast<int32_t*>(take(kDsRadix * sizeof(int32_t)));
-  t.tile_heads = reinterpret_cast<int32_t*>(take(T * sizeof(int32_t)));
-  t.tile_off = reinterpret_cast<int32_t*>(take(T * sizeof(int32_t)));
-  t.vstart = reinterpret_cast<int32_t*>(take((M + 1) * sizeof(int32_t)));
+  t.mpre = c.take<int32_t>(C + 1);
+  t.lo = c.take<double>(3 * C);
+  t.kmax = c.take<double>(3 * C);
+  t.flags = c.take<int32_t>(C);
+  t.plan = c.take<DsPlan>(1);
+  for (int k = 0; k < 2; ++k) t.keys[k] = c.take<uint64_t>(M);
+  for (int k = 0; k < 2; ++k) t.rows[k] = c.take<int32_t>(M);
+  t.hist = c.take<int32_t>((size_t)kDsRadix * T);
+  t.hist_off = c.take<int32_t>((size_t)kDsRadix * T);
+  t.digit_total = c.take<int32_t>(kDsRadix);
+  t.tile_heads = c.take<int32_t>(T);
+  t.tile_off = c.take<int32_t>(T);
+  t.vstart = c.take<int32_t>(M + 1);
   if (w) *w = t;
-  return off;
-}
-
-// The largest c < C with pre[c] <= x: empty clouds share their prefix with the next cloud, so x lands on its owner.
-__device__ inline int ds_owner(const int32_t* __restrict__ pre, int clouds, int x) {
-  int lo = 0, hi = clouds - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (pre[mid] <= x) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+  return c.off;
 }
 
 __device__ inline int ds_bits(double v) {  // bits to hold the integer v in [0, 2^31)
   int b = 0;
   while (b < 31 && (double)(1u << b) <= v) ++b;
   return b;
-}
-
-// Exclusive block scan of one int per thread (n threads, n a multiple of 64, <= 1024); returns the block total.
-template <int N>
-__device__ inline int ds_block_scan(int v, int* excl, int* scratch) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  int x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) scratch[wave] = x;
-  __syncthreads();
-  if (t == 0) {
-    int run = 0;
-    for (int w = 0; w < N / 64; ++w) { const int s = scratch[w]; scratch[w] = run; run += s; }
-    scratch[N / 64] = run;
-  }
-  __syncthreads();
-  *excl = scratch[wave] + x - v;
-  const int total = scratch[N / 64];
-  __syncthreads();
-  return total;
 }
 
 template <class T>
@@ -196,7 +156,7 @@ __global__ __launch_bounds__(kDsScanThreads) void k_ds_plan(const int32_t* __res
     for (int k = 0; k < 3; ++k) km[k] = fmax(km[k], w.kmax[3 * c + k]);  // NaN (a non-finite cloud) is dropped
   }
   int run;
-  const int total = ds_block_scan<kDsScanThreads>(loc, &run, scratch);
+  const int total = block_scan<kDsScanThreads>(loc, &run, scratch);
   for (int c = c0; c < c1; ++c) { w.mpre[c] = run; run += desc[2 * c + 1]; }
 #pragma unroll
   for (int k = 0; k < 3; ++k) smax[k][t] = km[k];
@@ -238,7 +198,7 @@ __global__ __launch_bounds__(kDsThreads) void k_ds_keys(const T* __restrict__ pt
   const DsPlan plan = *w.plan;
   if (plan.abort) return;
   for (int m = blockIdx.x * kDsThreads + threadIdx.x; m < members; m += gridDim.x * kDsThreads) {
-    const int c = ds_owner(w.mpre, clouds, m);
+    const int c = owner(w.mpre, clouds, m);
     const int row = desc[2 * c] + (m - w.mpre[c]);
     const T* p = pts + 3 * (size_t)row;
     uint64_t key = (uint64_t)c;
@@ -283,7 +243,7 @@ __global__ __launch_bounds__(kDsScanThreads) void k_ds_digits(int tiles, int pas
     const int b = b0 + threadIdx.x;
     const int v = b < tiles ? row[b] : 0;
     int excl;
-    const int total = ds_block_scan<kDsScanThreads>(v, &excl, scratch);
+    const int total = block_scan<kDsScanThreads>(v, &excl, scratch);
     if (b < tiles) off[b] = run + excl;
     run += total;
   }
@@ -307,7 +267,7 @@ __global__ __launch_bounds__(kDsThreads) void k_ds_scatter(int members, int pass
   // digit d starts at (members of smaller digits) + (members of digit d in earlier tiles)
   const int total_d = w.digit_total[t];
   int excl;
-  ds_block_scan<kDsThreads>(total_d, &excl, scratch);
+  block_scan<kDsThreads>(total_d, &excl, scratch);
   base[t] = excl + w.hist_off[(size_t)t * tiles + tile];
   __syncthreads();
   const uint64_t below = (1ull << lane) - 1;
@@ -366,7 +326,7 @@ __global__ __launch_bounds__(kDsThreads) void k_ds_heads(int members, DsWork w) 
     if (i < members) n += ds_head(keys, i);
   }
   int excl;
-  const int total = ds_block_scan<kDsThreads>(n, &excl, scratch);
+  const int total = block_scan<kDsThreads>(n, &excl, scratch);
   if (threadIdx.x == 0) w.tile_heads[blockIdx.x] = total;
 }
 
@@ -378,7 +338,7 @@ __global__ __launch_bounds__(kDsScanThreads) void k_ds_tiles(int tiles, int memb
     const int b = b0 + threadIdx.x;
     const int v = b < tiles ? w.tile_heads[b] : 0;
     int excl;
-    const int total = ds_block_scan<kDsScanThreads>(v, &excl, scratch);
+    const int total = block_scan<kDsScanThreads>(v, &excl, scratch);
     if (b < tiles) w.tile_off[b] = run + excl;
     run += total;
   }
@@ -400,7 +360,7 @@ __global__ __launch_bounds__(kDsThreads) void k_ds_voxels(int members, DsWork w)
     if (i < members) n += ds_head(keys, i);
   }
   int excl;
-  ds_block_scan<kDsThreads>(n, &excl, scratch);
+  block_scan<kDsThreads>(n, &excl, scratch);
   int v = w.tile_off[blockIdx.x] + excl;
   for (int j = 0; j < kDsItems; ++j) {
     const int64_t i = first + j;
@@ -471,18 +431,6 @@ __global__ __launch_bounds__(kDsThreads) void k_ds_clouds(int clouds, DsWork w, 
   out_count[c] = b - a;
 }
 
-int ds_check(int clouds, const int32_t* desc, int64_t n_pts, int64_t* members) {
-  int64_t m = 0;
-  for (int c = 0; c < clouds; ++c) {
-    const int64_t s0 = desc[2 * c], n = desc[2 * c + 1];
-    if (s0 < 0 || n < 0 || s0 + n > n_pts) return DPC_ERR_SHAPE;
-    m += n;
-    if (m > INT32_MAX - 1) return DPC_ERR_SHAPE;
-  }
-  *members = m;
-  return DPC_OK;
-}
-
 inline unsigned ds_grid(int64_t members) {
   const int64_t b = (members + kDsThreads - 1) / kDsThreads;
   return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
@@ -535,7 +483,9 @@ int dpc_voxel_downsample(const void* pts, int n_pts, int is_f64, const int32_t* 
   if (clouds == 0) return DPC_OK;
   if (!host_cloud_desc) return DPC_ERR_NULL;
   int64_t members = 0;
-  const int rc = ds_check(clouds, host_cloud_desc, n_pts, &members);
+  // members are indexed by int32, and vstart holds M + 1 of them
+  const int rc = check_desc<2>(host_cloud_desc, clouds, {(int64_t)n_pts}, INT32_MAX - 1, &members,
+                               [](const int32_t*) { return true; });
   if (rc != DPC_OK) return rc;
   if (!cloud_desc || !out_count || !out_offset || !workspace || (members > 0 && (!pts || !out))) return DPC_ERR_NULL;
   hipStream_t st = (hipStream_t)stream;

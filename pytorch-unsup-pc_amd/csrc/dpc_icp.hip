@@ -20,6 +20,8 @@
 #include <limits>
 
 #include "../../include/dpc_render.h"
+#include "dpc_batch.h"
+#include "dpc_nearest.h"
 #include "dpc_profile.h"
 
 namespace {
@@ -33,21 +35,17 @@ struct IcpGeom {
   int max_ns, max_nt, src_blocks, slice, nslice;
 };
 
-IcpGeom icp_geometry(int pairs, const int32_t* src_count, const int32_t* tgt_count) {
+// From the source and target count of every pair: src_count[p * stride], tgt_count[p * stride].
+IcpGeom icp_geometry(int pairs, const int32_t* src_count, const int32_t* tgt_count, int stride) {
   IcpGeom g{0, 0, 0, 256, 1};
   for (int p = 0; p < pairs; ++p) {
-    g.max_ns = src_count[p] > g.max_ns ? src_count[p] : g.max_ns;
-    g.max_nt = tgt_count[p] > g.max_nt ? tgt_count[p] : g.max_nt;
+    const int ns = src_count[(size_t)p * stride], nt = tgt_count[(size_t)p * stride];
+    g.max_ns = ns > g.max_ns ? ns : g.max_ns;
+    g.max_nt = nt > g.max_nt ? nt : g.max_nt;
   }
   g.src_blocks = g.max_ns > 0 ? (g.max_ns + kIcpThreads - 1) / kIcpThreads : 1;
-  // target slices: as in nearest_slices, enough blocks for about four workgroups per CU, slices of whole 256-target groups
-  const long total = (long)pairs * g.src_blocks;
-  long want = (1024 + total - 1) / total;
-  const long max_slices = (g.max_nt + 255) / 256;
-  want = want < 1 ? 1 : (want > max_slices ? max_slices : want);
-  if (g.max_nt > 0) {
-    int slice = (int)((g.max_nt + want - 1) / want);
-    g.slice = ((slice + 255) / 256) * 256;
+  if (g.max_nt > 0) {  // target slices by nearest_slice (dpc_nearest.h), every pair with the batch's source blocks
+    g.slice = (int)nearest_slice((int64_t)pairs * g.src_blocks, g.max_nt);
     g.nslice = (g.max_nt + g.slice - 1) / g.slice;
   }
   return g;
@@ -62,25 +60,18 @@ struct IcpWork {
   int* done;        // [P]
 };
 
-size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 size_t icp_carve(const IcpGeom& g, int pairs, char* base, IcpWork* w) {
   const size_t pts = (size_t)pairs * g.max_ns;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align16(bytes);
-    return p;
-  };
+  Carver c{base};
   IcpWork t;
-  t.cur = reinterpret_cast<double*>(take(pts * 3 * sizeof(double)));
-  t.part_d2 = reinterpret_cast<double*>(take((size_t)g.nslice * pts * sizeof(double)));
-  t.part_idx = reinterpret_cast<int*>(take((size_t)g.nslice * pts * sizeof(int)));
-  t.mom = reinterpret_cast<double*>(take((size_t)pairs * g.src_blocks * kIcpMoments * sizeof(double)));
-  t.state = reinterpret_cast<double*>(take((size_t)pairs * kIcpState * sizeof(double)));
-  t.done = reinterpret_cast<int*>(take((size_t)pairs * sizeof(int)));
+  t.cur = c.take<double>(pts * 3);
+  t.part_d2 = c.take<double>((size_t)g.nslice * pts);
+  t.part_idx = c.take<int>((size_t)g.nslice * pts);
+  t.mom = c.take<double>((size_t)pairs * g.src_blocks * kIcpMoments);
+  t.state = c.take<double>((size_t)pairs * kIcpState);
+  t.done = c.take<int>(pairs);
   if (w) *w = t;
-  return off + 16;
+  return c.off + 16;
 }
 
 // x' = R x + t, each row summed left to right without FMA contraction (the numpy restatement in the tests does the same)
@@ -376,8 +367,7 @@ size_t dpc_icp_workspace_bytes(int pairs, const int32_t* src_count, const int32_
   if (pairs <= 0 || !src_count || !tgt_count) return 0;
   for (int p = 0; p < pairs; ++p)
     if (src_count[p] < 0 || tgt_count[p] < 0) return 0;
-  const IcpGeom g = icp_geometry(pairs, src_count, tgt_count);
-  return icp_carve(g, pairs, nullptr, nullptr);
+  return icp_carve(icp_geometry(pairs, src_count, tgt_count, 1), pairs, nullptr, nullptr);
 }
 
 int dpc_icp_point_to_point(const double* src, int n_src, const double* tgt, int n_tgt, const int32_t* pair_desc,
@@ -388,21 +378,10 @@ int dpc_icp_point_to_point(const double* src, int n_src, const double* tgt, int 
     return DPC_ERR_SHAPE;
   if (pairs == 0) return DPC_OK;
   if (!host_pair_desc) return DPC_ERR_NULL;
-  int32_t* sc = new int32_t[pairs];
-  int32_t* tc = new int32_t[pairs];
-  int rc = DPC_OK;
-  for (int p = 0; p < pairs && rc == DPC_OK; ++p) {
-    const int64_t s0 = host_pair_desc[4 * p], ns = host_pair_desc[4 * p + 1];
-    const int64_t t0 = host_pair_desc[4 * p + 2], nt = host_pair_desc[4 * p + 3];
-    if (s0 < 0 || ns < 0 || t0 < 0 || nt < 0 || s0 + ns > n_src || t0 + nt > n_tgt || (nt == 0 && ns > 0))
-      rc = DPC_ERR_SHAPE;
-    sc[p] = (int32_t)ns;
-    tc[p] = (int32_t)nt;
-  }
-  const IcpGeom g = icp_geometry(pairs, sc, tc);
-  delete[] sc;
-  delete[] tc;
+  const int rc = check_desc<4>(host_pair_desc, pairs, {(int64_t)n_src, (int64_t)n_tgt}, INT64_MAX, nullptr,
+                               [](const int32_t* d) { return !(d[3] == 0 && d[1] > 0); });  // argmin over an empty set
   if (rc != DPC_OK) return rc;
+  const IcpGeom g = icp_geometry(pairs, host_pair_desc + 1, host_pair_desc + 3, 4);
   if (!pair_desc || !init || !transform || !fitness || !inlier_rmse || !iterations || !workspace) return DPC_ERR_NULL;
   if ((g.max_ns > 0 && !src) || (g.max_nt > 0 && !tgt)) return DPC_ERR_NULL;
   IcpWork w;

@@ -1,5 +1,6 @@
 // The nearest-target scan shared by k_nearest_partial (dpc_nearest.hip) and k_chamfer_partial (dpc_chamfer.hip), so the
-// two cannot drift: both are pinned bit for bit against the reference's point_cloud_distance (F11, F16).
+// two cannot drift: both are pinned bit for bit against the reference's point_cloud_distance (F11, F16).  Also the rule
+// that slices the targets of a search, shared by those two and dpc_icp.hip (nearest_slice).
 //
 // One lane owns one source point (sx, sy, sz); targets vt[j0, j1) stream through the LDS tiles tx / ty / tz, whole block
 // cooperating (every thread of the block must call this with the same j0, j1).  Arithmetic follows the reference op for
@@ -11,7 +12,23 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <limits>
+
+// Targets per slice when the targets of a search are split over workgroups (dpc_point_cloud_distance,
+// dpc_nearest_batched, dpc_icp_point_to_point): enough slices that (source blocks x slices) comes close to a multiple of
+// four workgroups per CU, slices of whole 256-target groups (every resident block then carries the same load: 800 blocks
+// on 256 CUs ran 22 % slower than 992).  src_blocks: the blocks of 256 sources; the callers count them in int, which
+// wraps to <= 0 for a source count within 255 of 2^31, and such a count asks for a single slice (never a division by
+// it).  max_nt >= 1: the targets in the largest set.  The slice exceeds int32 only for max_nt within 255 of 2^31; the
+// callers narrow it to the kernels' int.
+inline int64_t nearest_slice(int64_t src_blocks, int64_t max_nt) {
+  int64_t want = src_blocks > 0 ? (1024 + src_blocks - 1) / src_blocks : 1;
+  const int64_t max_slices = (max_nt + 255) / 256;
+  if (want > max_slices) want = max_slices;
+  const int64_t slice = (max_nt + want - 1) / want;
+  return ((slice + 255) / 256) * 256;
+}
 
 template <class T, int kThreads, int kTile>
 __device__ __forceinline__ void nearest_scan(const T* __restrict__ vt, int j0, int j1, T sx, T sy, T sz, T* tx, T* ty, T* tz,

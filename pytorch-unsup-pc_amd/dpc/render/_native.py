@@ -29,19 +29,6 @@ DPC_STATUS_KEY_OVERFLOW = 4
 DPC_STATUS_NONFINITE = 8
 DPC_STATUS_DENSIFY_ORDER = 16
 
-# every symbol include/dpc_render.h declares (tests/test_abi.py checks the header against this list)
-SYMBOLS = (
-    "dpc_abi_version", "dpc_strerror", "dpc_mask_words_per_plane", "dpc_cells_bytes", "dpc_workspace_bytes", "dpc_check_grid", "dpc_locate",
-    "dpc_project_fwd", "dpc_project_bwd", "dpc_project_loss_fwd", "dpc_project_loss_bwd", "dpc_transform_fwd", "dpc_transform_bwd",
-    "dpc_splat_fwd", "dpc_splat_bwd", "dpc_smooth", "dpc_drc_fwd", "dpc_drc_bwd",
-    "dpc_silhouette_loss", "dpc_point_dropout_indices", "dpc_point_dropout_indices_live", "dpc_schedule_update", "dpc_taps_bucket",
-    "dpc_project_loss_step",
-    "dpc_nearest_workspace_bytes", "dpc_point_cloud_distance", "dpc_icp_workspace_bytes", "dpc_icp_point_to_point",
-    "dpc_chamfer_workspace_bytes", "dpc_nearest_batched", "dpc_downsample_workspace_bytes", "dpc_voxel_downsample",
-    "dpc_densify_workspace_bytes", "dpc_densify",
-    "dpc_profile_enable", "dpc_profile_disable", "dpc_profile_count", "dpc_profile_get", "dpc_profile_get_id", "dpc_profile_pair_overhead",
-)
-
 
 class DpcParams(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("N", ctypes.c_int32), ("D", ctypes.c_int32), ("H", ctypes.c_int32),
@@ -50,6 +37,56 @@ class DpcParams(ctypes.Structure):
                 ("clip_val", ctypes.c_float), ("max_depth", ctypes.c_float), ("point_replicas", ctypes.c_int32),
                 ("N_src", ctypes.c_int32), ("point_index", ctypes.c_void_p), ("status", ctypes.c_void_p),
                 ("n_live", ctypes.c_void_p), ("dev_taps_xy", ctypes.c_void_p), ("dev_taps_z", ctypes.c_void_p)]
+
+
+# (name, restype, argtypes) of every symbol include/dpc_render.h declares (tests/test_abi_and_host.py checks the header
+# against SYMBOLS); argtypes None: the function takes no argument
+_i, _i64, _d, _sz = ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_size_t
+_vp, _pp = ctypes.c_void_p, ctypes.POINTER(DpcParams)
+_FUNCTIONS = (
+    ("dpc_abi_version", _i, None),
+    ("dpc_strerror", ctypes.c_char_p, [_i]),
+    ("dpc_mask_words_per_plane", _sz, [_pp]),
+    ("dpc_cells_bytes", _sz, [_pp]),
+    ("dpc_workspace_bytes", _sz, [_pp]),
+    ("dpc_check_grid", _i, [_pp, _i]),
+    ("dpc_locate", _i, [_pp] + [_vp] * 7),
+    ("dpc_project_fwd", _i, [_pp] + [_vp] * 16),
+    ("dpc_project_bwd", _i, [_pp] + [_vp] * 17),
+    # ABI 15: (gt, gt_factor, weights) in every fused-loss call
+    ("dpc_project_loss_fwd", _i, [_pp] + [_vp] * 8 + [_i, _vp, _i] + [_vp] * 12 + [ctypes.POINTER(_i), _vp]),
+    ("dpc_project_loss_bwd", _i, [_pp] + [_vp] * 13 + [_i, _vp, _i] + [_vp] * 2 + [_i] + [_vp] * 4),
+    ("dpc_transform_fwd", _i, [_pp] + [_vp] * 6),
+    ("dpc_transform_bwd", _i, [_pp] + [_vp] * 8),
+    ("dpc_splat_fwd", _i, [_pp, _vp, _i, _vp, _vp, _vp]),
+    ("dpc_splat_bwd", _i, [_pp, _vp, _i, _vp, _vp, _vp]),
+    ("dpc_smooth", _i, [_pp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("dpc_drc_fwd", _i, [_pp] + [_vp] * 5),
+    ("dpc_drc_bwd", _i, [_pp] + [_vp] * 6),
+    ("dpc_silhouette_loss", _i, [_vp, _i, _vp, _vp] + [_i] * 4 + [_vp, _vp, _vp, _vp]),
+    ("dpc_point_dropout_indices", _i, [_i, _i, _i, _vp, _vp, _vp]),
+    ("dpc_point_dropout_indices_live", _i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    ("dpc_schedule_update", _i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    ("dpc_taps_bucket", _i, [_vp, _i]),
+    ("dpc_project_loss_step", _i, [_pp] + [_vp] * 8 + [_i, _vp, _i] + [_vp] * 15),
+    ("dpc_nearest_workspace_bytes", _sz, [_i, _i, _i]),
+    ("dpc_point_cloud_distance", _i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("dpc_icp_workspace_bytes", _sz, [_i, _vp, _vp]),
+    ("dpc_icp_point_to_point", _i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _d, _i, _d, _d] + [_vp] * 6),
+    ("dpc_chamfer_workspace_bytes", _sz, [_i, _vp, _i]),
+    ("dpc_nearest_batched", _i, [_vp, _i, _i, _vp, _vp, _i] + [_vp] * 5),
+    ("dpc_downsample_workspace_bytes", _sz, [_i, _i]),
+    ("dpc_voxel_downsample", _i, [_vp, _i, _i, _vp, _vp, _i, _d] + [_vp] * 6),
+    ("dpc_densify_workspace_bytes", _sz, [_i, _i64, _i64, _i64, _i]),
+    ("dpc_densify", _i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp] + [_i] * 4 + [_vp] * 5),
+    ("dpc_profile_enable", _i, [_i]),
+    ("dpc_profile_disable", _i, None),
+    ("dpc_profile_count", _i, None),
+    ("dpc_profile_get", _i, [_i, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float)]),
+    ("dpc_profile_get_id", _i, [_i, ctypes.c_char_p, _i]),
+    ("dpc_profile_pair_overhead", _i, [_vp, _i, ctypes.POINTER(ctypes.c_float)]),
+)
+SYMBOLS = tuple(name for name, _, _ in _FUNCTIONS)
 
 
 class DpcError(RuntimeError):
@@ -71,78 +108,11 @@ def lib():
                 "(needs /opt/rocm/bin/hipcc) or `python -c 'import __graft_entry__ as g; g.build()'`. "
                 "There is no CPU fallback." % (LIB_PATH, _CSRC))
         L = ctypes.CDLL(LIB_PATH)
-        vp, pp = ctypes.c_void_p, ctypes.POINTER(DpcParams)
-        L.dpc_abi_version.restype = ctypes.c_int
-        L.dpc_strerror.restype = ctypes.c_char_p
-        L.dpc_strerror.argtypes = [ctypes.c_int]
-        L.dpc_mask_words_per_plane.restype = ctypes.c_size_t
-        L.dpc_mask_words_per_plane.argtypes = [pp]
-        L.dpc_cells_bytes.restype = ctypes.c_size_t
-        L.dpc_cells_bytes.argtypes = [pp]
-        L.dpc_workspace_bytes.restype = ctypes.c_size_t
-        L.dpc_workspace_bytes.argtypes = [pp]
-        L.dpc_check_grid.restype = ctypes.c_int
-        L.dpc_check_grid.argtypes = [pp, ctypes.c_int]
-        for name, nptr in (("dpc_project_fwd", 16), ("dpc_project_bwd", 17), ("dpc_transform_fwd", 6),
-                           ("dpc_transform_bwd", 8), ("dpc_drc_fwd", 5), ("dpc_drc_bwd", 6), ("dpc_locate", 7)):
+        for name, restype, argtypes in _FUNCTIONS:
             fn = getattr(L, name)
-            fn.restype = ctypes.c_int
-            fn.argtypes = [pp] + [vp] * nptr
-        L.dpc_project_loss_fwd.restype = ctypes.c_int
-        # ABI 15: (gt, gt_factor, weights) in every fused-loss call
-        L.dpc_project_loss_fwd.argtypes = [pp] + [vp] * 8 + [ctypes.c_int, vp, ctypes.c_int] + [vp] * 12 + [ctypes.POINTER(ctypes.c_int), vp]
-        L.dpc_project_loss_bwd.restype = ctypes.c_int
-        L.dpc_project_loss_bwd.argtypes = [pp] + [vp] * 13 + [ctypes.c_int, vp, ctypes.c_int] + [vp] * 2 + [ctypes.c_int] + [vp] * 4
-        L.dpc_splat_fwd.restype = ctypes.c_int
-        L.dpc_splat_fwd.argtypes = [pp, vp, ctypes.c_int, vp, vp, vp]
-        L.dpc_splat_bwd.restype = ctypes.c_int
-        L.dpc_splat_bwd.argtypes = [pp, vp, ctypes.c_int, vp, vp, vp]
-        L.dpc_profile_enable.restype = ctypes.c_int
-        L.dpc_profile_enable.argtypes = [ctypes.c_int]
-        L.dpc_profile_disable.restype = ctypes.c_int
-        L.dpc_profile_count.restype = ctypes.c_int
-        L.dpc_profile_get.restype = ctypes.c_int
-        L.dpc_profile_get.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_float)]
-        L.dpc_profile_get_id.restype = ctypes.c_int
-        L.dpc_profile_get_id.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
-        L.dpc_profile_pair_overhead.restype = ctypes.c_int
-        L.dpc_profile_pair_overhead.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
-        L.dpc_silhouette_loss.restype = ctypes.c_int
-        L.dpc_silhouette_loss.argtypes = [vp, ctypes.c_int, vp, vp] + [ctypes.c_int] * 4 + [vp, vp, vp, vp]
-        L.dpc_nearest_workspace_bytes.restype = ctypes.c_size_t
-        L.dpc_nearest_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        L.dpc_point_cloud_distance.restype = ctypes.c_int
-        L.dpc_point_cloud_distance.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]
-        L.dpc_icp_workspace_bytes.restype = ctypes.c_size_t
-        L.dpc_icp_workspace_bytes.argtypes = [ctypes.c_int, vp, vp]
-        L.dpc_icp_point_to_point.restype = ctypes.c_int
-        L.dpc_icp_point_to_point.argtypes = ([vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_double,
-                                              ctypes.c_int, ctypes.c_double, ctypes.c_double] + [vp] * 6)
-        L.dpc_chamfer_workspace_bytes.restype = ctypes.c_size_t
-        L.dpc_chamfer_workspace_bytes.argtypes = [ctypes.c_int, vp, ctypes.c_int]
-        L.dpc_nearest_batched.restype = ctypes.c_int
-        L.dpc_nearest_batched.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int] + [vp] * 5
-        L.dpc_downsample_workspace_bytes.restype = ctypes.c_size_t
-        L.dpc_downsample_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.dpc_voxel_downsample.restype = ctypes.c_int
-        L.dpc_voxel_downsample.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_double] + [vp] * 6
-        L.dpc_densify_workspace_bytes.restype = ctypes.c_size_t
-        L.dpc_densify_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
-        L.dpc_densify.restype = ctypes.c_int
-        L.dpc_densify.argtypes = ([vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp] + [ctypes.c_int] * 4
-                                  + [vp] * 5)
-        L.dpc_smooth.restype = ctypes.c_int
-        L.dpc_smooth.argtypes = [pp, vp, vp, ctypes.c_int, vp, vp, vp, vp]
-        L.dpc_point_dropout_indices.restype = ctypes.c_int
-        L.dpc_point_dropout_indices.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]
-        L.dpc_point_dropout_indices_live.restype = ctypes.c_int
-        L.dpc_point_dropout_indices_live.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
-        L.dpc_schedule_update.restype = ctypes.c_int
-        L.dpc_schedule_update.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
-        L.dpc_taps_bucket.restype = ctypes.c_int
-        L.dpc_taps_bucket.argtypes = [vp, ctypes.c_int]
-        L.dpc_project_loss_step.restype = ctypes.c_int
-        L.dpc_project_loss_step.argtypes = [pp] + [vp] * 8 + [ctypes.c_int, vp, ctypes.c_int] + [vp] * 15
+            fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
         if L.dpc_abi_version() != ABI_VERSION:
             raise RuntimeError("dpc.render: libdpc_render.so ABI %d, expected %d -- rebuild it (make -C %s)"
                                % (L.dpc_abi_version(), ABI_VERSION, _CSRC))

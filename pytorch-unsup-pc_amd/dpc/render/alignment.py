@@ -16,7 +16,7 @@ import math
 import numpy as np
 import torch
 
-from . import _native
+from . import _batch, _native
 
 ICP_THRESHOLD = 0.2  # compute_alignment.py:37
 
@@ -24,21 +24,13 @@ ICP_THRESHOLD = 0.2  # compute_alignment.py:37
 # ------------------------------------------------------------------------------------------------------
 # batched ICP                                             reference: compute_alignment.py:28-42 (open3d_icp)
 # ------------------------------------------------------------------------------------------------------
+# Host numpy rather than _batch.cloud's tensors: ICP packs its clouds on the host, and the round trip through torch
+# cost a 250-pair call about 1.5 ms.
 def _as_f64_cloud(x, what, i):
     a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
     if a.ndim != 2 or a.shape[1] != 3:
         raise ValueError("%s[%d] must be [n,3], got %s" % (what, i, tuple(a.shape)))
     return np.ascontiguousarray(a, dtype=np.float64)   # float32 -> float64 is exact, like open3d's Vector3dVector
-
-
-def _device_of(*groups):
-    for g in groups:
-        for x in g:
-            if isinstance(x, torch.Tensor) and x.is_cuda:
-                return x.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("dpc.render.icp_point_to_point runs on MI355X only: no HIP device (there is no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def icp_point_to_point(sources, targets, max_correspondence_distance, init=None, max_iteration=30, relative_fitness=1e-6,
@@ -73,23 +65,22 @@ def icp_point_to_point(sources, targets, max_correspondence_distance, init=None,
 
     src_start = np.cumsum([0] + [len(s) for s in srcs])
     tgt_start = np.cumsum([0] + [len(t) for t in tgts])
-    desc = np.zeros((max(P, 1), 4), dtype=np.int32)
-    for i, k in enumerate(target_of):
-        desc[i] = (src_start[i], len(srcs[i]), tgt_start[k], len(tgts[k]))
     L = _native.lib()
     n_src, n_tgt = int(src_start[-1]), int(tgt_start[-1])
-    if n_src > np.iinfo(np.int32).max or n_tgt > np.iinfo(np.int32).max:
+    if n_src > _batch.INT32_MAX or n_tgt > _batch.INT32_MAX:
         raise ValueError("icp_point_to_point: more than 2^31 - 1 points")
-    host_desc = np.ascontiguousarray(desc)
-    # the same checks the library makes (DPC_ERR_SHAPE, before any launch), asked of it without touching the device
-    rc = L.dpc_icp_point_to_point(None, n_src, None, n_tgt, None, host_desc.ctypes.data_as(ctypes.c_void_p), P, None,
-                                  float(max_correspondence_distance), int(max_iteration), float(relative_fitness),
-                                  float(relative_rmse), None, None, None, None, None, None)
-    if rc == _native.DPC_ERR_SHAPE:
-        raise ValueError("icp_point_to_point: invalid arguments (max_correspondence_distance %r, max_iteration %r, "
-                         "an empty target for a non-empty source, or a range outside the clouds)"
-                         % (max_correspondence_distance, max_iteration))
-    dev = _device_of(sources, targets, [init] if isinstance(init, torch.Tensor) else [])
+    desc = _batch.table([(src_start[i], len(srcs[i]), tgt_start[k], len(tgts[k])) for i, k in enumerate(target_of)], 4,
+                        "icp_point_to_point: more than 2^31 - 1 points")
+    host_desc = desc.ctypes.data_as(ctypes.c_void_p)
+    _batch.dry_run(L.dpc_icp_point_to_point(None, n_src, None, n_tgt, None, host_desc, P, None,
+                                            float(max_correspondence_distance), int(max_iteration),
+                                            float(relative_fitness), float(relative_rmse), None, None, None, None, None,
+                                            None),
+                   "icp_point_to_point: invalid arguments (max_correspondence_distance %r, max_iteration %r, an empty "
+                   "target for a non-empty source, or a range outside the clouds)"
+                   % (max_correspondence_distance, max_iteration))
+    dev = _batch.device("dpc.render.icp_point_to_point", sources, targets,
+                        [init] if isinstance(init, torch.Tensor) else [])
     out_t = torch.empty((P, 4, 4), dtype=torch.float64, device=dev)
     out_f = torch.empty((P,), dtype=torch.float64, device=dev)
     out_r = torch.empty((P,), dtype=torch.float64, device=dev)
@@ -100,12 +91,12 @@ def icp_point_to_point(sources, targets, max_correspondence_distance, init=None,
     tgt = torch.from_numpy(np.concatenate(tgts) if n_tgt else np.zeros((1, 3))).to(dev)
     desc_d = torch.from_numpy(desc).to(dev)
     init_d = torch.from_numpy(init_np).to(dev)
-    counts = np.ascontiguousarray(desc[:P, 1]), np.ascontiguousarray(desc[:P, 3])
-    ws_bytes = L.dpc_icp_workspace_bytes(P, counts[0].ctypes.data_as(ctypes.c_void_p), counts[1].ctypes.data_as(ctypes.c_void_p))
-    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+    counts = np.ascontiguousarray(desc[:, 1]), np.ascontiguousarray(desc[:, 3])
+    ws = _batch.workspace(L.dpc_icp_workspace_bytes(P, counts[0].ctypes.data_as(ctypes.c_void_p),
+                                                    counts[1].ctypes.data_as(ctypes.c_void_p)), dev)
     with torch.cuda.device(dev):
-        rc = L.dpc_icp_point_to_point(_native.ptr(src), n_src, _native.ptr(tgt), n_tgt, _native.ptr(desc_d),
-                                      host_desc.ctypes.data_as(ctypes.c_void_p), P, _native.ptr(init_d),
+        rc = L.dpc_icp_point_to_point(_native.ptr(src), n_src, _native.ptr(tgt), n_tgt, _native.ptr(desc_d), host_desc, P,
+                                      _native.ptr(init_d),
                                       float(max_correspondence_distance), int(max_iteration), float(relative_fitness),
                                       float(relative_rmse), _native.ptr(out_t), _native.ptr(out_f), _native.ptr(out_r),
                                       _native.ptr(out_i), _native.ptr(ws), _native.stream_ptr(dev))

@@ -18,18 +18,10 @@ import os
 import numpy as np
 import torch
 
-from . import _native
+from . import _batch, _native
 from .predictions import load_predictions
 
-
-def _device(*groups):
-    for g in groups:
-        for x in g:
-            if isinstance(x, torch.Tensor) and x.is_cuda:
-                return x.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("dpc.render Chamfer evaluation runs on MI355X only: no HIP device (there is no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device())
+_WHAT = "dpc.render Chamfer evaluation"
 
 
 def _pair_table(pairs):
@@ -37,9 +29,7 @@ def _pair_table(pairs):
     if desc.ndim != 2 or desc.shape[1] != 4:
         raise ValueError("nearest_batched: pairs must be [P,4] (src_start, src_count, tgt_start, tgt_count), got %s"
                          % (tuple(desc.shape),))
-    if desc.size and (desc.min() < np.iinfo(np.int32).min or desc.max() > np.iinfo(np.int32).max):
-        raise ValueError("nearest_batched: pair table entries must fit int32")
-    return np.ascontiguousarray(desc, dtype=np.int32)
+    return _batch.table(desc, 4, "nearest_batched: pair table entries must fit int32")
 
 
 def nearest_batched(points, pairs, return_distances=False):
@@ -54,21 +44,17 @@ def nearest_batched(points, pairs, return_distances=False):
     desc = _pair_table(pairs)
     P = desc.shape[0]
     L = _native.lib()
-    pts = points if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points))
-    if pts.dim() != 2 or pts.shape[1] != 3:
-        raise ValueError("nearest_batched: points must be [n,3], got %s" % (tuple(pts.shape),))
+    pts = _batch.cloud(points, "nearest_batched: points")
     n_pts = int(pts.shape[0])
-    if n_pts > np.iinfo(np.int32).max:
+    if n_pts > _batch.INT32_MAX:
         raise ValueError("nearest_batched: more than 2^31 - 1 points")
     host_desc = desc.ctypes.data_as(ctypes.c_void_p)
-    # the library's own checks (DPC_ERR_SHAPE, before any launch), asked of it without touching the device
-    rc = L.dpc_nearest_batched(None, n_pts, 0, None, host_desc, P, None, None, None, None, None)
-    if rc == _native.DPC_ERR_SHAPE:
-        raise ValueError("nearest_batched: invalid pair table (a negative start or count, a range outside the %d points, "
-                         "an empty target for a non-empty source, or more than 2^31 - 1 output points)" % n_pts)
-    dev = _device([pts])
+    _batch.dry_run(L.dpc_nearest_batched(None, n_pts, 0, None, host_desc, P, None, None, None, None, None),
+                   "nearest_batched: invalid pair table (a negative start or count, a range outside the %d points, "
+                   "an empty target for a non-empty source, or more than 2^31 - 1 output points)" % n_pts)
+    dev = _batch.device(_WHAT, [pts])
     dtype = torch.float64 if pts.dtype == torch.float64 else torch.float32
-    pts = pts.detach().to(device=dev, dtype=dtype).contiguous()
+    pts = pts.to(device=dev, dtype=dtype).contiguous()
     is64 = int(dtype == torch.float64)
     total = int(desc[:, 1].astype(np.int64).sum()) if P else 0
     mean = torch.empty((P,), dtype=torch.float64, device=dev)
@@ -76,21 +62,12 @@ def nearest_batched(points, pairs, return_distances=False):
     idx = torch.empty((total,), dtype=torch.int64, device=dev) if return_distances else None
     if P:
         desc_d = torch.from_numpy(desc).to(dev)
-        ws = torch.empty((max(L.dpc_chamfer_workspace_bytes(P, host_desc, is64), 16),), dtype=torch.uint8, device=dev)
+        ws = _batch.workspace(L.dpc_chamfer_workspace_bytes(P, host_desc, is64), dev)
         with torch.cuda.device(dev):
             rc = L.dpc_nearest_batched(_native.ptr(pts), n_pts, is64, _native.ptr(desc_d), host_desc, P, _native.ptr(mean),
                                        _native.ptr(dist), _native.ptr(idx), _native.ptr(ws), _native.stream_ptr(dev))
         _native.check(rc, "dpc_nearest_batched")
     return (mean, dist, idx) if return_distances else mean
-
-
-def _cloud(x, what, i):
-    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError("%s[%d] must be [n,3], got %s" % (what, i, tuple(t.shape)))
-    if t.dtype not in (torch.float32, torch.float64):
-        t = t.float()
-    return t.detach()
 
 
 def chamfer_batched(preds, gts, gt_of=None):
@@ -102,8 +79,8 @@ def chamfer_batched(preds, gts, gt_of=None):
     (point_cloud_distance's rule, per pair): all 2P directed pairs go into one native call, or two when fp32-only and
     fp64 pairs are mixed.  NaN or inf coordinates raise ValueError naming the first bad input (one device reduction),
     standing in for the reference's assert on NaN distances; an empty GT for a non-empty prediction raises too."""
-    P_list = [_cloud(p, "preds", i) for i, p in enumerate(preds)]
-    G_list = [_cloud(g, "gts", i) for i, g in enumerate(gts)]
+    P_list = [_batch.cloud(p, "preds[%d]" % i) for i, p in enumerate(preds)]
+    G_list = [_batch.cloud(g, "gts[%d]" % i) for i, g in enumerate(gts)]
     P = len(P_list)
     if gt_of is None:
         if len(G_list) != P:
@@ -116,7 +93,7 @@ def chamfer_batched(preds, gts, gt_of=None):
     for i, k in enumerate(gt_of):
         if len(G_list[k]) == 0 and len(P_list[i]) > 0:
             raise ValueError("chamfer_batched: GT cloud %d is empty but prediction %d is not (argmin of an empty set)" % (k, i))
-    dev = _device(P_list, G_list)
+    dev = _batch.device(_WHAT, P_list, G_list)
     out = torch.empty((P, 2), dtype=torch.float64, device=dev)
     if P == 0:
         return out
@@ -134,15 +111,11 @@ def _chamfer_group(preds, gts, gt_of, dev, dtype):
     used = sorted(set(gt_of))
     clouds = [gts[k] for k in used] + list(preds)
     names = ["gts[%d]" % k for k in used] + ["preds[%d]" % i for i in range(len(preds))]
-    on_dev = any(c.is_cuda for c in clouds)
-    parts = [c.to(device=dev, dtype=dtype) for c in clouds] if on_dev else [c.to(dtype) for c in clouds]
-    packed = torch.cat(parts) if parts else torch.zeros((0, 3), dtype=dtype)
-    packed = packed.to(dev).contiguous()
+    packed, start = _batch.pack(clouds, dev, dtype)
     if packed.numel() and not bool(torch.isfinite(packed).all()):
         for name, c in zip(names, clouds):
             if not bool(torch.isfinite(c).all()):
                 raise ValueError("chamfer_batched: %s holds a NaN or inf coordinate" % name)
-    start = np.cumsum([0] + [len(c) for c in clouds])
     slot = {k: j for j, k in enumerate(used)}
     desc = np.zeros((2 * len(preds), 4), dtype=np.int64)
     for i, k in enumerate(gt_of):
@@ -150,7 +123,7 @@ def _chamfer_group(preds, gts, gt_of, dev, dtype):
         gs, gn = start[slot[k]], len(gts[k])
         desc[2 * i] = (ps, pn, gs, gn)
         desc[2 * i + 1] = (gs, gn, ps, pn)
-    if start[-1] > np.iinfo(np.int32).max:
+    if start[-1] > _batch.INT32_MAX:
         raise ValueError("chamfer_batched: more than 2^31 - 1 points in one call")
     return nearest_batched(packed, desc).view(len(preds), 2)
 
@@ -204,7 +177,7 @@ def chamfer_of_split(predictions, gt_clouds, reference_rotation=None, models_per
     if int(models_per_call) < 1:
         raise ValueError("chamfer_of_split: models_per_call must be >= 1")
     preds = [_prediction(e, m) for m, e in enumerate(predictions)]
-    gts = [_cloud(g, "gt_clouds", m) for m, g in enumerate(gt_clouds)]
+    gts = [_batch.cloud(g, "gt_clouds[%d]" % m) for m, g in enumerate(gt_clouds)]
     views = {p.shape[0] for p, _ in preds}
     if len(views) > 1:
         raise ValueError("chamfer_of_split: every model needs the same number of views, got %s" % sorted(views))
@@ -217,7 +190,7 @@ def chamfer_of_split(predictions, gt_clouds, reference_rotation=None, models_per
     out = np.zeros((M, V, 2), dtype=np.float64)
     if M == 0 or V == 0:
         return out
-    dev = _device([p for p, _ in preds], gts)
+    dev = _batch.device(_WHAT, [p for p, _ in preds], gts)
     step = int(models_per_call)
     for a in range(0, M, step):
         group = range(a, min(M, a + step))

@@ -18,7 +18,7 @@ import numbers
 import numpy as np
 import torch
 
-from . import _native
+from . import _batch, _native
 
 ROUNDS_PER_SYNC = 8  # rounds enqueued between two reads of the "models left" counter
 
@@ -129,35 +129,31 @@ def _mesh(mesh, i):
     return V, E.astype(np.int32), F.astype(np.int32), fe, most
 
 
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("dpc.render densification runs on MI355X only: no HIP device (there is no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _densify_packed(meshes, n, rounds_per_sync=ROUNDS_PER_SYNC):
     """One dpc_densify job.  Returns (out [sum(v_i + n), 3] float64 on the device, [v_i + n] rows per model, rounds)."""
     C = len(meshes)
-    desc = np.zeros((C, 7), dtype=np.int32)
+    desc_rows = []
     vo = eo = fo = 0
-    for m, (V, E, F, _, _) in enumerate(meshes):
-        desc[m] = (vo, len(V), eo, len(E), fo, len(F), n)
+    for V, E, F, _, _ in meshes:
+        desc_rows.append((vo, len(V), eo, len(E), fo, len(F), n))
         vo, eo, fo = vo + len(V), eo + len(E), fo + len(F)
+    desc = _batch.table(desc_rows, 7,
+                        "densify: more than 2^31 - 1 vertices, edges or faces, or num_points %d, in one job" % n)
     most = max(mm[4] for mm in meshes)
     L = _native.lib()
     host_desc = desc.ctypes.data_as(ctypes.c_void_p)
-    # the library's own checks (DPC_ERR_SHAPE, before any launch), asked of it without touching the device
-    rc = L.dpc_densify(None, vo, None, eo, None, None, fo, None, host_desc, C, most, 1, 0, None, None, None, None, None)
-    if rc == _native.DPC_ERR_SHAPE:
-        raise MeshError("densify: refused by dpc_densify (%d models, num_points %d: an id would pass 2^31 - 1)" % (C, n))
-    dev = _device()
+    _batch.dry_run(L.dpc_densify(None, vo, None, eo, None, None, fo, None, host_desc, C, most, 1, 0, None, None, None,
+                                 None, None),
+                   "densify: refused by dpc_densify (%d models, num_points %d: an id would pass 2^31 - 1)" % (C, n),
+                   MeshError)
+    dev = _batch.device("dpc.render densification")
     cat = lambda k, dt, w: torch.from_numpy(np.concatenate([mm[k] for mm in meshes]).astype(dt).reshape(-1, w)).to(dev)
     verts, edges, faces, face_edges = cat(0, np.float64, 3), cat(1, np.int32, 2), cat(2, np.int32, 3), cat(3, np.int32, 3)
     rows = [len(mm[0]) + n for mm in meshes]
     out = torch.empty((max(sum(rows), 1), 3), dtype=torch.float64, device=dev)
     info = torch.zeros((2,), dtype=torch.int32, device=dev)  # status, models with splits left
     desc_d = torch.from_numpy(desc).to(dev)
-    ws = torch.empty((max(L.dpc_densify_workspace_bytes(C, eo, fo, C * n, most), 16),), dtype=torch.uint8, device=dev)
+    ws = _batch.workspace(L.dpc_densify_workspace_bytes(C, eo, fo, C * n, most), dev)
     rounds, begin = 0, 1
     with torch.cuda.device(dev):
         while True:
@@ -172,13 +168,11 @@ def _densify_packed(meshes, n, rounds_per_sync=ROUNDS_PER_SYNC):
                 break
             if rounds > n + rounds_per_sync:  # every round splits at least one edge of every model with splits left
                 raise RuntimeError("dpc_densify: %d rounds and %d models still unfinished" % (rounds, left))
-    if status & _native.DPC_STATUS_NONFINITE:
-        raise MeshError("densify: a vertex, edge length or midpoint is not finite")
-    if status & _native.DPC_STATUS_BAD_INDEX:
-        raise MeshError("densify: dpc_densify found an inconsistent mesh")
-    if status & _native.DPC_STATUS_DENSIFY_ORDER:
-        raise MeshError("densify: a new edge was longer than 0.87 x its round's longest edge; the round order does "
-                           "not hold for this mesh and the output would not be the reference's")
+    _batch.raise_status(status, [
+        (_native.DPC_STATUS_NONFINITE, "densify: a vertex, edge length or midpoint is not finite"),
+        (_native.DPC_STATUS_BAD_INDEX, "densify: dpc_densify found an inconsistent mesh"),
+        (_native.DPC_STATUS_DENSIFY_ORDER, "densify: a new edge was longer than 0.87 x its round's longest edge; the round "
+         "order does not hold for this mesh and the output would not be the reference's")], MeshError)
     return out, rows, rounds
 
 

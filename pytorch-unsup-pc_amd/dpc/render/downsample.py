@@ -17,7 +17,7 @@ import numbers
 import numpy as np
 import torch
 
-from . import _native
+from . import _batch, _native
 
 
 def _voxel_size(voxel_size):
@@ -31,21 +31,7 @@ def _voxel_size(voxel_size):
 
 
 def _cloud(x, i):
-    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError("voxel_down_sample: cloud %d must be [n,3], got %s" % (i, tuple(t.shape)))
-    if t.dtype not in (torch.float32, torch.float64):
-        raise ValueError("voxel_down_sample: cloud %d must be float32 or float64, got %s" % (i, t.dtype))
-    return t.detach()
-
-
-def _device(clouds):
-    for c in clouds:
-        if c.is_cuda:
-            return c.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("dpc.render voxel downsampling runs on MI355X only: no HIP device (there is no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device())
+    return _batch.cloud(x, "voxel_down_sample: cloud %d" % i, cast=None)
 
 
 def _downsample_packed(clouds, vs):
@@ -54,44 +40,34 @@ def _downsample_packed(clouds, vs):
     C = len(clouds)
     counts = np.array([len(c) for c in clouds], dtype=np.int64)
     M = int(counts.sum())
-    desc = np.zeros((C, 2), dtype=np.int32)
-    if M > np.iinfo(np.int32).max - 1:
+    if M > _batch.INT32_MAX - 1:
         raise ValueError("voxel_down_sample: more than 2^31 - 2 points in one call")
-    desc[:, 0] = np.cumsum(counts) - counts
-    desc[:, 1] = counts
+    desc = _batch.table(np.stack([np.cumsum(counts) - counts, counts], axis=1), 2,
+                        "voxel_down_sample: more than 2^31 - 2 points in one call")
     L = _native.lib()
     host_desc = desc.ctypes.data_as(ctypes.c_void_p)
-    # the library's own checks (DPC_ERR_SHAPE, before any launch), asked of it without touching the device
-    rc = L.dpc_voxel_downsample(None, M, 0, None, host_desc, C, vs, None, None, None, None, None, None)
-    if rc == _native.DPC_ERR_SHAPE:
-        raise ValueError("voxel_down_sample: refused by dpc_voxel_downsample (voxel_size %r, %d points)" % (vs, M))
-    dev = _device(clouds)
+    _batch.dry_run(L.dpc_voxel_downsample(None, M, 0, None, host_desc, C, vs, None, None, None, None, None, None),
+                   "voxel_down_sample: refused by dpc_voxel_downsample (voxel_size %r, %d points)" % (vs, M))
+    dev = _batch.device("dpc.render voxel downsampling", clouds)
     dtype = torch.float64 if any(c.dtype == torch.float64 for c in clouds) else torch.float32  # widening is exact
-    if any(c.is_cuda for c in clouds):
-        pts = torch.cat([c.to(device=dev, dtype=dtype) for c in clouds])
-    else:  # one host -> device copy
-        pts = torch.from_numpy(np.concatenate([c.numpy() for c in clouds])).to(dev)
-    pts = pts.contiguous()
+    pts, _ = _batch.pack(clouds, dev, dtype)
     out = torch.empty((max(M, 1), 3), dtype=torch.float64, device=dev)
     info = torch.zeros((1 + 2 * C,), dtype=torch.int32, device=dev)  # status, out_count [C], out_offset [C]
     desc_d = torch.from_numpy(desc).to(dev)
-    ws = torch.empty((max(L.dpc_downsample_workspace_bytes(C, M), 16),), dtype=torch.uint8, device=dev)
+    ws = _batch.workspace(L.dpc_downsample_workspace_bytes(C, M), dev)
     with torch.cuda.device(dev):
         rc = L.dpc_voxel_downsample(_native.ptr(pts), M, int(dtype == torch.float64), _native.ptr(desc_d), host_desc, C, vs,
                                     _native.ptr(out), _native.ptr(info[1:1 + C]), _native.ptr(info[1 + C:]),
                                     _native.ptr(info[:1]), _native.ptr(ws), _native.stream_ptr(dev))
     _native.check(rc, "dpc_voxel_downsample")
     info = info.cpu().numpy().astype(np.int64)  # the call's one synchronisation
-    status = int(info[0])
-    if status & _native.DPC_STATUS_NONFINITE:
-        bad = next(i for i, c in enumerate(clouds) if not bool(torch.isfinite(c).all()))
-        raise ValueError("voxel_down_sample: cloud %d holds a NaN or inf coordinate" % bad)
-    if status & _native.DPC_STATUS_VOXEL_TOO_SMALL:
-        raise ValueError("voxel_down_sample: voxel_size %r is too small for a cloud's extent (open3d: voxel_size * "
-                         "2147483647 < the padded bounding box's largest side)" % vs)
-    if status & _native.DPC_STATUS_KEY_OVERFLOW:
-        raise ValueError("voxel_down_sample: the batch's voxel keys need more than 64 bits at voxel_size %r (%d clouds); "
-                         "pass fewer clouds per call or a larger voxel" % (vs, C))
+    _batch.raise_status(int(info[0]), [
+        (_native.DPC_STATUS_NONFINITE, lambda: "voxel_down_sample: cloud %d holds a NaN or inf coordinate"
+         % next(i for i, c in enumerate(clouds) if not bool(torch.isfinite(c).all()))),
+        (_native.DPC_STATUS_VOXEL_TOO_SMALL, "voxel_down_sample: voxel_size %r is too small for a cloud's extent (open3d: "
+         "voxel_size * 2147483647 < the padded bounding box's largest side)" % vs),
+        (_native.DPC_STATUS_KEY_OVERFLOW, "voxel_down_sample: the batch's voxel keys need more than 64 bits at voxel_size "
+         "%r (%d clouds); pass fewer clouds per call or a larger voxel" % (vs, C))])
     counts, offsets = info[1:1 + C], info[1 + C:]
     V = int(counts.sum())
     return out[:V].clone(), counts, offsets

@@ -4,14 +4,14 @@ import re, subprocess, sys
 txt = open(sys.argv[1]).read()
 rows, cur = [], {}
 for line in txt.splitlines():
-    m = re.search(r"remark: (?:\S+ )?\s*(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs|LDS Size \[bytes/block\]): (.*?)(?: \[-Rpass|$)", line)
+    m = re.search(r"remark: (?:\S+ )?\s*(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|TotalSGPRs|LDS Size \[bytes/block\]): (.*?)(?: \[-Rpass|$)", line)
     if not m: continue
     k, v = m.group(1), m.group(2).strip()
     if k == "Function Name":
         if cur: rows.append(cur)
         cur = {"name": subprocess.run(["c++filt", v], capture_output=True, text=True).stdout.strip()}
     else:
-        cur[k.split(" ")[0]] = v
+        cur[k.split(" ")[0].replace("Total", "")] = v
 if cur: rows.append(cur)
 for r in rows:
     n = re.sub(r"\(anonymous namespace\)::", "", r["name"]); n = re.sub(r"\(.*", "", n).replace("void ", "")
