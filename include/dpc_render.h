@@ -61,7 +61,9 @@ enum {
   DPC_STATUS_VOXEL_TOO_SMALL = 2, /* dpc_voxel_downsample: open3d's "voxel_size is too small" (nothing was computed)    */
   DPC_STATUS_KEY_OVERFLOW = 4,    /* dpc_voxel_downsample: the batch's voxel keys need more than 64 bits (nothing computed) */
   DPC_STATUS_NONFINITE = 8,       /* dpc_voxel_downsample: a NaN or infinite coordinate (nothing was computed);
-                                   * dpc_densify: a non-finite vertex, edge length or midpoint (that model stops)       */
+                                   * dpc_densify: a non-finite vertex, edge length or midpoint (that model stops);
+                                   * dpc_render_points: a non-finite coordinate, colour or radius, or a radius <= 0, in
+                                   * a cloud (that image stays background)                                             */
   DPC_STATUS_DENSIFY_ORDER = 16   /* dpc_densify: a new edge longer than kDnBand x the round's longest edge: the
                                    * round-ordering argument failed and the output may differ from the reference's      */
 };
@@ -451,6 +453,58 @@ int dpc_densify(const double* verts, int n_verts, const int32_t* edges, int n_ed
                 const int32_t* face_edges, int n_faces, const int32_t* model_desc, const int32_t* host_model_desc,
                 int models, int max_face_count, int begin, int rounds, double* out, int32_t* status, int32_t* active,
                 void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Point-cloud rendering (dpc/render/render_point_cloud.py:19-53 and render_point_cloud_runner.py: one Blender 2.79b
+ * process per model running render_point_cloud_blender.py) for P ragged clouds in one call, ray-traced in fp64.
+ *
+ * Geometry, after render_point_cloud_blender.py:
+ *   points   a prediction-frame point p is the scene point (X, Y, Z) = (p2, -p0, p1) (add_points, :150-164: is_mvc
+ *            negates column 0, then x = p[2], y = p[0], z = p[1]); the caller maps them, this call takes scene points.
+ *            Each is a sphere of radius point_size = 0.01, DEFAULT_SIZE times the unit UV-sphere prototype (:113, :137,
+ *            :196); per-point radii replace it (load_data's colored subsets, :139-147).
+ *   camera   obj_centened_camera_pos(d, az, el) = (d cos az cos el, d sin az cos el, d sin el) (deg / 180 * pi), placed
+ *            at C = (y, x, z) (the swap at :46-48); TRACK_NEGATIVE_Z / UP_Y on the origin: f = -C / |C|,
+ *            r = normalise(f x e_z), u = r x f.  Elevation +-90 deg (|f x e_z| < 1e-12) has no such frame: the Python
+ *            layer refuses it.  Frames are computed on the host in fp64 and passed per image: no device trigonometry.
+ *   lens     F = lens_mm / 32 * S pixels for an S x S image (32 mm sensor).  like_train_data (:83-87) sets 60 mm,
+ *            F = 1.875 S, the training renderer's focal_length; without it Blender keeps its startup camera (35 mm in
+ *            2.79's default scene, not checked here).
+ *   samples  pixel (i, j) (row i from the top) has ss x ss samples (a, b):
+ *              x_s = (j + (b + 0.5) / ss) - S/2,   y_s = S/2 - (i + (a + 0.5) / ss),
+ *              D = (f + (x_s / F) r) + (y_s / F) u, per component in that order.
+ *   hit      m = C - P, a = D.D, b = m.D, c = m.m - r^2, disc = b b - a c; the sphere is hit when c > 0, disc >= 0 and
+ *            t = (-b - sqrt(disc)) / a > 0.  Each sample keeps the minimum of the 64-bit key (bits(float32(t)) << 32) | k,
+ *            k the point's index in its cloud: ties in float32 depth go to the lowest index; none: background (-1).
+ *   shading  (our own; Cycles is not reproduced) at the winner, with the fp64 t: H = C + t D, n = (H - P) / r,
+ *            v = -D / |D|, colour = albedo (0.4 + 0.6 max(0, n.v)), albedo 0.5 grey (the prototype material, :95-97)
+ *            or the point's colour; background white (horizon_color = (1, 1, 1), :64).
+ *   pixel    the ss^2 sample colours summed in fp64 in row-major (a, b) order onto 0.0, divided once by ss^2 and rounded
+ *            once to float32.  (The uint8 image, floor(255 clip(v, 0, 1) + 0.5) of that float32, is the Python layer's.)
+ * All of it in fp64 with every operation rounded on its own (built with -ffp-contract=off); dot products are
+ * (x x' + y y') + z z'; sqrt and division are the correctly rounded IEEE operations.
+ *
+ * Deliberate deviations from the reference's image: exact spheres instead of bevelled UV spheres; no round trip of the
+ * coordinates through the PLY text's '%f'; a box filter over stratified samples instead of Cycles' path tracing and pixel
+ * filter; no colour management; RGB without an alpha channel.
+ *
+ * Arguments: points [n_points,3] float64 (DEVICE), scene frame; colors [n_points,3] float32 (DEVICE) or NULL (grey);
+ * radii [n_points] float64 (DEVICE) or NULL (every point `radius`); cloud p is (start, count) = table[p] (DEVICE) =
+ * host_table[p] (HOST, the same values), k counting from start; frames [P,12] float64 (DEVICE): C, r, u, f of image p;
+ * image_size S, supersample ss, focal F (pixels), radius the default radius.  Outputs: image [P,S,S,3] float32 (DEVICE);
+ * ids [P,S ss,S ss] int32 (DEVICE) or NULL: the winning k of every sample (row i ss + a, column j ss + b), -1 for none.
+ * status (DEVICE, zeroed by the caller; NULL allowed): DPC_STATUS_NONFINITE when a point of a cloud has a NaN or infinite
+ * coordinate, colour or radius, or a radius that is not > 0; that image (and its ids) stays background.  No
+ * floating-point atomics: the per-sample minimum is an integer one, so results are bit-identical from run to run and do
+ * not depend on how clouds are batched.  No workspace, no host synchronisation and no host -> device copy.
+ * DPC_ERR_SHAPE, before any launch, for P < 0, n_points < 0 or 3 n_points > 2^31 - 1, S outside [1, 4096], ss outside
+ * [1, 4], F or radius not finite and > 0, a negative start or count, a range outside [0, n_points), or
+ * P ceil(S / 16)^2 x 256 > 2^31 - 1 (the launch's work-items).  With valid arguments and NULL device pointers it returns
+ * DPC_ERR_NULL without touching a device.  Added without a new ABI number.
+ * ------------------------------------------------------------------------------------------------- */
+int dpc_render_points(const double* points, const float* colors, const double* radii, int n_points, const int32_t* table,
+                      const int32_t* host_table, int images, const double* frames, int image_size, int supersample,
+                      double focal, double radius, float* image, int32_t* ids, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Opt-in measurement aid (nothing in the reference corresponds to it).  After dpc_profile_enable(capacity)

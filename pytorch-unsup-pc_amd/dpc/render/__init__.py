@@ -25,6 +25,7 @@ from .alignment import (alignment_candidates, alignment_to_ground_truth, as_rota
 from .chamfer import chamfer_batched, chamfer_of_split, eval_chamfer, nearest_batched  # noqa: F401
 from .downsample import downsample_split, voxel_down_sample  # noqa: F401
 from .densify import MeshError, densify_meshes, densify_split, load_obj_mesh  # noqa: F401
+from .visualise import camera_frame, render_point_cloud, render_point_clouds, render_split, write_png  # noqa: F401
 
 __all__ = [
     "pointcloud_project_fast", "pointcloud_project", "pc_perspective_transform", "pointcloud2voxels3d_fast",
@@ -38,6 +39,7 @@ __all__ = [
     "quaternion_from_campos", "as_rotation_matrix", "from_rotation_matrix", "pose_errors",
     "nearest_batched", "chamfer_batched", "chamfer_of_split", "eval_chamfer", "voxel_down_sample", "downsample_split",
     "load_obj_mesh", "densify_meshes", "densify_split", "MeshError",
+    "camera_frame", "render_point_clouds", "render_point_cloud", "render_split", "write_png",
 ]
 
 

@@ -79,6 +79,7 @@ _FUNCTIONS = (
     ("dpc_voxel_downsample", _i, [_vp, _i, _i, _vp, _vp, _i, _d] + [_vp] * 6),
     ("dpc_densify_workspace_bytes", _sz, [_i, _i64, _i64, _i64, _i]),
     ("dpc_densify", _i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp] + [_i] * 4 + [_vp] * 5),
+    ("dpc_render_points", _i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _d, _d] + [_vp] * 4),
     ("dpc_profile_enable", _i, [_i]),
     ("dpc_profile_disable", _i, None),
     ("dpc_profile_count", _i, None),
