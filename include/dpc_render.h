@@ -57,15 +57,18 @@ enum {
 enum {
   DPC_STATUS_BAD_INDEX = 1,   /* a point_index entry was outside [0, N_src): the point was dropped (the reference's fancy
                                * indexing raises IndexError there, dpc/util/point_cloud_to.py:266-295); dpc_densify: a
-                               * mesh id out of range or inconsistent, or an edge on more than max_face_count faces    */
+                               * mesh id out of range or inconsistent, or an edge on more than max_face_count faces;
+                               * dpc_render_meshes: a face's vertex index or material id outside its mesh (skipped)    */
   DPC_STATUS_VOXEL_TOO_SMALL = 2, /* dpc_voxel_downsample: open3d's "voxel_size is too small" (nothing was computed)    */
   DPC_STATUS_KEY_OVERFLOW = 4,    /* dpc_voxel_downsample: the batch's voxel keys need more than 64 bits (nothing computed) */
   DPC_STATUS_NONFINITE = 8,       /* dpc_voxel_downsample: a NaN or infinite coordinate (nothing was computed);
                                    * dpc_densify: a non-finite vertex, edge length or midpoint (that model stops);
                                    * dpc_render_points: a non-finite coordinate, colour or radius, or a radius <= 0, in
-                                   * a cloud (that image stays background)                                             */
-  DPC_STATUS_DENSIFY_ORDER = 16   /* dpc_densify: a new edge longer than kDnBand x the round's longest edge: the
+                                   * a cloud (that image stays background); dpc_render_meshes: a face with a NaN or
+                                   * infinite vertex or projection (it was skipped)                                    */
+  DPC_STATUS_DENSIFY_ORDER = 16,  /* dpc_densify: a new edge longer than kDnBand x the round's longest edge: the
                                    * round-ordering argument failed and the output may differ from the reference's      */
+  DPC_STATUS_NEAR = 32            /* dpc_render_meshes: a face has a vertex at depth d <= DPC_MESH_NEAR (it was skipped)   */
 };
 
 /* Geometry and camera constants of one call (dpc/resources/default_config.yaml:77-89 and the cfg fields
@@ -505,6 +508,69 @@ int dpc_densify(const double* verts, int n_verts, const int32_t* edges, int n_ed
 int dpc_render_points(const double* points, const float* colors, const double* radii, int n_points, const int32_t* table,
                       const int32_t* host_table, int images, const double* frames, int image_size, int supersample,
                       double focal, double radius, float* image, int32_t* ids, int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Training views from triangle meshes: what the reference downloads as <synth_set>-renders.tar.gz (render_N.png RGBA,
+ * depth_N.png, camera_N.mat per model, made with Blender) for W views of M ragged meshes in one call, rasterised in fp64
+ * with the camera of the reference's own projection (pc_perspective_transform, dpc/util/point_cloud_to.py:136-178).
+ *
+ *   camera   view w has a rotation R (row-major 3 x 3: the rotation of q = quaternion_from_campos(cam_pos), computed on
+ *            the host in fp64), camera_distance and focal_length f.  A vertex p (.obj coordinates) goes to
+ *              r_k = (R_k0 p_0 + R_k1 p_1) + R_k2 p_2,   d = r_0 + camera_distance,   v = (r_1 f) / d,   u = (r_2 f) / d,
+ *            and to the pixel coordinates  x = (u + 0.5) S  (columns),  y = (0.5 - v) S  (rows, row 0 at v = +0.5).
+ *            Pixel (i, j) of the S x S image covers y in [i, i + 1), x in [j, j + 1).
+ *   samples  ss x ss per pixel: sample (a, b) of pixel (i, j) at y = i + (a + 0.5) / ss, x = j + (b + 0.5) / ss.
+ *   coverage the edge function of the directed edge a -> b at p is E = (b_x - a_x)(p_y - a_y) - (b_y - a_y)(p_x - a_x),
+ *            evaluated with the ends in lexicographic (x, then y) order and negated when that swapped them, so that the
+ *            two faces on an edge get the same bits.  With e_0, e_1, e_2 the functions of the edges 1 -> 2, 2 -> 0, 0 -> 1
+ *            and A that of 0 -> 1 at vertex 2, a sample is inside when A != 0 and all e_k >= 0 or all e_k <= 0
+ *            (inclusive, both windings).  A projected triangle with A = 0 covers nothing.
+ *   depth    perspective-correct: 1 / d = ((e_0 / A) w_0 + (e_1 / A) w_1) + (e_2 / A) w_2 with w_k = 1 / d_k; a sample
+ *            whose 1 / d is not > 0 is not covered.
+ *   visible  each sample keeps the minimum of the 64-bit key (bits(float32(d)) << 32) | k, k the face's index in its mesh,
+ *            an integer minimum: the image does not depend on the order of the faces, on tiling or on batching, and
+ *            ties in float32 depth go to the lowest index.
+ *   guards   a face with a vertex index outside its mesh or a material id outside its table (DPC_STATUS_BAD_INDEX), with
+ *            a vertex whose coordinates, d, x or y are not finite (DPC_STATUS_NONFINITE) or with a vertex at
+ *            d <= DPC_MESH_NEAR (DPC_STATUS_NEAR; a guard, not a clipping path: ShapeNet models sit inside the unit
+ *            cube at distance 2) is skipped whole and sets its bit.  None of these values becomes an address.
+ *   shading  per covered sample Kd[material] (DPC_MESH_AMBIENT + DPC_MESH_DIFFUSE |n_0| / |n|), n = (r_1 - r_0) x
+ *            (r_2 - r_0) the face normal in camera space (|n| = 0: the ambient term alone): a headlight along the view
+ *            axis (-1, 0, 0).  No textures, no smooth normals, no shadows, no specular term.
+ *   pixel    alpha = covered / ss^2; rgb = the covered samples' colours summed in row-major (a, b) order onto 0.0 and
+ *            divided by their number, clipped to [0, 1] (straight alpha; 0 when nothing is covered); every channel to
+ *            uint8 by floor(255 x + 0.5).
+ *   depth px the fp64 d of the sample with the smallest key of the pixel (the first such sample in (a, b) order), stored
+ *            as min(65535, floor(d / 10 * 65535 + 0.5)): the inverse of the reference's loadDepth
+ *            (dpc/run/create_data_torch.py:66-70); 65535 where nothing is covered.  face_id is that key's face, -1 for none.
+ * All of it in fp64 with every operation rounded on its own (built with -ffp-contract=off); sqrt and division are the
+ * correctly rounded IEEE operations.
+ *
+ * Deliberate deviations from the archive's Blender renders: flat shading by a headlight instead of Blender's lamps and
+ * smooth normals; diffuse colour only (no textures, no transparency); a box filter over a regular sample grid.
+ *
+ * Arguments: verts [n_verts,3] float64, faces [n_faces,3] int32 (vertex indices local to the mesh), face_mat [n_faces] int32
+ * (local to the mesh's materials), kd [n_mats,3] float64 (all DEVICE); mesh m is the row meshes[m] (DEVICE) =
+ * host_meshes[m] (HOST, the same values) of 6 int32: (vertex start, count, face start, count, material start, count);
+ * view w renders mesh view_mesh[w] (DEVICE) = host_view_mesh[w] (HOST) with view_cam[w] (DEVICE) = 11 float64: R,
+ * camera_distance, focal_length.  Several views may share a mesh.  Outputs (DEVICE): rgba [W,S,S,4] uint8, depth [W,S,S]
+ * uint16, face_id [W,S,S] int32 or NULL.  status (DEVICE, zeroed by the caller; NULL allowed) gets the bits above OR-ed in.
+ * workspace (DEVICE): dpc_render_meshes_workspace_bytes(host_meshes, M, host_view_mesh, W) bytes (0 for a table it
+ * refuses), 16 W + 32 (vertices of the views' meshes) + 8 (faces of the views' meshes) + 4 * 15 at most.  No
+ * floating-point atomics, no allocation, no host synchronisation and no host -> device copy.  DPC_ERR_SHAPE, before any
+ * launch, for negative counts, 3 n > 2^31 - 1, S outside [1, 1024], ss outside [1, 4], W > 65535, a negative start or
+ * count or a range outside its buffer, a view's mesh outside [0, M), or W ceil(S / 16)^2 x 256 > 2^31 - 1.  With valid
+ * arguments and NULL device pointers it returns DPC_ERR_NULL without touching a device.  Added without a new ABI number.
+ * ------------------------------------------------------------------------------------------------- */
+#define DPC_MESH_NEAR 1e-3    /* the near guard: faces with a vertex at d <= this are skipped */
+#define DPC_MESH_AMBIENT 0.25 /* shading: ambient + diffuse = 1 */
+#define DPC_MESH_DIFFUSE 0.75
+size_t dpc_render_meshes_workspace_bytes(const int32_t* host_meshes, int n_meshes, const int32_t* host_view_mesh, int views);
+int dpc_render_meshes(const double* verts, int n_verts, const int32_t* faces, const int32_t* face_mat, int n_faces,
+                      const double* kd, int n_mats, const int32_t* meshes, const int32_t* host_meshes, int n_meshes,
+                      const int32_t* view_mesh, const int32_t* host_view_mesh, const double* view_cam, int views,
+                      int image_size, int supersample, uint8_t* rgba, uint16_t* depth, int32_t* face_id,
+                      int32_t* status, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Opt-in measurement aid (nothing in the reference corresponds to it).  After dpc_profile_enable(capacity)

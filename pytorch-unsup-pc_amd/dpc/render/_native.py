@@ -28,6 +28,9 @@ DPC_STATUS_VOXEL_TOO_SMALL = 2
 DPC_STATUS_KEY_OVERFLOW = 4
 DPC_STATUS_NONFINITE = 8
 DPC_STATUS_DENSIFY_ORDER = 16
+DPC_STATUS_NEAR = 32
+DPC_MESH_NEAR = 1e-3
+DPC_MESH_AMBIENT, DPC_MESH_DIFFUSE = 0.25, 0.75
 
 
 class DpcParams(ctypes.Structure):
@@ -80,6 +83,8 @@ _FUNCTIONS = (
     ("dpc_densify_workspace_bytes", _sz, [_i, _i64, _i64, _i64, _i]),
     ("dpc_densify", _i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp] + [_i] * 4 + [_vp] * 5),
     ("dpc_render_points", _i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _d, _d] + [_vp] * 4),
+    ("dpc_render_meshes_workspace_bytes", _sz, [_vp, _i, _vp, _i]),
+    ("dpc_render_meshes", _i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i] + [_vp] * 6),
     ("dpc_profile_enable", _i, [_i]),
     ("dpc_profile_disable", _i, None),
     ("dpc_profile_count", _i, None),

@@ -1,0 +1,477 @@
+"""Training views from ShapeNet meshes on the GPU, in place of the reference's downloaded Blender renders.
+
+The reference trains on <synth_set>-renders.tar.gz (data/download_train_data.sh): per model render_N.png (RGBA),
+camera_N.mat and depth_N.png, which dpc/run/create_data_torch.py packs into <model>_features.p.  Here the views of a
+whole group of models are rasterised in one dpc_render_meshes call (csrc/dpc_mesh_raster.hip), in fp64, with the camera
+the reference's own projection expects (pc_perspective_transform's quaternion branch); include/dpc_render.h states the
+semantics and the deliberate deviations from Blender's image.
+
+    load_obj_scene          .obj (+ .mtl diffuse colours) -> V, F, material, Kd, names; every polygon, fan-triangulated
+    sample_camera_positions random camera positions in Blender's Z-up frame (the ranges are an assumption)
+    view_rotation           cam_pos -> the 3 x 3 rotation of quaternion_from_campos(cam_pos), host fp64
+    view_transform          the renderer's host transform of points: (d, v, u) of pc_perspective_transform
+    render_mesh_views       scenes x camera positions -> rgba [W,S,S,4] uint8, depth [W,S,S] uint16 on the device
+    camera_extrinsic        the 4 x 4 `extrinsic` of camera_N.mat for a camera position
+    features_of_views       the dict create_record pickles (image, mask, name, extrinsic, cam_pos, depth)
+    render_training_views   the loop over a split with caller-supplied I/O
+
+Reading .obj files stays on the host; writing PNG / .mat / pickle files stays with the caller (tools/render_train_data.py).
+"""
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from . import _batch, _native
+from .alignment import as_rotation_matrix, quaternion_from_campos
+from .densify import MeshError
+
+DEFAULT_KD = 0.5           # the grey of a face without a usable material
+WORKSPACE_LIMIT = 4 << 30  # bytes of dpc_render_meshes workspace per job (a single model may need more)
+MAX_DEPTH = 10.0           # depth_N.png spans [0, 10] over 16 bits (create_data_torch.py:66-70)
+
+
+# ------------------------------------------------------------------------------------------------------
+# reading meshes
+# ------------------------------------------------------------------------------------------------------
+def _read_mtl(path):
+    """{material name: Kd (r, g, b)} of a .mtl file; materials without a Kd line are left out."""
+    out, name = {}, None
+    with open(path) as fh:
+        for text in fh:
+            fields = text.split()
+            if not fields:
+                continue
+            if fields[0] == "newmtl":
+                name = " ".join(fields[1:])
+            elif fields[0] == "Kd" and name is not None and len(fields) >= 4:
+                out[name] = [float(x) for x in fields[1:4]]
+    return out
+
+
+def load_obj_scene(path):
+    """An .obj file as (V [n,3] float64, F [f,3] int64, material [f] int64, Kd [k,3] float64, names [k]).
+
+    Every face is kept and polygons are fan-triangulated ((0, i, i + 1)); only the vertex field of "v/vt/vn" is read.
+    `usemtl` selects the material of the faces after it; the `mtllib` files, looked up next to the .obj, are read for Kd
+    only.  Faces before any usemtl, a missing .mtl file and a material without Kd get one default grey (name "", Kd
+    0.5), appended to the table when needed.  Kd values are clipped to [0, 1].  ValueError for a relative (<= 0) face
+    index, as load_obj_mesh refuses them, IndexError for an index beyond the vertices or a face with fewer than three
+    corners."""
+    verts, faces, mats = [], [], []
+    table, names, index = {}, [], {}
+    here = os.path.dirname(os.path.abspath(path))
+    current = None
+
+    def material(name):
+        key = name if name in table else None
+        if key not in index:
+            index[key] = len(names)
+            names.append("" if key is None else key)
+        return index[key]
+
+    with open(path) as fh:
+        for text in fh:
+            fields = text.split()
+            if not fields:
+                continue
+            tag = fields[0]
+            if tag == "v":
+                if len(fields) < 4:
+                    raise IndexError("load_obj_scene: %s: a vertex line with %d coordinates" % (path, len(fields) - 1))
+                verts.append([float(x) for x in fields[1:4]])
+            elif tag == "f":
+                if len(fields) < 4:
+                    raise IndexError("load_obj_scene: %s: a face line with %d indices" % (path, len(fields) - 1))
+                corners = [int(field.split("/", 1)[0]) - 1 for field in fields[1:]]
+                if min(corners) < 0:
+                    raise ValueError("load_obj_scene: %s: face index %d <= 0 (relative OBJ indices are refused)"
+                                     % (path, min(corners) + 1))
+                m = material(current)
+                for i in range(1, len(corners) - 1):
+                    faces.append((corners[0], corners[i], corners[i + 1]))
+                    mats.append(m)
+            elif tag == "usemtl":
+                current = " ".join(fields[1:])
+            elif tag == "mtllib":
+                for name in fields[1:]:
+                    lib = os.path.join(here, name)
+                    if os.path.isfile(lib):
+                        table.update(_read_mtl(lib))
+    V = np.array(verts, dtype=np.float64).reshape(-1, 3)
+    F = np.array(faces, dtype=np.int64).reshape(-1, 3)
+    if len(F) and F.max() >= len(V):
+        raise IndexError("load_obj_scene: %s: face index %d beyond the %d vertices" % (path, F.max() + 1, len(V)))
+    Kd = np.array([[DEFAULT_KD] * 3 if n not in table else table[n] for n in names], dtype=np.float64).reshape(-1, 3)
+    return V, F, np.array(mats, dtype=np.int64), np.clip(Kd, 0.0, 1.0), names
+
+
+# ------------------------------------------------------------------------------------------------------
+# cameras
+# ------------------------------------------------------------------------------------------------------
+def sample_camera_positions(num_models, num_views, seed, azimuth_deg=(0.0, 360.0), elevation_deg=(-20.0, 40.0),
+                            distance=2.0):
+    """[num_models, num_views, 3] float64 camera positions in Blender's Z-up frame, (d cos el cos az, d cos el sin az,
+    d sin el), azimuth and elevation uniform in their ranges (numpy default_rng(seed)), distance a scalar or a (lo, hi)
+    range.
+
+    ASSUMPTION: the distribution behind the released archive is not recorded in the reference; these defaults (all
+    azimuths, elevations of -20 .. 40 degrees, distance 2) are ours.  The image does not depend on the distance: the
+    projection normalises cam_pos and places the camera at cfg.camera_distance.  Elevations reaching +-90 degrees are
+    refused: ypr_from_campos divides by sqrt(cx^2 + cy^2) there."""
+    az, el = (tuple(float(x) for x in r) for r in (azimuth_deg, elevation_deg))
+    dist = (float(distance),) * 2 if np.ndim(distance) == 0 else tuple(float(x) for x in distance)
+    if len(az) != 2 or len(el) != 2 or len(dist) != 2 or not np.isfinite(az + el + dist).all():
+        raise ValueError("sample_camera_positions: azimuth_deg, elevation_deg must be finite (lo, hi) pairs")
+    if az[0] > az[1] or el[0] > el[1] or dist[0] > dist[1] or dist[0] <= 0.0:
+        raise ValueError("sample_camera_positions: ranges must be ordered and distance > 0")
+    if el[0] <= -90.0 or el[1] >= 90.0:
+        raise ValueError("sample_camera_positions: elevation range %r reaches +-90 degrees, where the reference's "
+                         "ypr_from_campos divides by zero" % (el,))
+    M, V = int(num_models), int(num_views)
+    if M < 0 or V < 0:
+        raise ValueError("sample_camera_positions: num_models and num_views must be >= 0")
+    rng = np.random.default_rng(seed)
+    a = np.deg2rad(rng.uniform(az[0], az[1], (M, V)))
+    e = np.deg2rad(rng.uniform(el[0], el[1], (M, V)))
+    d = rng.uniform(dist[0], dist[1], (M, V))
+    return np.stack([d * np.cos(e) * np.cos(a), d * np.cos(e) * np.sin(a), d * np.sin(e)], axis=-1)
+
+
+def view_rotation(cam_pos):
+    """The rotation R of q = quaternion_from_campos(cam_pos) (host fp64, [3,3]): quaternion_rotate(p, q) = R p.
+    ValueError for a position on the vertical axis (elevation +-90 degrees) or a non-finite one."""
+    c = np.asarray(cam_pos, dtype=np.float64).reshape(-1)
+    if c.shape != (3,) or not np.isfinite(c).all() or not np.hypot(c[0], c[1]) > 0.0:
+        raise ValueError("view_rotation: cam_pos %r must be three finite values off the vertical axis" % (cam_pos,))
+    return as_rotation_matrix(quaternion_from_campos(c))
+
+
+def view_transform(points, cam_pos, camera_distance=2.0, focal_length=1.875):
+    """The renderer's host transform of [n,3] .obj-space points for one camera: (d, v, u) [n,3] with r = R p,
+    d = r_0 + camera_distance, v = r_1 f / d, u = r_2 f / d.  pc_perspective_transform's quaternion branch returns
+    (d - camera_distance, v, u)."""
+    P = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    R = view_rotation(cam_pos)
+    r = np.stack([(R[k, 0] * P[:, 0] + R[k, 1] * P[:, 1]) + R[k, 2] * P[:, 2] for k in range(3)], axis=1)
+    d = r[:, 0] + float(camera_distance)
+    return np.stack([d, (r[:, 1] * float(focal_length)) / d, (r[:, 2] * float(focal_length)) / d], axis=1)
+
+
+def camera_extrinsic(cam_pos, camera_distance=2.0):
+    """The 4 x 4 `extrinsic` of camera_N.mat (float64): the matrix E that camera_from_blender (util/camera.py:15-35)
+    rearranges into [[R, t], [0, 1]] with R = view_rotation(cam_pos) and t = (camera_distance, 0, 0), so that the matrix
+    branch of pc_perspective_transform gives the quaternion branch's (d, f r_1, f r_2)."""
+    R = view_rotation(cam_pos)
+    E = np.zeros((4, 4), dtype=np.float64)
+    E[2, 0], E[2, 2], E[2, 1] = -R[0, 0], R[0, 1], R[0, 2]
+    E[1, 0], E[1, 2], E[1, 1] = R[1, 0], -R[1, 1], -R[1, 2]
+    E[0, 0], E[0, 2], E[0, 1] = -R[2, 0], R[2, 1], R[2, 2]
+    E[2, 3], E[1, 3], E[0, 3], E[3, 3] = float(camera_distance), 0.0, 0.0, 1.0
+    return E
+
+
+# ------------------------------------------------------------------------------------------------------
+# rendering
+# ------------------------------------------------------------------------------------------------------
+def _cfg_get(cfg, key, default):
+    if cfg is None:
+        return default
+    if isinstance(cfg, dict):
+        return cfg.get(key, default)
+    return getattr(cfg, key, default)
+
+
+def _scene(scene, i):
+    """(V, F, material, Kd[, names]) -> host arrays (float64 [n,3], int32 [f,3], int32 [f], float64 [k,3])."""
+    if len(scene) < 4:
+        raise ValueError("render_mesh_views: scene %d must be (V, F, material, Kd[, names])" % i)
+    V, F, mat, Kd = (np.asarray(x) for x in scene[:4])
+    V = np.ascontiguousarray(V.reshape(-1, 3) if V.size == 0 else V, dtype=np.float64)
+    F = F.reshape(-1, 3) if F.size == 0 else F
+    Kd = np.ascontiguousarray(Kd.reshape(-1, 3) if Kd.size == 0 else Kd, dtype=np.float64)
+    mat = mat.reshape(-1)
+    if V.ndim != 2 or V.shape[1] != 3 or F.ndim != 2 or F.shape[1] != 3 or Kd.ndim != 2 or Kd.shape[1] != 3:
+        raise ValueError("render_mesh_views: scene %d: V, F and Kd must be [n,3], [f,3] and [k,3], got %s, %s, %s"
+                         % (i, V.shape, F.shape, Kd.shape))
+    if len(mat) != len(F):
+        raise ValueError("render_mesh_views: scene %d: %d material ids for %d faces" % (i, len(mat), len(F)))
+    for what, a in (("F", F), ("material", mat)):
+        if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > _batch.INT32_MAX):
+            raise ValueError("render_mesh_views: scene %d: %s does not fit int32" % (i, what))
+    if not (np.isfinite(Kd).all() and (Kd >= 0.0).all() and (Kd <= 1.0).all()):
+        raise ValueError("render_mesh_views: scene %d: Kd must lie in [0, 1]" % i)
+    return V, np.ascontiguousarray(F, dtype=np.int32), np.ascontiguousarray(mat, dtype=np.int32), Kd
+
+
+def _tables(items, view_scene):
+    rows, vo, fo, ko = [], 0, 0, 0
+    for V, F, _, Kd in items:
+        rows.append((vo, len(V), fo, len(F), ko, len(Kd)))
+        vo, fo, ko = vo + len(V), fo + len(F), ko + len(Kd)
+    meshes = _batch.table(rows if rows else np.zeros((0, 6)), 6,
+                          "render_mesh_views: more than 2^31 - 1 vertices, faces or materials in one call")
+    views = _batch.table(np.asarray(view_scene, dtype=np.int64).reshape(-1, 1), 1, "render_mesh_views: bad scene index")
+    return meshes, views.reshape(-1), (vo, fo, ko)
+
+
+def _workspace_bytes(meshes, views):
+    L = _native.lib()
+    return L.dpc_render_meshes_workspace_bytes(meshes.ctypes.data_as(ctypes.c_void_p), len(meshes),
+                                               views.ctypes.data_as(ctypes.c_void_p), len(views))
+
+
+def _status_message(items, view_scene, cams, S, bits):
+    """Which scene a status bit came from, found on the host."""
+    N = _native
+    for i, (V, F, mat, Kd) in enumerate(items):
+        if bits & N.DPC_STATUS_BAD_INDEX and len(F) and (F.min() < 0 or F.max() >= len(V) or mat.min() < 0
+                                                         or mat.max() >= len(Kd)):
+            return "render_mesh_views: scene %d has a face index outside its vertices or a material id outside its table" % i
+        if bits & N.DPC_STATUS_NONFINITE and not np.isfinite(V).all():
+            return "render_mesh_views: scene %d holds a NaN or infinite vertex coordinate" % i
+    if bits & N.DPC_STATUS_BAD_INDEX:
+        return "render_mesh_views: a face index or material id is out of range"
+    if bits & N.DPC_STATUS_NONFINITE:
+        return "render_mesh_views: a vertex or its projection is not finite"
+    for w, s in enumerate(view_scene):
+        V, F = items[s][0], items[s][1]
+        R = cams[w, :9].reshape(3, 3)
+        d = (R[0, 0] * V[:, 0] + R[0, 1] * V[:, 1]) + R[0, 2] * V[:, 2] + cams[w, 9]
+        if len(F) and (d[np.unique(F)] <= N.DPC_MESH_NEAR).any():
+            return ("render_mesh_views: view %d of scene %d: a face reaches the camera plane (depth <= %g); the model "
+                    "must lie in front of the camera" % (w, s, N.DPC_MESH_NEAR))
+    return "render_mesh_views: a face reaches the camera plane (depth <= %g)" % N.DPC_MESH_NEAR
+
+
+def render_mesh_views(scenes, cam_pos, cfg=None, image_size=128, supersample=3, return_face_id=False, view_scene=None,
+                      camera_distance=None, focal_length=None):
+    """Render views of M scenes ((V, F, material, Kd[, names]) as load_obj_scene returns them) in one dpc_render_meshes call.
+
+    cam_pos: [M,V,3] (or a list of [v_i,3] per scene) camera positions in Blender's frame, views scene-major; or, with
+    view_scene [W] (the scene of each view, in any order), [W,3].  camera_distance and focal_length come from cfg (a
+    dict or attribute object; 2.0 and 1.875 when missing) as pc_perspective_transform reads them, unless given.
+    Returns (rgba [W,S,S,4] uint8, depth [W,S,S] uint16) on the device, with return_face_id also face_id [W,S,S] int32:
+    the face that gives the depth pixel (-1: background).  Each scene is stored once however many views it has.
+    MeshError (a ValueError) naming the scene for a face index or material id out of range, a non-finite vertex or a
+    face at the camera plane; ValueError before anything touches a device for bad arguments."""
+    items = [_scene(s, i) for i, s in enumerate(scenes)]
+    if view_scene is None:
+        per = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in cam_pos]
+        if len(per) != len(items):
+            raise ValueError("render_mesh_views: cam_pos has %d entries for %d scenes" % (len(per), len(items)))
+        view_scene = np.concatenate([np.full(len(c), i, dtype=np.int64) for i, c in enumerate(per)]) if per else []
+        pos = np.concatenate(per) if per else np.zeros((0, 3))
+    else:
+        pos = np.asarray(cam_pos, dtype=np.float64).reshape(-1, 3)
+    view_scene = np.asarray(view_scene, dtype=np.int64).reshape(-1)
+    W = len(view_scene)
+    if len(pos) != W:
+        raise ValueError("render_mesh_views: %d camera positions for %d views" % (len(pos), W))
+    if W and (view_scene.min() < 0 or view_scene.max() >= len(items)):
+        raise ValueError("render_mesh_views: view_scene names a scene outside [0, %d)" % len(items))
+    cd = float(_cfg_get(cfg, "camera_distance", 2.0) if camera_distance is None else camera_distance)
+    fl = float(_cfg_get(cfg, "focal_length", 1.875) if focal_length is None else focal_length)
+    if not (np.isfinite(cd) and np.isfinite(fl) and cd > 0.0 and fl > 0.0):
+        raise ValueError("render_mesh_views: camera_distance %r and focal_length %r must be finite and > 0" % (cd, fl))
+    cams = np.zeros((W, 11), dtype=np.float64)
+    for w in range(W):
+        try:
+            cams[w, :9] = view_rotation(pos[w]).reshape(-1)
+        except ValueError as exc:
+            raise ValueError("render_mesh_views: view %d: %s" % (w, exc)) from exc
+    cams[:, 9], cams[:, 10] = cd, fl
+    S, ss = int(image_size), int(supersample)
+    meshes, views, (nv, nf, nk) = _tables(items, view_scene)
+    L = _native.lib()
+    hm, hv = meshes.ctypes.data_as(ctypes.c_void_p), views.ctypes.data_as(ctypes.c_void_p)
+    _batch.dry_run(L.dpc_render_meshes(None, nv, None, None, nf, None, nk, None, hm, len(meshes), None, hv, None, W, S, ss,
+                                       None, None, None, None, None, None),
+                   "render_mesh_views: refused by dpc_render_meshes (%d scenes, %d views, image_size %d, supersample %d): "
+                   "need 1 <= image_size <= 1024, 1 <= supersample <= 4, at most 65535 views" % (len(items), W, S, ss))
+    dev = _batch.device("dpc.render mesh rendering")
+    rgba = torch.empty((W, S, S, 4), dtype=torch.uint8, device=dev)
+    depth = torch.empty((W, S, S), dtype=torch.uint16, device=dev)
+    face_id = torch.empty((W, S, S), dtype=torch.int32, device=dev) if return_face_id else None
+    if W:
+        cat = lambda k, dt, shape: torch.from_numpy(np.concatenate([it[k] for it in items]).astype(dt, copy=False)
+                                                    .reshape(shape)).to(dev)
+        verts, faces, mats, kd = cat(0, np.float64, (-1, 3)), cat(1, np.int32, (-1, 3)), cat(2, np.int32, (-1,)), \
+            cat(3, np.float64, (-1, 3))
+        meshes_d, views_d, cams_d = (torch.from_numpy(a).to(dev) for a in (meshes, views, cams))
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        ws = _batch.workspace(_workspace_bytes(meshes, views), dev)
+        P = _native.ptr
+        with torch.cuda.device(dev):
+            rc = L.dpc_render_meshes(P(verts) if nv else None, nv, P(faces) if nf else None, P(mats) if nf else None, nf,
+                                     P(kd) if nk else None, nk, P(meshes_d), hm, len(meshes), P(views_d), hv, P(cams_d), W,
+                                     S, ss, P(rgba), P(depth), P(face_id), P(status), P(ws), _native.stream_ptr(dev))
+        _native.check(rc, "dpc_render_meshes")
+        bits = int(status.item())
+        if bits:
+            raise MeshError(_status_message(items, view_scene, cams, S, bits))
+    return (rgba, depth, face_id) if return_face_id else (rgba, depth)
+
+
+# ------------------------------------------------------------------------------------------------------
+# features                                               reference: dpc/run/create_data_torch.py:66-70, 102-162
+# ------------------------------------------------------------------------------------------------------
+def _host(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def features_of_views(rgba, depth=None, cam_pos=None, extrinsic=None, name="", image_size=None, store_camera=True,
+                      store_depth=True):
+    """The dict create_record pickles as <model>_features.p for the V views of one model.
+
+    rgba [V,S,S,4] uint8 (what imread returns for render_N.png): mask = alpha / 255; image = (rgb mask + 255 (1 - mask))
+    / 255, the reference's white background, computed in float64 and stored as float32 like its `rgbs` array.  Keys:
+    image [V,S,S,3] float32, mask [V,S,S,1] float32, name; with store_camera extrinsic [V,4,4] and cam_pos [V,3] float32;
+    with store_depth depth [V,S,S,1] float32 from the uint16 depth [V,S,S] by loadDepth's arithmetic.  Only
+    image_size == S (or None): the reference resizes with skimage otherwise, which is not reproduced here, so a
+    different size raises ValueError: render at that size instead."""
+    img = _host(rgba)
+    if img.dtype != np.uint8 or img.ndim != 4 or img.shape[3] != 4 or img.shape[1] != img.shape[2]:
+        raise ValueError("features_of_views: rgba must be [V,S,S,4] uint8, got %s %s" % (img.dtype, img.shape))
+    V, S = img.shape[0], img.shape[1]
+    if image_size is not None and int(image_size) != S:
+        raise ValueError("features_of_views: image_size %d differs from the rendered %d; the reference's resize "
+                         "(skimage) is not reproduced: render at image_size %d" % (image_size, S, image_size))
+    rgbs = np.zeros((V, S, S, 3), dtype=np.float32)
+    masks = np.zeros((V, S, S, 1), dtype=np.float32)
+    for k in range(V):
+        rgb = img[k][:, :, 0:3]
+        mask = img[k][:, :, [3]]
+        mask = mask / 255.0
+        mask_fg = np.repeat(mask, 3, 2)
+        mask_bg = 1.0 - mask_fg
+        rgb = rgb * mask_fg + np.ones(rgb.shape) * 255.0 * mask_bg
+        rgb = rgb / 255.0
+        rgbs[k, :, :, :] = rgb
+        masks[k, :, :, :] = mask
+    feature = {"image": rgbs, "mask": masks, "name": name}
+    if store_camera:
+        if cam_pos is None or extrinsic is None:
+            raise ValueError("features_of_views: store_camera needs cam_pos [V,3] and extrinsic [V,4,4]")
+        cameras = np.zeros((V, 4, 4), dtype=np.float32)
+        pos = np.zeros((V, 3), dtype=np.float32)
+        cameras[:] = np.asarray(extrinsic, dtype=np.float64).reshape(V, 4, 4)
+        pos[:] = np.asarray(cam_pos, dtype=np.float64).reshape(V, 3)
+        feature["extrinsic"] = cameras
+        feature["cam_pos"] = pos
+    if store_depth:
+        if depth is None:
+            raise ValueError("features_of_views: store_depth needs depth [V,S,S] uint16")
+        dm = _host(depth)
+        if dm.dtype != np.uint16 or dm.shape != (V, S, S):
+            raise ValueError("features_of_views: depth must be [%d,%d,%d] uint16, got %s %s" % (V, S, S, dm.dtype, dm.shape))
+        depths = np.zeros((V, S, S, 1), dtype=np.float32)
+        for k in range(V):
+            d = dm[k].astype(np.float32)
+            d = d * np.float32(MAX_DEPTH - 0) / np.float32(pow(2, 16) - 1) + np.float32(0)   # loadDepth
+            d = (d - np.float32(0.0)) / np.float32(MAX_DEPTH)
+            d = d * np.float32(MAX_DEPTH) + np.float32(0.0)   # the order-0 resize between these two lines keeps an equal size
+            depths[k, :, :] = np.expand_dims(d, -1)
+        feature["depth"] = depths
+    return feature
+
+
+# ------------------------------------------------------------------------------------------------------
+# a split
+# ------------------------------------------------------------------------------------------------------
+def _groups(items, view_counts, step, workspace_limit):
+    """Consecutive index ranges of items, each at most `step` models and, unless it is one model, at most
+    workspace_limit bytes of dpc_render_meshes workspace."""
+    start, verts, faces = 0, 0, 0
+    for k, it in enumerate(items):
+        v, f = len(it[0]) * view_counts[k], len(it[1]) * view_counts[k]
+        need = 16 * sum(view_counts[start:k + 1]) + 32 * (verts + v) + 8 * (faces + f) + 64
+        if k > start and (k - start >= step or need > workspace_limit):
+            yield start, k
+            start, verts, faces = k, 0, 0
+        verts, faces = verts + v, faces + f
+    if start < len(items):
+        yield start, len(items)
+
+
+def _render_or_isolate(items, names, cams, errors, kwargs):
+    """One call for the batch; when it raises MeshError (a status bit is batch-wide), each model alone, so that the error
+    names the model or, with an `errors` dict, is recorded there and that model's result is None."""
+    try:
+        rgba, depth = render_mesh_views(items, cams, **kwargs)
+        rgba, depth = rgba.cpu().numpy(), depth.cpu().numpy()
+        out, o = [], 0
+        for c in cams:
+            out.append((rgba[o:o + len(c)], depth[o:o + len(c)]))
+            o += len(c)
+        return out
+    except MeshError as exc:
+        if len(items) == 1:
+            if errors is None:
+                raise MeshError("model %r: %s" % (names[0], exc)) from exc
+            errors[names[0]] = str(exc)
+            return [None]
+    return [r for it, name, c in zip(items, names, cams) for r in _render_or_isolate([it], [name], [c], errors, kwargs)]
+
+
+def render_training_views(model_names, load_scene, cam_pos, save=None, models_per_call=64, errors=None, keep=True,
+                          workspace_limit=WORKSPACE_LIMIT, **render):
+    """The views of every model of a split, at most models_per_call models (and workspace_limit bytes of workspace) per
+    dpc_render_meshes call.
+
+    load_scene(name) -> (V, F, material, Kd[, names]) (load_obj_scene(path), say), or None to skip the model;
+    cam_pos: {name: [V,3]}, a callable name -> [V,3], or an array [len(model_names),V,3]; save(name, rgba [V,S,S,4] uint8,
+    depth [V,S,S] uint16, cam_pos [V,3]) is called per model with host arrays.  **render goes to render_mesh_views (cfg,
+    image_size, supersample, camera_distance, focal_length).  Returns {name: (rgba, depth)}, or {} with keep=False.  The
+    images do not depend on the batching.  A model whose loading or rendering fails raises an error that names it; with
+    an `errors` dict it is recorded there (errors[name] = message) and skipped, and the other models go on."""
+    step = int(models_per_call)
+    if step < 1:
+        raise ValueError("render_training_views: models_per_call must be >= 1")
+    model_names = list(model_names)
+    if callable(cam_pos):
+        cams_of = cam_pos
+    elif isinstance(cam_pos, dict):
+        cams_of = cam_pos.__getitem__
+    else:
+        arr = np.asarray(cam_pos, dtype=np.float64)
+        if arr.ndim != 3 or arr.shape[0] != len(model_names) or arr.shape[2] != 3:
+            raise ValueError("render_training_views: cam_pos must be [%d,V,3], got %s" % (len(model_names), arr.shape))
+        lookup = {n: arr[i] for i, n in enumerate(model_names)}
+        cams_of = lookup.__getitem__
+    result, names, items, cams = {}, [], [], []
+
+    def flush():
+        for a, b in _groups(items, [len(c) for c in cams], step, workspace_limit):
+            done = _render_or_isolate(items[a:b], names[a:b], cams[a:b], errors, render)
+            for name, c, res in zip(names[a:b], cams[a:b], done):
+                if res is None:
+                    continue
+                if keep:
+                    result[name] = res
+                if save is not None:
+                    save(name, res[0], res[1], c)
+        del names[:], items[:], cams[:]
+
+    for name in model_names:
+        try:
+            scene = load_scene(name)
+            if scene is None:
+                continue
+            item = _scene(scene, len(items))
+            c = np.asarray(cams_of(name), dtype=np.float64).reshape(-1, 3)
+            for p in c:
+                view_rotation(p)
+        except (ValueError, IndexError, KeyError, OSError) as exc:
+            if errors is None:
+                raise type(exc)("model %r: %s" % (name, exc)) from exc
+            errors[name] = str(exc)
+            continue
+        items.append(item)
+        names.append(name)
+        cams.append(c)
+        if len(names) >= step:
+            flush()
+    flush()
+    return result

@@ -11,6 +11,7 @@ of our own; include/dpc_render.h states the semantics and the deliberate deviati
     render_point_cloud   the reference's render_point_cloud(point_cloud, cfg) -> numpy uint8 [S,S,3]
     render_split         render_point_cloud_runner.py's loop for a list of model names
     write_png            8-bit RGB PNG with zlib and struct only
+    write_png_rgba, write_png_gray16, read_png_any   the training views' render_N.png (RGBA8) and depth_N.png (16-bit grey)
 """
 import ctypes
 import numbers
@@ -295,3 +296,61 @@ def read_png(path):
     if (rows[:, 0] != 0).any():
         raise ValueError("read_png: %s uses PNG row filters" % path)
     return rows[:, 1:].reshape(h, w, 3).copy()
+
+
+_PNG_KINDS = {(8, 6): (np.dtype(np.uint8), 4), (16, 0): (np.dtype(">u2"), 1), (8, 2): (np.dtype(np.uint8), 3)}
+
+
+def _write_png_rows(path, rows, w, h, depth, ctype):
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    raw = b"".join(b"\x00" + rows[i].tobytes() for i in range(h))  # filter type 0 on every row
+    data = (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, depth, ctype, 0, 0, 0))
+            + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+    with open(path, "wb") as fh:
+        fh.write(data)
+
+
+def write_png_rgba(path, image_u8):
+    """An 8-bit RGBA PNG (straight alpha) of a [H,W,4] uint8 image: render_N.png of the training views."""
+    img = np.ascontiguousarray(image_u8.detach().cpu().numpy() if isinstance(image_u8, torch.Tensor) else image_u8)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 4:
+        raise ValueError("write_png_rgba: need a [H,W,4] uint8 image, got %s %s" % (img.dtype, img.shape))
+    _write_png_rows(path, img, img.shape[1], img.shape[0], 8, 6)
+
+
+def write_png_gray16(path, image_u16):
+    """A 16-bit greyscale PNG of a [H,W] uint16 image (big-endian samples): depth_N.png of the training views."""
+    img = np.ascontiguousarray(image_u16.detach().cpu().numpy() if isinstance(image_u16, torch.Tensor) else image_u16)
+    if img.dtype != np.uint16 or img.ndim != 2:
+        raise ValueError("write_png_gray16: need a [H,W] uint16 image, got %s %s" % (img.dtype, img.shape))
+    _write_png_rows(path, img.astype(">u2"), img.shape[1], img.shape[0], 16, 0)
+
+
+def read_png_any(path):
+    """The image of a PNG that write_png, write_png_rgba or write_png_gray16 wrote (filter 0 rows): [H,W,3] or [H,W,4]
+    uint8, or [H,W] uint16."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError("read_png_any: %s is not a PNG" % path)
+    pos, idat, w, h, kind = 8, b"", 0, 0, None
+    while pos < len(data):
+        n, tag = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + n]
+        if tag == b"IHDR":
+            w, h, depth, ctype = struct.unpack(">IIBB", body[:10])
+            kind = _PNG_KINDS.get((depth, ctype))
+            if kind is None:
+                raise ValueError("read_png_any: %s is not 8-bit RGB / RGBA or 16-bit grey" % path)
+        elif tag == b"IDAT":
+            idat += body
+        pos += 12 + n
+    dtype, channels = kind
+    stride = w * channels * dtype.itemsize
+    rows = np.frombuffer(zlib.decompress(idat), dtype=np.uint8).reshape(h, 1 + stride)
+    if (rows[:, 0] != 0).any():
+        raise ValueError("read_png_any: %s uses PNG row filters" % path)
+    px = np.ascontiguousarray(rows[:, 1:]).view(dtype).reshape((h, w, channels) if channels > 1 else (h, w))
+    return px.astype(np.uint16 if dtype.itemsize == 2 else np.uint8)
