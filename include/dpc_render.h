@@ -548,6 +548,7 @@ int dpc_render_points(const double* points, const float* colors, const double* r
  *
  * Deliberate deviations from the archive's Blender renders: flat shading by a headlight instead of Blender's lamps and
  * smooth normals; diffuse colour only (no textures, no transparency); a box filter over a regular sample grid.
+ * dpc_render_meshes_shaded below adds the models' textures and smooth normals.
  *
  * Arguments: verts [n_verts,3] float64, faces [n_faces,3] int32 (vertex indices local to the mesh), face_mat [n_faces] int32
  * (local to the mesh's materials), kd [n_mats,3] float64 (all DEVICE); mesh m is the row meshes[m] (DEVICE) =
@@ -571,6 +572,63 @@ int dpc_render_meshes(const double* verts, int n_verts, const int32_t* faces, co
                       const int32_t* view_mesh, const int32_t* host_view_mesh, const double* view_cam, int views,
                       int image_size, int supersample, uint8_t* rgba, uint16_t* depth, int32_t* face_id,
                       int32_t* status, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * The same views with the models' own textures (map_Kd) and smooth vertex normals (vn): dpc_render_meshes with
+ * per-corner attributes interpolated perspective-correctly over the winning face of every sample.  Camera, samples,
+ * coverage, depth, the visible face, the guards, the pixel filter, depth px and face_id are dpc_render_meshes's, by the
+ * same code: for the same meshes and cameras depth, face_id and the alpha channel are its bytes.  Only the colour of a
+ * covered sample differs.  For the sample's winning face, with e_k, A and w_k as above:
+ *
+ *   weights  g_k = (e_k / A) w_k,   d = 1 / ((g_0 + g_1) + g_2)  (the sample's fp64 depth),   c_k = g_k d.
+ *   texture  the face is textured when mat_tex[material] >= 0 and its three face_uv entries are >= 0.  Then
+ *              u = (c_0 u_0 + c_1 u_1) + c_2 u_2,   v likewise,   fu = u - floor(u),   fv = v - floor(v)   (repeat),
+ *              x = fu Wt - 0.5,   y = (1 - fv) Ht - 0.5   (row 0 of the image is the top of the texture, v = 1),
+ *              x0 = floor(x), ax = x - x0, bx = 1 - ax;   y0 = floor(y), ay = y - y0, by = 1 - ay,
+ *            the integer columns x0, x0 + 1 and rows y0, y0 + 1 wrapped modulo Wt and Ht, a texel T = byte / 255.0, and
+ *              rgb = (T[y0][x0] bx + T[y0][x0 + 1] ax) by + (T[y0 + 1][x0] bx + T[y0 + 1][x0 + 1] ax) ay
+ *            per channel takes the place of Kd[material].  No colour-space conversion, no alpha, no map_d, no
+ *            mip-mapping.  An untextured face, and a sample whose u or v is not finite, use Kd[material].
+ *   normals  when the face's three face_vn entries are >= 0: m_k = R vn_k ((R_q0 p_0 + R_q1 p_1) + R_q2 p_2, not
+ *            normalised), n = (c_0 m_0 + c_1 m_1) + c_2 m_2 per component, |n| = sqrt((n_0^2 + n_1^2) + n_2^2) and
+ *            shade = DPC_MESH_AMBIENT + DPC_MESH_DIFFUSE (|n_0| / |n|).  When |n| is zero or not finite, or the face
+ *            lacks a normal at a corner, shade is dpc_render_meshes's face-normal shade.
+ *   colour   the sample's colour is rgb shade (one product per channel); pixels as in dpc_render_meshes.
+ *   guards   besides dpc_render_meshes's: a face_uv or face_vn entry below -1 or outside the mesh's range, or a
+ *            mat_tex of the face's material below -1 or outside the mesh's textures, is DPC_STATUS_BAD_INDEX; a uv or a
+ *            normal that the face names (entry >= 0) and that is not finite is DPC_STATUS_NONFINITE; the face is skipped
+ *            whole.  None of these values becomes an address; texel addresses come from the wrapped integers alone.
+ * Every product, sum, division, floor and sqrt is one rounded fp64 operation (-ffp-contract=off).
+ *
+ * Remaining deviations from the archive's Blender renders: a headlight only; no shadows or specular term; no
+ * transparency; no mip-mapping; no colour management; a box filter over a regular sample grid.
+ *
+ * Arguments: dpc_render_meshes's, and uv [n_uv,2] float64, face_uv [n_faces,3] int32 (local to the mesh's uvs, -1: none),
+ * normals [n_vn,3] float64, face_vn [n_faces,3] int32 (local, -1: none), mat_tex [n_mats] int32 (the material's texture,
+ * local to the mesh's textures, -1: none), texels: n_texel_bytes uint8 of packed RGB rows (all DEVICE); texture t is the
+ * row tex[t] (DEVICE) = host_tex[t] (HOST) of 3 int64: (byte offset of its first texel, width, height), offsets beyond
+ * 2^31 allowed.  A mesh row has 12 int32: dpc_render_meshes's 6, then (uv start, count, normal start, count, texture
+ * start, count).  face_uv NULL switches textures off (uv, mat_tex, tex and texels are then not read), face_vn NULL smooth
+ * normals; with both NULL, or with every face_uv, face_vn or mat_tex entry -1, the output is dpc_render_meshes's byte for
+ * byte.  workspace: dpc_render_meshes_shaded_workspace_bytes(host_meshes (rows of 12), M, host_view_mesh, W) bytes, the
+ * same figure as dpc_render_meshes's: attributes are fetched per face where a pixel is shaded.  No floating-point
+ * atomics, no allocation, no host synchronisation and no host -> device copy.  DPC_ERR_SHAPE, before any launch, for
+ * everything dpc_render_meshes refuses, and for n_uv, n_vn, n_tex or n_texel_bytes < 0, 2 n_uv or 3 n_vn > 2^31 - 1, a
+ * uv, normal or texture range outside its buffer, a texture with a negative offset, a side outside [1, 65536] or
+ * 3 width height bytes that do not fit between its offset and n_texel_bytes.  With valid arguments and NULL device
+ * pointers it returns DPC_ERR_NULL without touching a device; so it does when face_uv is given without the mat_tex, uv,
+ * tex or texels it needs, or face_vn without normals.  Added without a new ABI number.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_render_meshes_shaded_workspace_bytes(const int32_t* host_meshes, int n_meshes, const int32_t* host_view_mesh,
+                                                int views);
+int dpc_render_meshes_shaded(const double* verts, int n_verts, const int32_t* faces, const int32_t* face_mat, int n_faces,
+                             const double* kd, int n_mats, const double* uv, int n_uv, const int32_t* face_uv,
+                             const double* normals, int n_vn, const int32_t* face_vn, const int32_t* mat_tex,
+                             const uint8_t* texels, int64_t n_texel_bytes, const int64_t* tex, const int64_t* host_tex,
+                             int n_tex, const int32_t* meshes, const int32_t* host_meshes, int n_meshes,
+                             const int32_t* view_mesh, const int32_t* host_view_mesh, const double* view_cam, int views,
+                             int image_size, int supersample, uint8_t* rgba, uint16_t* depth, int32_t* face_id,
+                             int32_t* status, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Opt-in measurement aid (nothing in the reference corresponds to it).  After dpc_profile_enable(capacity)

@@ -27,8 +27,8 @@ from .downsample import downsample_split, voxel_down_sample  # noqa: F401
 from .densify import MeshError, densify_meshes, densify_split, load_obj_mesh  # noqa: F401
 from .visualise import (camera_frame, read_png_any, render_point_cloud, render_point_clouds, render_split, write_png,  # noqa: F401
                         write_png_gray16, write_png_rgba)
-from .meshviews import (camera_extrinsic, features_of_views, load_obj_scene, render_mesh_views, render_training_views,  # noqa: F401
-                        sample_camera_positions, view_rotation, view_transform)
+from .meshviews import (ShadedScene, camera_extrinsic, features_of_views, load_obj_scene, load_obj_scene_shaded,  # noqa: F401
+                        render_mesh_views, render_training_views, sample_camera_positions, view_rotation, view_transform)
 
 __all__ = [
     "pointcloud_project_fast", "pointcloud_project", "pc_perspective_transform", "pointcloud2voxels3d_fast",
@@ -45,7 +45,7 @@ __all__ = [
     "camera_frame", "render_point_clouds", "render_point_cloud", "render_split", "write_png",
     "write_png_rgba", "write_png_gray16", "read_png_any",
     "load_obj_scene", "sample_camera_positions", "view_rotation", "view_transform", "render_mesh_views", "camera_extrinsic",
-    "features_of_views", "render_training_views",
+    "features_of_views", "render_training_views", "load_obj_scene_shaded", "ShadedScene",
 ]
 
 

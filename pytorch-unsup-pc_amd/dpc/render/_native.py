@@ -85,6 +85,9 @@ _FUNCTIONS = (
     ("dpc_render_points", _i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _d, _d] + [_vp] * 4),
     ("dpc_render_meshes_workspace_bytes", _sz, [_vp, _i, _vp, _i]),
     ("dpc_render_meshes", _i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i] + [_vp] * 6),
+    ("dpc_render_meshes_shaded_workspace_bytes", _sz, [_vp, _i, _vp, _i]),
+    ("dpc_render_meshes_shaded", _i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _vp, _i,
+                                      _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i] + [_vp] * 6),
     ("dpc_profile_enable", _i, [_i]),
     ("dpc_profile_disable", _i, None),
     ("dpc_profile_count", _i, None),

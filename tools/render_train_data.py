@@ -4,7 +4,8 @@
 
     python tools/render_train_data.py --shapenet_path=ShapeNetCore.v1 --synth_set=03001627 --subset=train \\
                                       --out_dir=renders [--num_views=5] [--image_size=128] [--seed=0] \\
-                                      [--write_features=DIR] [--shapenet_v2] [--supersample=3] [--models_per_call=64]
+                                      [--write_features=DIR] [--shapenet_v2] [--supersample=3] [--models_per_call=64] \\
+                                      [--textures] [--smooth_normals]
 
 Reads the model names from splits/<synth_set>_<subset>.txt (relative to the working directory, as the reference does)
 and each mesh from <shapenet_path>/<synth_set>/<model>/model.obj (models/model_normalized.obj with --shapenet_v2), with
@@ -14,7 +15,10 @@ reference's dpc/run/create_data_torch.py runs on it unchanged.  With --write_fea
 DIR/<model>_features.p itself (image, mask, name, extrinsic, cam_pos, depth at --image_size; no resize).  Camera
 positions are drawn by dpc.render.sample_camera_positions from --seed and the model's place in the split (its ranges
 are an assumption: the archive's are not recorded), so a rerun draws the same views.  Models whose outputs all exist are
-skipped; a model that cannot be read or rendered is reported and skipped, and the others go on."""
+skipped; a model that cannot be read or rendered is reported and skipped, and the others go on.  --textures uses the
+models' map_Kd images where faces have texture coordinates, --smooth_normals their vn normals (both off by default: flat
+facets in each material's diffuse colour); an image that cannot be read leaves its material untextured and is listed
+per model under "warnings" in the summary."""
 import argparse
 import os
 import pickle
@@ -41,15 +45,18 @@ def parse_arguments(argv):
     parser.add_argument("--models_per_call", type=int, default=64)
     parser.add_argument("--camera_distance", type=float, default=2.0)
     parser.add_argument("--focal_length", type=float, default=1.875)
+    parser.add_argument("--textures", action="store_true")
+    parser.add_argument("--smooth_normals", action="store_true")
     return parser.parse_args(argv)
 
 
 def main(argv=None):
-    """Returns {"written": [names], "skipped": [names], "failed": {name: message}}."""
+    """Returns {"written": [names], "skipped": [names], "failed": {name: message}}, with --textures or --smooth_normals
+    also "warnings": {name: [messages]} for the models whose loading left any."""
     import scipy.io
 
-    from dpc.render import (camera_extrinsic, features_of_views, load_obj_scene, render_training_views,
-                            sample_camera_positions, write_png_gray16, write_png_rgba)
+    from dpc.render import (camera_extrinsic, features_of_views, load_obj_scene, load_obj_scene_shaded,
+                            render_training_views, sample_camera_positions, write_png_gray16, write_png_rgba)
 
     cfg = parse_arguments(sys.argv[1:] if argv is None else argv)
     if cfg.num_views < 1:
@@ -77,8 +84,17 @@ def main(argv=None):
     positions = sample_camera_positions(len(models), cfg.num_views, cfg.seed)   # by place in the split: stable across reruns
     cam_pos = {n: positions[i] for i, n in enumerate(models)}
 
+    shaded = cfg.textures or cfg.smooth_normals
+    warnings = {}
+
     def load_scene(name):
-        return load_obj_scene(os.path.join(cfg.shapenet_path, cfg.synth_set, name, model_file))
+        path = os.path.join(cfg.shapenet_path, cfg.synth_set, name, model_file)
+        if not shaded:
+            return load_obj_scene(path)
+        scene = load_obj_scene_shaded(path)
+        if scene.warnings:
+            warnings[name] = list(scene.warnings)
+        return scene
 
     def save(name, rgba, depth, pos):
         os.makedirs(os.path.join(out_dir, name), exist_ok=True)
@@ -97,10 +113,16 @@ def main(argv=None):
     written, failed = [], {}
     render_training_views(todo, load_scene, cam_pos, save, cfg.models_per_call, errors=failed, keep=False,
                           image_size=cfg.image_size, supersample=cfg.supersample, camera_distance=cfg.camera_distance,
-                          focal_length=cfg.focal_length)
+                          focal_length=cfg.focal_length, textures=cfg.textures, smooth_normals=cfg.smooth_normals)
     for name, msg in failed.items():
         print("failed", name, msg)
-    return {"written": written, "skipped": skipped, "failed": failed}
+    summary = {"written": written, "skipped": skipped, "failed": failed}
+    if shaded:
+        for name, lines in warnings.items():
+            for line in lines:
+                print("warning", name, line)
+        summary["warnings"] = warnings
+    return summary
 
 
 if __name__ == "__main__":
