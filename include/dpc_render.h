@@ -383,6 +383,47 @@ int dpc_nearest_batched(const void* pts, int n_pts, int is_f64, const int32_t* p
                         int pairs, double* mean, void* min_dist, int64_t* idx, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Chamfer loss: the backward of dpc_nearest_batched, and the means of squared distances.  The reference's
+ * point_cloud_distance (dpc/util/point_cloud_distance.py:25-40) is plain torch code and differentiates under autograd;
+ * this is its gradient in closed form for P directed pairs at once, with nothing of size Ns x Nt materialised.
+ *
+ * dpc_nearest_batched_bwd: pts, n_pts, is_f64, pair_desc, host_pair_desc, pairs as in the forward; min_dist, idx
+ * [sum src_count] are the forward's outputs for the same points and table.  Upstream gradients: gmean [P] float64 | NULL
+ * (of the means) and gdist [sum src_count] in the compute type | NULL (of the per-point values); NULL counts as zeros.
+ * For source point i of pair p, with s its coordinates, t = target idx[i] of the pair, d = min_dist[i], n_p = src_count:
+ *   weight         w = gdist[i] + gmean[p] / n_p, formed in fp64 and rounded once to the compute type;
+ *   distance mode  (squared == 0) the target receives c = ((t - s) / d) * w per component and the source -c: one
+ *                  subtraction, one IEEE divide, one multiply, no FMA contraction;
+ *   d == 0         (coincident points) the reference's autograd yields NaN (inf * 0).  DELIBERATE DEVIATION: c is exactly
+ *                  zero here, for source and target, so a cloud compared with itself has a finite, zero gradient;
+ *   squared mode   (squared != 0) the per-point value is d * d (rounded once; its means: dpc_chamfer_pair_means); the
+ *                  target receives c = (2 w) * (t - s) and the source -c.  There is no division; min_dist may be NULL;
+ *   ties           exact and near ties follow the forward's idx, as the reference's indexing does.
+ * dpts [n_pts,3] in the compute type; EVERY row is written, a point in no pair gets zero.  The gradient of packed point
+ * x is summed in a fixed order: per pair, the terms x receives as a target are added in ascending source position onto
+ * 0.0 (a target nobody chose: +0.0); then, pairs ascending, onto 0.0: the pair's source-role term of x, then the pair's
+ * target-role sum of x.  A point may be a source in one pair and a target in others (views share one GT copy; ranges
+ * may overlap).  No floating-point atomics: two identical calls are bit-identical, and a pair's contribution does not
+ * depend on the other pairs of the call.  The per-pair prefixes are built on the device from pair_desc: no host
+ * synchronisation, no host -> device copy, capturable into a hipGraph.  An idx outside [0, tgt_count) (never the
+ * forward's own) reads nothing and yields NaN.  DPC_ERR_SHAPE, before any launch, for every table dpc_nearest_batched
+ * refuses, and for more than 2^31 - 1 target points summed over the pairs.  With a valid table and NULL device
+ * pointers the call returns DPC_ERR_NULL without touching a device.  workspace:
+ * dpc_chamfer_bwd_workspace_bytes(pairs, host_pair_desc, is_f64) bytes (0 when the table is invalid or pairs <= 0).
+ *
+ * dpc_chamfer_pair_means: mean[p] = np.mean, as float64, of the src_count values of pair p in `values` ([sum src_count]
+ * in the compute type, packed in pair order), by the summation kernels of dpc_nearest_batched (numpy's order, NaN for an
+ * empty pair).  Only the counts of the table are used; the same refusals; workspace: dpc_chamfer_workspace_bytes.
+ * Added without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_chamfer_bwd_workspace_bytes(int pairs, const int32_t* host_pair_desc, int is_f64);
+int dpc_nearest_batched_bwd(const void* pts, int n_pts, int is_f64, const int32_t* pair_desc, const int32_t* host_pair_desc,
+                            int pairs, const void* min_dist, const int64_t* idx, const double* gmean, const void* gdist,
+                            int squared, void* dpts, void* workspace, void* stream);
+int dpc_chamfer_pair_means(const void* values, int is_f64, const int32_t* pair_desc, const int32_t* host_pair_desc, int pairs,
+                           double* mean, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Voxel-grid downsampling of ground-truth clouds (densify/downsample_gt.py:47-57: open3d.voxel_down_sample(pcd,
  * voxel_size) per model) for C clouds in one call.  open3d's PointCloud::VoxelDownSample (0.7 - 0.9, the same body in each),
  * restated from its C++ source for one cloud p[0..n), all in fp64 (float32 input is widened exactly first):

@@ -14,6 +14,8 @@
 //   k_chamfer_mean     one lane per pair: adds the chunk sums in order onto 0.0 and divides by src_count in fp64.
 // The last two reproduce np.mean of the float64 distances bit for bit (numpy 2.x's np.add.reduce: buffers of 8192
 // elements summed with pairwise_sum, buffer sums added left to right; tests/test_chamfer_host.py pins that order).
+// dpc_chamfer_pair_means runs the scan and the last two alone over values the caller packed (the squared distances of the
+// Chamfer loss, whose backward is dpc_chamfer_bwd.hip).
 // Compute-bound on the fp32 / fp64 vector pipe in k_chamfer_partial: sum over pairs of src_count x tgt_count d2s.
 #include <hip/hip_runtime.h>
 
@@ -299,6 +301,23 @@ int chamfer_impl(const T* pts, const int32_t* desc, const ChGeom& g, int pairs, 
   return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
 }
 
+// The mean stage alone, over values the caller packed in pair order (the squared distances of the Chamfer loss).
+template <class T>
+int chamfer_means_impl(const T* values, const int32_t* desc, const ChGeom& g, int pairs, double* mean, void* workspace,
+                       hipStream_t st) {
+  ChWork w;
+  chamfer_carve(g, pairs, sizeof(T), static_cast<char*>(workspace), &w);
+  constexpr bool kIsF64 = sizeof(T) == sizeof(double);
+  DPC_LAUNCH("k_chamfer_scan", dpc_kid("k_chamfer_scan"), k_chamfer_scan, dim3(1), dim3(kChScanThreads), 0, st, desc, pairs,
+             g.slice, w.pre);
+  if (g.chunks > 0)
+    DPC_LAUNCH("k_chamfer_chunks", dpc_kid(kIsF64 ? "k_chamfer_chunks<double>" : "k_chamfer_chunks<float>"),
+               k_chamfer_chunks<T>, dim3((unsigned)g.chunks), dim3(64), 0, st, pairs, w.pre, values, w.chunk_sum);
+  DPC_LAUNCH("k_chamfer_mean", dpc_kid("k_chamfer_mean"), k_chamfer_mean, dim3((pairs + 63) / 64), dim3(64), 0, st, pairs,
+             w.pre, (const double*)w.chunk_sum, mean);
+  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+}
+
 }  // namespace
 
 extern "C" {
@@ -325,6 +344,20 @@ int dpc_nearest_batched(const void* pts, int n_pts, int is_f64, const int32_t* p
                                 idx, workspace, st);
   return chamfer_impl<float>(static_cast<const float*>(pts), pair_desc, g, pairs, mean, static_cast<float*>(min_dist), idx,
                              workspace, st);
+}
+
+int dpc_chamfer_pair_means(const void* values, int is_f64, const int32_t* pair_desc, const int32_t* host_pair_desc, int pairs,
+                           double* mean, void* workspace, void* stream) {
+  if (pairs < 0) return DPC_ERR_SHAPE;
+  if (pairs == 0) return DPC_OK;
+  if (!host_pair_desc) return DPC_ERR_NULL;
+  const int rc = chamfer_check(pairs, host_pair_desc, -1);
+  if (rc != DPC_OK) return rc;
+  const ChGeom g = chamfer_geometry(pairs, host_pair_desc);
+  if (!pair_desc || !mean || !workspace || (g.points > 0 && !values)) return DPC_ERR_NULL;
+  hipStream_t st = (hipStream_t)stream;
+  if (is_f64) return chamfer_means_impl<double>(static_cast<const double*>(values), pair_desc, g, pairs, mean, workspace, st);
+  return chamfer_means_impl<float>(static_cast<const float*>(values), pair_desc, g, pairs, mean, workspace, st);
 }
 
 }  // extern "C"

@@ -22,7 +22,7 @@ from ._ops import (DeviceSchedule, Drc, Geometry, ProjectFused, ProjectLossFused
 from .predictions import chamfer_of_predictions, load_predictions, save_predictions  # noqa: F401
 from .alignment import (alignment_candidates, alignment_to_ground_truth, as_rotation_matrix, from_rotation_matrix,  # noqa: F401
                         icp_point_to_point, pose_errors, quat_w_avg_markley, quaternion_from_campos, reference_rotation)
-from .chamfer import chamfer_batched, chamfer_of_split, eval_chamfer, nearest_batched  # noqa: F401
+from .chamfer import chamfer_batched, chamfer_loss, chamfer_of_split, eval_chamfer, nearest_batched  # noqa: F401
 from .downsample import downsample_split, voxel_down_sample  # noqa: F401
 from .densify import MeshError, densify_meshes, densify_split, load_obj_mesh  # noqa: F401
 from .visualise import (camera_frame, read_png_any, render_point_cloud, render_point_clouds, render_split, write_png,  # noqa: F401
@@ -40,7 +40,7 @@ __all__ = [
     "DeviceSchedule", "check_status", "set_debug_checks", "taps_bucket", "project_loss_step",
     "icp_point_to_point", "alignment_to_ground_truth", "alignment_candidates", "reference_rotation", "quat_w_avg_markley",
     "quaternion_from_campos", "as_rotation_matrix", "from_rotation_matrix", "pose_errors",
-    "nearest_batched", "chamfer_batched", "chamfer_of_split", "eval_chamfer", "voxel_down_sample", "downsample_split",
+    "nearest_batched", "chamfer_batched", "chamfer_loss", "chamfer_of_split", "eval_chamfer", "voxel_down_sample", "downsample_split",
     "load_obj_mesh", "densify_meshes", "densify_split", "MeshError",
     "camera_frame", "render_point_clouds", "render_point_cloud", "render_split", "write_png",
     "write_png_rgba", "write_png_gray16", "read_png_any",
@@ -670,7 +670,10 @@ def point_cloud_distance(Vs, Vt):
     """For each point of Vs [Ns,3] the closest point of Vt [Nt,3] (point_cloud_distance.py:25-40).
 
     Returns (proj [Ns,3] = Vt[idx], minDist [Ns], idx [Ns] int64) like the reference; fp32 or fp64 after the inputs.
-    Nothing of size Ns x Nt is materialised.  No gradient (the reference only evaluates with it)."""
+    Nothing of size Ns x Nt is materialised.  When Vs or Vt requires grad, minDist and proj carry gradient as the
+    reference's do under autograd (minDist through dpc_nearest_batched_bwd as a one-pair call, proj through torch's
+    indexing), with the same values as without; where a source point coincides with its nearest target the reference's
+    gradient is NaN and this one is exactly zero (include/dpc_render.h)."""
     dev = _native.require_device(Vs, Vt)
     if Vs.dim() != 2 or Vt.dim() != 2 or Vs.shape[1] != 3 or Vt.shape[1] != 3:
         raise ValueError("point_cloud_distance expects [Ns,3] and [Nt,3], got %s and %s" % (tuple(Vs.shape), tuple(Vt.shape)))
@@ -679,6 +682,10 @@ def point_cloud_distance(Vs, Vt):
     ns, nt = vs.shape[0], vt.shape[0]
     if nt == 0 and ns > 0:
         raise IndexError("point_cloud_distance: empty target cloud (argmin of an empty sequence)")
+    if torch.is_grad_enabled() and (Vs.requires_grad or Vt.requires_grad):
+        vt = Vt.to(dtype)
+        _, dist, idx = nearest_batched(torch.cat([vt, Vs.to(dtype)]), [[nt, ns, 0, nt]], return_distances=True)
+        return vt[idx], dist, idx
     L = _native.lib()
     is64 = int(dtype == torch.float64)
     proj = torch.empty((ns, 3), dtype=dtype, device=dev)

@@ -78,6 +78,9 @@ _FUNCTIONS = (
     ("dpc_icp_point_to_point", _i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _d, _i, _d, _d] + [_vp] * 6),
     ("dpc_chamfer_workspace_bytes", _sz, [_i, _vp, _i]),
     ("dpc_nearest_batched", _i, [_vp, _i, _i, _vp, _vp, _i] + [_vp] * 5),
+    ("dpc_chamfer_bwd_workspace_bytes", _sz, [_i, _vp, _i]),
+    ("dpc_nearest_batched_bwd", _i, [_vp, _i, _i, _vp, _vp, _i] + [_vp] * 4 + [_i] + [_vp] * 3),
+    ("dpc_chamfer_pair_means", _i, [_vp, _i, _vp, _vp, _i] + [_vp] * 3),
     ("dpc_downsample_workspace_bytes", _sz, [_i, _i]),
     ("dpc_voxel_downsample", _i, [_vp, _i, _i, _vp, _vp, _i, _d] + [_vp] * 6),
     ("dpc_densify_workspace_bytes", _sz, [_i, _i64, _i64, _i64, _i]),

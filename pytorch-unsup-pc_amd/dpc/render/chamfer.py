@@ -7,6 +7,8 @@ in numpy's float64 order, so every number equals the reference's own compute_dis
 
     nearest_batched   the thin wrapper over the C ABI: packed points, a [P,4] pair table, [P] float64 means
     chamfer_batched   (mean pred -> gt, mean gt -> pred) for lists of clouds, [P,2] float64
+    chamfer_loss      the same two means as a differentiable loss (optionally of squared distances): gradients reach
+                      every prediction and GT cloud that requires them (csrc/dpc_chamfer_bwd.hip)
     chamfer_of_split  the reference's chamfer_dists [M,V,2] for loaded predictions and GT clouds
     eval_chamfer      run_eval's file loop: <save_dir>/<model>_pc.pkl plus a caller-supplied GT loader
 
@@ -32,15 +34,87 @@ def _pair_table(pairs):
     return _batch.table(desc, 4, "nearest_batched: pair table entries must fit int32")
 
 
-def nearest_batched(points, pairs, return_distances=False):
+def _forward(pts, desc, dev, dtype, want_points, squared):
+    """One dpc_nearest_batched call on pts (on dev, in dtype, contiguous): (means, values, min_dist, idx, device table);
+    values are the distances, or their squares (rounded once) with `squared`, whose means then come from
+    dpc_chamfer_pair_means, the same summation kernels.  Without want_points the last four are None."""
+    L = _native.lib()
+    P, n_pts = desc.shape[0], int(pts.shape[0])
+    is64 = int(dtype == torch.float64)
+    host_desc = desc.ctypes.data_as(ctypes.c_void_p)
+    total = int(desc[:, 1].astype(np.int64).sum()) if P else 0
+    mean = torch.empty((P,), dtype=torch.float64, device=dev)
+    dist = torch.empty((total,), dtype=dtype, device=dev) if want_points else None
+    idx = torch.empty((total,), dtype=torch.int64, device=dev) if want_points else None
+    val, desc_d = dist, None
+    if P:
+        desc_d = torch.from_numpy(desc).to(dev)
+        ws = _batch.workspace(L.dpc_chamfer_workspace_bytes(P, host_desc, is64), dev)
+        with torch.cuda.device(dev):
+            rc = L.dpc_nearest_batched(_native.ptr(pts), n_pts, is64, _native.ptr(desc_d), host_desc, P, _native.ptr(mean),
+                                       _native.ptr(dist), _native.ptr(idx), _native.ptr(ws), _native.stream_ptr(dev))
+            _native.check(rc, "dpc_nearest_batched")
+            if squared:
+                val = dist * dist
+                rc = L.dpc_chamfer_pair_means(_native.ptr(val), is64, _native.ptr(desc_d), host_desc, P, _native.ptr(mean),
+                                              _native.ptr(ws), _native.stream_ptr(dev))
+                _native.check(rc, "dpc_chamfer_pair_means")
+    elif squared:
+        val = dist * dist
+    return mean, val, dist, idx, desc_d
+
+
+class _NearestBatched(torch.autograd.Function):
+    """nearest_batched with a gradient: the forward keeps the packed points, the table and its own min_dist / idx, the
+    backward is one dpc_nearest_batched_bwd call (csrc/dpc_chamfer_bwd.hip)."""
+
+    @staticmethod
+    def forward(ctx, points, desc, dev, dtype, squared):
+        pts = points.detach().to(device=dev, dtype=dtype).contiguous()
+        mean, val, dist, idx, desc_d = _forward(pts, desc, dev, dtype, True, squared)
+        ctx.save_for_backward(pts, dist, idx)
+        ctx.desc, ctx.desc_d, ctx.squared, ctx.like = desc, desc_d, bool(squared), (points.device, points.dtype)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(idx)
+        return mean, val, idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gmean, gval, _gidx):
+        pts, dist, idx = ctx.saved_tensors
+        desc, dev, dtype = ctx.desc, pts.device, pts.dtype
+        P, n_pts, is64 = desc.shape[0], int(pts.shape[0]), int(pts.dtype == torch.float64)
+        if P == 0 or (gmean is None and gval is None):
+            dpts = torch.zeros_like(pts)
+        else:
+            L = _native.lib()
+            host_desc = desc.ctypes.data_as(ctypes.c_void_p)
+            gmean = None if gmean is None else gmean.to(device=dev, dtype=torch.float64).contiguous()
+            gval = None if gval is None else gval.to(device=dev, dtype=dtype).contiguous()
+            dpts = torch.empty_like(pts)
+            ws = _batch.workspace(L.dpc_chamfer_bwd_workspace_bytes(P, host_desc, is64), dev)
+            with torch.cuda.device(dev):
+                rc = L.dpc_nearest_batched_bwd(_native.ptr(pts), n_pts, is64, _native.ptr(ctx.desc_d), host_desc, P,
+                                               _native.ptr(dist), _native.ptr(idx), _native.ptr(gmean), _native.ptr(gval),
+                                               int(ctx.squared), _native.ptr(dpts), _native.ptr(ws), _native.stream_ptr(dev))
+            _native.check(rc, "dpc_nearest_batched_bwd")
+        return dpts.to(device=ctx.like[0], dtype=ctx.like[1]), None, None, None, None
+
+
+def nearest_batched(points, pairs, return_distances=False, squared=False):
     """Nearest-target distances of P directed pairs over one packed cloud buffer, with per-pair float64 means.
 
     points: [n,3] tensor (or array) holding every cloud; pairs: [P,4] rows (src_start, src_count, tgt_start, tgt_count)
     indexing it.  Pair p's distances are exactly point_cloud_distance(points[src], points[tgt])[1] and its mean is
     np.mean of them as float64, bit for bit (NaN when src_count == 0).  fp64 arithmetic when points is fp64, fp32
     otherwise (as point_cloud_distance).  Returns means [P] float64 on the device, or (means, min_dist [sum src_count],
-    idx [sum src_count] int64) with return_distances, the distances packed in pair order.  A bad table raises ValueError
-    before anything is launched."""
+    idx [sum src_count] int64) with return_distances, the distances packed in pair order.  With squared, the per-point
+    values are the squared distances (d * d, rounded once) and the means are theirs, in the same summation order.  A bad
+    table raises ValueError before anything is launched.
+
+    When points requires grad, the means and the per-point values carry gradient (dpc_nearest_batched_bwd; idx does
+    not), which arrives in the dtype of points.  The gradient follows idx through ties; where a source coincides with
+    its target (distance 0) the reference's autograd gives NaN and this gives exactly zero (include/dpc_render.h)."""
     desc = _pair_table(pairs)
     P = desc.shape[0]
     L = _native.lib()
@@ -54,20 +128,15 @@ def nearest_batched(points, pairs, return_distances=False):
                    "an empty target for a non-empty source, or more than 2^31 - 1 output points)" % n_pts)
     dev = _batch.device(_WHAT, [pts])
     dtype = torch.float64 if pts.dtype == torch.float64 else torch.float32
+    if isinstance(points, torch.Tensor) and points.requires_grad and torch.is_grad_enabled():
+        _batch.dry_run(L.dpc_nearest_batched_bwd(None, n_pts, 0, None, host_desc, P, None, None, None, None, 0, None, None,
+                                                 None),
+                       "nearest_batched: more than 2^31 - 1 target points over the pairs of a differentiable call")
+        mean, val, idx = _NearestBatched.apply(points, desc, dev, dtype, bool(squared))
+        return (mean, val, idx) if return_distances else mean
     pts = pts.to(device=dev, dtype=dtype).contiguous()
-    is64 = int(dtype == torch.float64)
-    total = int(desc[:, 1].astype(np.int64).sum()) if P else 0
-    mean = torch.empty((P,), dtype=torch.float64, device=dev)
-    dist = torch.empty((total,), dtype=dtype, device=dev) if return_distances else None
-    idx = torch.empty((total,), dtype=torch.int64, device=dev) if return_distances else None
-    if P:
-        desc_d = torch.from_numpy(desc).to(dev)
-        ws = _batch.workspace(L.dpc_chamfer_workspace_bytes(P, host_desc, is64), dev)
-        with torch.cuda.device(dev):
-            rc = L.dpc_nearest_batched(_native.ptr(pts), n_pts, is64, _native.ptr(desc_d), host_desc, P, _native.ptr(mean),
-                                       _native.ptr(dist), _native.ptr(idx), _native.ptr(ws), _native.stream_ptr(dev))
-        _native.check(rc, "dpc_nearest_batched")
-    return (mean, dist, idx) if return_distances else mean
+    mean, val, _, idx, _ = _forward(pts, desc, dev, dtype, return_distances or squared, squared)
+    return (mean, val, idx) if return_distances else mean
 
 
 def chamfer_batched(preds, gts, gt_of=None):
@@ -126,6 +195,75 @@ def _chamfer_group(preds, gts, gt_of, dev, dtype):
     if start[-1] > _batch.INT32_MAX:
         raise ValueError("chamfer_batched: more than 2^31 - 1 points in one call")
     return nearest_batched(packed, desc).view(len(preds), 2)
+
+
+def _loss_clouds(x, what):
+    """x as a list of [n,3] float32 / float64 tensors that keep their autograd history: a [B,N,3] tensor gives its B
+    rows, a list gives its entries (arrays wrapped; other dtypes converted to float32)."""
+    if isinstance(x, torch.Tensor) and x.dim() == 3:
+        x = x.unbind(0)
+    out = []
+    for i, c in enumerate(x):
+        t = c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c))
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("chamfer_loss: %s[%d] must be [n,3], got %s" % (what, i, tuple(t.shape)))
+        out.append(t if t.dtype in (torch.float32, torch.float64) else t.to(torch.float32))
+    return out
+
+
+def chamfer_loss(preds, gts, gt_of=None, squared=False):
+    """chamfer_batched as a loss: [P,2] float64 (mean pred -> gt, mean gt -> pred) on the device, carrying gradient to
+    every prediction and GT cloud that requires it.  squared: means of the squared distances instead.
+
+    preds, gts: lists of [n,3] tensors or arrays, or [B,N,3] tensors; gt_of as in chamfer_batched (views of one model
+    share one GT copy, whose gradient sums over them).  The per-pair fp32 / fp64 rule is chamfer_batched's.  The clouds
+    are packed with torch.cat, so autograd carries the packed gradient of dpc_nearest_batched_bwd back to the inputs.
+    No host synchronisation and no finiteness check: a NaN or inf coordinate gives non-finite output, as in torch.  The
+    values equal chamfer_batched's bit for bit (without squared).  Where a point coincides with its nearest neighbour the
+    gradient of the distance is defined as zero (the reference's autograd: NaN); see include/dpc_render.h.  An empty GT
+    for a non-empty prediction raises ValueError."""
+    P_list, G_list = _loss_clouds(preds, "preds"), _loss_clouds(gts, "gts")
+    P = len(P_list)
+    if gt_of is None:
+        if len(G_list) != P:
+            raise ValueError("chamfer_loss: %d predictions and %d GT clouds need gt_of" % (P, len(G_list)))
+        gt_of = range(P)
+    gt_of = list(gt_of)
+    if len(gt_of) != P or any(not isinstance(k, (int, np.integer)) or k < 0 or k >= len(G_list) for k in gt_of):
+        raise ValueError("chamfer_loss: gt_of must map each of the %d predictions to one of %d GT clouds" % (P, len(G_list)))
+    gt_of = [int(k) for k in gt_of]
+    for i, k in enumerate(gt_of):
+        if len(G_list[k]) == 0 and len(P_list[i]) > 0:
+            raise ValueError("chamfer_loss: GT cloud %d is empty but prediction %d is not (argmin of an empty set)" % (k, i))
+    dev = _batch.device(_WHAT, P_list, G_list)
+    if P == 0:
+        return torch.empty((0, 2), dtype=torch.float64, device=dev)
+    f64 = [P_list[i].dtype == torch.float64 or G_list[k].dtype == torch.float64 for i, k in enumerate(gt_of)]
+    rows, order = [], []
+    for want in (False, True):
+        sel = [i for i in range(P) if f64[i] == want]
+        if not sel:
+            continue
+        dtype = torch.float64 if want else torch.float32
+        used = sorted({gt_of[i] for i in sel})
+        clouds = [G_list[k] for k in used] + [P_list[i] for i in sel]
+        start = np.cumsum([0] + [len(c) for c in clouds])
+        if start[-1] > _batch.INT32_MAX:
+            raise ValueError("chamfer_loss: more than 2^31 - 1 points in one call")
+        slot = {k: j for j, k in enumerate(used)}
+        desc = np.zeros((2 * len(sel), 4), dtype=np.int64)
+        for j, i in enumerate(sel):
+            ps, pn = start[len(used) + j], len(P_list[i])
+            gs, gn = start[slot[gt_of[i]]], len(G_list[gt_of[i]])
+            desc[2 * j] = (ps, pn, gs, gn)
+            desc[2 * j + 1] = (gs, gn, ps, pn)
+        packed = torch.cat([c.to(device=dev, dtype=dtype) for c in clouds])
+        rows.append(nearest_batched(packed, desc, squared=squared).view(len(sel), 2))
+        order += sel
+    if len(rows) == 1:
+        return rows[0]
+    inverse = np.argsort(np.asarray(order))
+    return torch.cat(rows)[torch.from_numpy(inverse).to(dev)]
 
 
 def _host_unit_quaternion(q):
