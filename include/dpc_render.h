@@ -315,6 +315,44 @@ int dpc_silhouette_loss(const float* gt, int gt_factor, const float* weights, co
                         float* loss_part, int32_t* winner, float* dpred, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Expected depth and its loss, fused (add_proj_depth_loss, dpc/util/losses.py:113-136, on drc_depth_projection,
+ * dpc/util/drc.py:145-160): from grid_wh of dpc_project_fwd (the grid after the clamp and the W, H passes) in one column
+ * kernel -- D pass, occupancy scale + clamp, DRC recurrence, depth, squared error -- instead of a smoothed grid, a
+ * [D+1,B,H,W] tensor of probabilities and a dozen elementwise passes.  Per ray (b, y, x), v_z the D-pass correlation of
+ * grid_wh[b, :, y, x] with the z taps (host_kern_z, or p->dev_taps_z when set; p->taps_z == 0: no pass):
+ *   o_z = s ? clamp(s_b v_z, 0, 1) : v_z,   y_z = clamp(o_z, eps, 1 - eps),   A_k = prod_{j<k} (1 - y_j),
+ *   p_0 = e^eps y_0,  p_k = y_k A_k,  p_D = e^eps A_D        (dpc_drc_fwd's probabilities),
+ *   depth[b, H-1-y, x] = sum_k p_k psi_k,   psi_k = k/D - 1/2 + camera_distance,  psi_D = max_depth   (rows flipped like proj).
+ * Loss, one cloud per sample (S = B):
+ *   g[s, y, x] = gt_depth[s, f*y, f*x]          TF-1 nearest-neighbour resize without align_corners, f = gt_factor >= 1;
+ *   g = max_depth where g == max_dataset_depth  when the two differ (:121-124);
+ *   loss = (1/2) sum_s w_s^2 sum_pix (g - depth)^2 / S       tf.nn.l2_loss / num_samples; w = weights [S] | NULL (= 1), squared
+ *                                                             like dpc_silhouette_loss's.  The caller applies proj_depth_weight.
+ * fwd: gt_depth [S, f*H, f*W] | NULL (projection only: depth alone is written); depth [B,H,W] | NULL; loss_tiles
+ *   [B, ceil(H*W/256)] scratch: the ray tiles' squared errors, added in tile order by a one-block second launch (no float
+ *   atomics: the loss is the same bits on every run); loss [1].
+ * bwd: recomputes the column; the gradient arriving at a ray's depth is dloss w_s^2 (depth - g) / S (dloss: device scalar |
+ *   NULL = 1; nothing when gt_depth is NULL) plus ddepth [B,H,W] | NULL (flipped like depth).  Outputs: dgrid_wh [B,D,H,W],
+ *   every element overwritten (hand it to dpc_project_bwd's dgrid_wh); ds [B] | NULL, the ray tiles' partials added in tile
+ *   order inside the launch (the same bits on every run).  One launch, nothing else is enqueued.
+ *   workspace: dpc_depth_workspace_bytes(p) bytes.  Its first 4 * B bytes are the tickets of the in-launch ds reduction:
+ *   ZERO ON ENTRY (zeroed by the caller once, when the buffer is made) and zero again when the launch has finished, so one
+ *   buffer serves any number of calls that run one after the other (one stream); calls that may overlap need a buffer each.
+ *   Only read when ds is given.  The rest is scratch and needs no initialisation.
+ * D = 32, 64, 128 with a z kernel of effective radius <= 15 run with the column in registers; every other depth or kernel
+ * length takes a generic kernel.  DPC_ERR_SHAPE, before any launch: f < 1, f*H or f*W > 1024, gt_depth without loss or
+ * loss_tiles, neither gt_depth nor depth (fwd), neither gt_depth nor ddepth (bwd).  Nothing synchronises or allocates.
+ * Added without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_depth_workspace_bytes(const DpcParams* p);
+int dpc_depth_loss_fwd(const DpcParams* p, const float* grid_wh, const float* s, const float* host_kern_z,
+                       const float* gt_depth, int gt_factor, float max_dataset_depth, const float* weights, float* depth,
+                       float* loss_tiles, float* loss, void* stream);
+int dpc_depth_loss_bwd(const DpcParams* p, const float* grid_wh, const float* s, const float* host_kern_z,
+                       const float* gt_depth, int gt_factor, float max_dataset_depth, const float* weights, const float* dloss,
+                       const float* ddepth, float* dgrid_wh, float* ds, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Evaluation side: point_cloud_distance (dpc/util/point_cloud_distance.py:25-40), the kernel of
  * the Chamfer evaluation (dpc/run/eval_chamfer_to.py:24-44).  For every source point vs[i] ([ns,3]) the nearest target
  * vt[j] ([nt,3]): idx[i] = first j minimising dist = sqrt(sum((vt[j]-vs[i])^2)) (int64, like torch.argmin),

@@ -28,12 +28,12 @@ def chair_unsupervised(**overrides):
         batch_size=8, step_size=4, variable_num_views=False, num_views_to_use=-1, saved_camera=True, saved_depth=False,
         # renderer
         vox_size=64, vox_size_z=-1, pc_gauss_kernel_size=21, pc_relative_sigma=3.0, pc_relative_sigma_end=0.2,
-        camera_distance=2.0, focal_length=1.875, drc_logsum_clip_val=1e-5, max_depth=10.0,
+        camera_distance=2.0, focal_length=1.875, drc_logsum_clip_val=1e-5, max_depth=10.0, max_dataset_depth=10.0,
         pc_fast=True, pose_quaternion=True, pc_separable_gauss_filter=True, drc_logsum=True, drc_tf_cumulative=True,
         ptn_max_projection=False, pc_rgb=False,
         # schedules, loss, optimiser
         pc_point_dropout=0.07, pc_point_dropout_scheduled=True, pc_point_dropout_exponential_schedule=False,
         pc_point_dropout_start_step=0.0, pc_point_dropout_end_step=1.0, max_number_of_steps=600000,
-        proj_weight=1.0, drc_weight=0.0, proj_depth_weight=0.0, weight_decay=0.001, learning_rate=1e-4)
+        proj_weight=1.0, drc_weight=0.0, proj_depth_weight=0.0, pc_gauss_filter_gt=False, weight_decay=0.001, learning_rate=1e-4)
     cfg.update(overrides)
     return cfg

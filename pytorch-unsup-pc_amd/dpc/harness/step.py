@@ -2,7 +2,7 @@
 
 Follows ModelPointCloud.forward / get_loss (dpc/models/model_pc_to.py:289-336, 339-408, 410-489) and the loop body
 of dpc/run/train_to.py:110-134 for the live configuration of the experiments (predict_pose, K pose candidates with a
-student, learned occupancy scale, no rgb / depth / drc losses, no translation, fixed focal length):
+student, learned occupancy scale, no rgb / drc losses, no translation, fixed focal length):
 
     images [B*V,3,S,S] -> encoder -> ids [B*V,z]; the first view's id of every object -> decoder -> points [B,N,3]
     pose FC of every image -> K candidate quaternions + 1 student quaternion per image
@@ -10,6 +10,12 @@ student, learned occupancy scale, no rgb / depth / drc losses, no translation, f
     renderer + min-of-K silhouette loss in ONE call (dpc.render.pointcloud_project_loss), which also pools the masks and
     applies the per-view weights (valid_samples, cfg.variable_num_views)
     student loss against the winning candidate, (proj + student) * proj_weight, backward, Adam
+
+Depth supervision (cfg.proj_depth_weight != 0, one pose candidate per image; add_proj_depth_loss, dpc/util/losses.py:113-136,
+called from get_loss): the renderer's projection (dpc.render.pointcloud_project_fast), the silhouette loss and the fused
+expected-depth loss (dpc.render.proj_depth_loss) on the same projection,
+    total = proj_weight * (proj + student) + proj_depth_weight * depth.
+With the default weight of 0 the step is the one above.
 """
 import numpy as np
 import torch
@@ -98,11 +104,19 @@ class TrainStep:
         out.update(n.poseNet(enc["poses"]))
         return out
 
-    def loss(self, images, masks, global_step=None, valid_samples=None):
+    def loss(self, images, masks, global_step=None, valid_samples=None, depths=None):
         """Forward of one step; returns (total loss, dict of the pieces the reference's outputs dict would hold).
         masks [B*V,1,Hm,Wm] go to the renderer as they are (it pools them to the silhouette size inside its kernels);
-        valid_samples [B*V] | None weights every view's projection and student terms (cfg.variable_num_views)."""
+        valid_samples [B*V] | None weights every view's projection and student terms (cfg.variable_num_views);
+        depths [B*V,Hd,Wd,1] (inputs["depths"]) are needed, and only read, when cfg.proj_depth_weight != 0."""
         cfg = self.cfg
+        depth_weight = cfg.get("proj_depth_weight", 0.0)
+        if depth_weight != 0:
+            if cfg.pose_predict_num_candidates != 1:
+                raise NotImplementedError("proj_depth_weight != 0 needs pose_predict_num_candidates == 1: with K candidates "
+                                          "the reference's depth loss does not broadcast")
+            if depths is None:
+                raise ValueError("proj_depth_weight != 0: the step needs `depths` (inputs['depths'], cfg.saved_depth)")
         step = self.global_step if global_step is None else global_step
         out = self.predict(images)
         K, V = cfg.pose_predict_num_candidates, cfg.step_size
@@ -122,6 +136,17 @@ class TrainStep:
                 host = np.stack([np.random.choice(all_points.shape[1], n_out, replace=False) for _ in range(clouds)])
                 point_index = torch.from_numpy(host.astype(np.int32)).to(all_points.device)
         kernel = R.smoothing_kernel(cfg, R.get_smooth_sigma(cfg, step))
+        if depth_weight != 0:
+            # projection, silhouette loss and depth loss as three nodes on one projection: the depth loss's gradient joins the
+            # silhouette's at the fused node's grid (get_loss, model_pc_to.py:391-408 with losses.py:113-136)
+            proj_out = R.pointcloud_project_fast(cfg, all_points, out["poses"], None, None, kernel, scaling_factor=all_scales,
+                                                 point_index=point_index, schedule=sched)
+            proj_loss, winner = R.silhouette_loss(proj_out["proj"], masks, K, valid_samples)
+            depth_loss, projs_depth = R.proj_depth_loss(cfg, proj_out, depths, valid_samples, return_depth=True)   # one pass
+            total = proj_loss.double() * cfg.proj_weight + depth_loss.double() * depth_weight
+            out.update(projs=proj_out["proj"], min_loss=winner, proj_loss=proj_loss, pooled_masks=pooled_masks(masks, cfg.vox_size),
+                       depth_loss=depth_loss, projs_depth=projs_depth)
+            return total, out
         proj_loss, proj_out, winner = R.pointcloud_project_loss(cfg, all_points, out["poses"], None, None, kernel,
                                                                 scaling_factor=all_scales, gt=masks, num_candidates=K,
                                                                 point_index=point_index, schedule=sched,
@@ -136,7 +161,7 @@ class TrainStep:
         out.update(projs=proj_out["proj"], min_loss=winner, proj_loss=proj_loss, pooled_masks=gt)
         return total, out
 
-    def __call__(self, images, masks, valid_samples=None):
+    def __call__(self, images, masks, valid_samples=None, depths=None):
         """zero_grad, forward, loss, backward, Adam step (train_to.py:112-131).  Returns the loss tensor (no host sync).
         With `grad_sync` set (dpc.render.parallel.OverlappedGradAllReduce) the ranks' gradients are summed while the
         backward runs; `sync_samples` = (objects of this rank, objects of all ranks)."""
@@ -144,7 +169,7 @@ class TrainStep:
             self.grad_sync.prepare(*self.sync_samples)
         else:
             self.optimizer.zero_grad(set_to_none=True)
-        total, _ = self.loss(images, masks, valid_samples=valid_samples)
+        total, _ = self.loss(images, masks, valid_samples=valid_samples, depths=depths)
         total.backward()
         if self.grad_sync is not None:
             self.grad_sync.finish()
@@ -179,6 +204,10 @@ class TrainStep:
         else:
             self._captured_schedule.update(kxy, kz, n_live)
 
+    def _no_captured_depth_step(self):
+        if self.cfg.get("proj_depth_weight", 0.0) != 0:
+            raise NotImplementedError("proj_depth_weight != 0: the depth-supervised step is eager only (no graph capture)")
+
     def capture_compute(self, images, masks, warmup=2, valid_samples=None):
         """The multi-rank variant of capture(): forward, loss and backward as ONE HIP graph whose backward accumulates
         straight into the flat buckets of `grad_sync` (every .grad is a view into them); the gradient exchange and Adam run
@@ -187,6 +216,7 @@ class TrainStep:
         `warmup` eager steps run first: the first one fixes which parameters take part in the exchange.
         Returns replay(images, masks[, valid_samples]) -> loss tensor (valid_samples: a static input like the masks, given
         at every replay when the capture had it)."""
+        self._no_captured_depth_step()
         sync = self.grad_sync
         if sync is None:
             raise RuntimeError("capture_compute() is the step with a gradient exchange (set grad_sync); use capture() without")
@@ -246,6 +276,7 @@ class TrainStep:
         another compiled tap window or the kept points outgrow the captured rows (`recaptures` counts).  Returns
         replay(images, masks[, valid_samples]) -> loss tensor (static memory, overwritten by the next replay); valid_samples
         is a static input like the masks, given at every replay when the capture had it."""
+        self._no_captured_depth_step()
         if self.grad_sync is not None:
             raise RuntimeError("capture() covers the single-process step; the overlapped gradient exchange runs eagerly")
         if self.cfg.pc_point_dropout != 1 and not self.device_dropout:

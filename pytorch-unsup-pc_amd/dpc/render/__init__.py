@@ -17,8 +17,9 @@ import numpy as np
 import torch
 
 from . import _native
-from ._ops import (DeviceSchedule, Drc, Geometry, ProjectFused, ProjectLossFused, ProjectLossStep, SilhouetteLoss, Smooth, Splat,
+from ._ops import (DepthLoss, DepthMap, DeviceSchedule, Drc, Geometry, ProjectFused, ProjectLossFused, ProjectLossStep, SilhouetteLoss, Smooth, Splat,
                    Transform, status_word, taps_bucket)
+from ._ops import _plane as _ops_plane
 from .predictions import chamfer_of_predictions, load_predictions, save_predictions  # noqa: F401
 from .alignment import (alignment_candidates, alignment_to_ground_truth, as_rotation_matrix, from_rotation_matrix,  # noqa: F401
                         icp_point_to_point, pose_errors, quat_w_avg_markley, quaternion_from_campos, reference_rotation)
@@ -37,7 +38,7 @@ __all__ = [
     "quaternion_rotate", "quaternion_multiply", "quaternion_conjugate", "quaternion_normalise",
     "get_smooth_sigma", "get_dropout_prob", "ProjectionOutputs", "silhouette_loss", "pointcloud_project_loss",
     "point_cloud_distance", "compute_distance", "chamfer_distances", "graphed_project_loss", "prefer_direct_graph_launch", "point_dropout_indices", "save_predictions", "load_predictions", "chamfer_of_predictions",
-    "DeviceSchedule", "check_status", "set_debug_checks", "taps_bucket", "project_loss_step",
+    "DeviceSchedule", "check_status", "set_debug_checks", "taps_bucket", "project_loss_step", "project_depth", "proj_depth_loss",
     "icp_point_to_point", "alignment_to_ground_truth", "alignment_candidates", "reference_rotation", "quat_w_avg_markley",
     "quaternion_from_campos", "as_rotation_matrix", "from_rotation_matrix", "pose_errors",
     "nearest_batched", "chamfer_batched", "chamfer_loss", "chamfer_of_split", "eval_chamfer", "voxel_down_sample", "downsample_split",
@@ -347,8 +348,9 @@ class ProjectionOutputs(dict):
 
     _LAZY = ("voxels", "tr_pc", "drc_probs", "proj_depth")
 
-    def __init__(self, proj, builder):
+    def __init__(self, proj, builder, fused=None):
         super().__init__(proj=proj, voxels_rgb=None, proj_rgb=None)
+        self._fused = fused   # (geom, grid_wh, s) of the fused path: what project_depth / proj_depth_loss start from
         self._builders = builder if isinstance(builder, dict) else {k: builder for k in self._LAZY}
         for k in self._LAZY:
             dict.__setitem__(self, k, None)
@@ -494,7 +496,8 @@ def pointcloud_project_fast(cfg, point_cloud, transform, predicted_translation, 
         out = staged()
         return ProjectionOutputs(out["proj"], lambda: out)
     return ProjectionOutputs(proj, _outputs_from_grid(cfg, geom, grid_wh, point_cloud, transform, predicted_translation,
-                                                      focal_length, scaling_factor, point_index))
+                                                      focal_length, scaling_factor, point_index),
+                             fused=(geom, grid_wh, scaling_factor))
 
 
 pointcloud_project = pointcloud_project_fast
@@ -640,6 +643,71 @@ def silhouette_loss(pred, gt, num_candidates=1, valid_samples=None):
     (proj_loss_pose_candidates): per sample the candidate with the smallest (unweighted) sum of squared differences wins
     and only winners contribute, w^2-weighted.  Returns (loss, winner [S] int32)."""
     return SilhouetteLoss.apply(pred, gt, num_candidates, valid_samples)
+
+
+# ------------------------------------------------------------------------------------------------------
+# Depth supervision                                  reference: dpc/util/losses.py:113-136 (add_proj_depth_loss)
+# ------------------------------------------------------------------------------------------------------
+def _fused_parts(outputs):
+    if not isinstance(outputs, ProjectionOutputs):
+        raise TypeError("outputs must be what pointcloud_project_fast returned, got %s" % type(outputs).__name__)
+    return outputs._fused
+
+
+def project_depth(outputs):
+    """Expected depth [B,H,W,1] of the projection `outputs` (what pointcloud_project_fast returned): the values of
+    outputs["proj_depth"] (drc_depth_projection, dpc/util/drc.py:152-160, rows flipped like proj) from one column kernel on
+    the fused node's grid instead of a smoothed grid plus the [D+1,B,H,W] probabilities; differentiable.  Outputs of the
+    staged fallback (a Gaussian longer than the fused window) hand back their own proj_depth."""
+    fused = _fused_parts(outputs)
+    if fused is None:
+        return outputs["proj_depth"]
+    geom, grid_wh, s = fused
+    return DepthMap.apply(grid_wh, s, geom)
+
+
+def proj_depth_loss(cfg, outputs, depths, valid_samples=None, return_depth=False):
+    """add_proj_depth_loss (dpc/util/losses.py:113-136) without its weight: (1/2) sum_s w_s^2 sum_pix (g - depth)^2 / S.
+    return_depth: (loss, depth [S,H,W,1] detached) -- the map the loss was formed from, written by the same launch.
+
+    outputs: what pointcloud_project_fast returned for S clouds (one per sample); depths: inputs["depths"], [S,Hd,Wd,1],
+    [S,1,Hd,Wd] or [S,Hd,Wd] with Hd = f*H, Wd = f*W for an integer f >= 1 -- g[s,y,x] = depths[s,f*y,f*x], the reference's
+    tf.image.resize_images(..., NEAREST_NEIGHBOR), and g = cfg.max_depth where depths == cfg.max_dataset_depth when the two
+    differ; valid_samples [S] | None: per-sample weights w, squared like silhouette_loss's (None, the reference: all ones).
+    The caller multiplies by cfg.proj_depth_weight.  On the fused path the whole loss is two launches forward and one backward
+    (csrc/dpc_depth.hip); outputs of the staged fallback get the same numbers from outputs["proj_depth"] with torch."""
+    if _get(cfg, "pc_gauss_filter_gt", False):
+        raise NotImplementedError("pc_gauss_filter_gt: true -- smoothing of the ground-truth depth is not implemented "
+                                  "(the reference's torch port prints 'Not implemented' there, dpc/util/losses_to.py)")
+    fused = _fused_parts(outputs)
+    S = outputs["proj"].shape[0]
+    H, W = outputs["proj"].shape[1], outputs["proj"].shape[2]
+    plane = _ops_plane(tuple(depths.shape))
+    if plane is None:
+        raise ValueError("depths must be [S,Hd,Wd,1], [S,1,Hd,Wd] or [S,Hd,Wd], got %s" % (tuple(depths.shape),))
+    if depths.shape[0] != S:
+        raise NotImplementedError("pose_predict_num_candidates: %d projections for %d depth maps -- the depth loss needs one "
+                                  "cloud per sample (with K candidates the reference's shapes do not broadcast)"
+                                  % (S, depths.shape[0]))
+    Hd, Wd = plane
+    if Hd < H or Wd < W or Hd % H or Wd % W or Hd // H != Wd // W:
+        raise ValueError("depths %dx%d are not an integer multiple of the %dx%d projections" % (Hd, Wd, H, W))
+    f = Hd // H
+    max_depth = float(_get(cfg, "max_depth", 10.0))
+    mdd = float(_get(cfg, "max_dataset_depth", max_depth))
+    if fused is not None:
+        geom, grid_wh, s = fused
+        loss, depth = DepthLoss.apply(grid_wh, s, depths, f, mdd, valid_samples, geom, bool(return_depth))
+        return (loss, depth) if return_depth else loss
+    pred = outputs["proj_depth"].reshape(S, H, W)
+    g = depths.reshape(S, Hd, Wd)[:, ::f, ::f].to(pred.dtype)
+    if mdd != max_depth:
+        g = torch.where(g == mdd, torch.full_like(g, max_depth), g)
+    sq = ((g - pred) ** 2).sum((1, 2))
+    if valid_samples is not None:
+        sq = sq * valid_samples.to(sq.dtype) ** 2
+    loss = 0.5 * sq.sum() / S
+    return (loss, outputs["proj_depth"].detach()) if return_depth else loss
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -67,6 +67,9 @@ _FUNCTIONS = (
     ("dpc_drc_fwd", _i, [_pp] + [_vp] * 5),
     ("dpc_drc_bwd", _i, [_pp] + [_vp] * 6),
     ("dpc_silhouette_loss", _i, [_vp, _i, _vp, _vp] + [_i] * 4 + [_vp, _vp, _vp, _vp]),
+    ("dpc_depth_workspace_bytes", _sz, [_pp]),
+    ("dpc_depth_loss_fwd", _i, [_pp] + [_vp] * 4 + [_i, ctypes.c_float] + [_vp] * 5),
+    ("dpc_depth_loss_bwd", _i, [_pp] + [_vp] * 4 + [_i, ctypes.c_float] + [_vp] * 7),
     ("dpc_point_dropout_indices", _i, [_i, _i, _i, _vp, _vp, _vp]),
     ("dpc_point_dropout_indices_live", _i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     ("dpc_schedule_update", _i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),

@@ -802,3 +802,113 @@ class SilhouetteLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dwinner):
         return _like_input(ctx.dpred * dloss, ctx.meta), None, None, None
+
+
+# ------------------------------------------------------------------------------------------------------
+# Expected depth and its loss from grid_wh (csrc/dpc_depth.hip)      reference: dpc/util/losses.py:113-136
+# ------------------------------------------------------------------------------------------------------
+_depth_ws = {}   # (device, stream, bytes) -> workspace whose tickets are zero between launches
+
+
+def _depth_workspace(dev, nbytes):
+    """Workspace of dpc_depth_loss_bwd.  Its first bytes are the tickets of the in-launch ds reduction: zero on entry, left
+    zero by the kernel -- so the buffer is zeroed ONCE, when it is made, and kept per device and stream (launches of one
+    stream run one after the other; another stream gets a buffer of its own).  While a HIP graph is being captured the buffer
+    is not kept: it comes from the graph's pool and its zero fill is part of the graph."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), _stream(dev), nbytes)
+    ws = _depth_ws.get(key)
+    if ws is None:
+        if len(_depth_ws) >= 16:
+            _depth_ws.clear()
+        ws = _depth_ws[key] = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _depth_backward(ctx, dloss, ddepth):
+    """One launch: d grid_wh (overwritten) and d s from the gradient arriving at the loss and / or the depth map."""
+    grid_wh, s32, gt32, w32 = ctx.saved
+    geom, dev, B = ctx.geom, grid_wh.device, grid_wh.shape[0]
+    L = N.lib()
+    Z = geom.sized(B, 0)
+    dgrid = torch.empty_like(grid_wh)
+    ds = None if s32 is None else torch.empty((B,), dtype=torch.float32, device=dev)
+    with _on(dev):
+        ws = _depth_workspace(dev, max(L.dpc_depth_workspace_bytes(Z.ref), 16))
+        rc = L.dpc_depth_loss_bwd(Z.ref, _dp(grid_wh), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), ctx.gt_factor,
+                                  ctx.max_dataset_depth, _dp(w32), _dp(_f32(dloss)), _dp(_f32(ddepth)), _dp(dgrid), _dp(ds),
+                                  _dp(ws), _stream(dev))
+    if rc != 0:
+        N.check(rc, "dpc_depth_loss_bwd")
+    return _like_input(dgrid, ctx.metas[0]), _like_input(ds, ctx.metas[1])
+
+
+def _depth_inputs(grid_wh, s, geom):
+    dev = N.require_device(grid_wh, s)
+    g32, s32 = _f32(grid_wh), _f32(s)
+    if tuple(g32.shape[1:]) != (geom.D, geom.H, geom.W):
+        raise ValueError("grid_wh must be [B,%d,%d,%d], got %s" % (geom.D, geom.H, geom.W, tuple(g32.shape)))
+    if s32 is not None and s32.numel() != g32.shape[0]:
+        raise ValueError("scaling_factor must hold one value per cloud (%d), got %s" % (g32.shape[0], tuple(s32.shape)))
+    return dev, g32, s32
+
+
+class DepthMap(torch.autograd.Function):
+    """drc_depth_projection of the fused path: grid_wh [B,D,H,W] (ProjectFused's second output), s [B,1] | None ->
+    expected depth [B,H,W,1], rows flipped like proj.  One launch forward, one backward."""
+
+    @staticmethod
+    def forward(ctx, grid_wh, s, geom):
+        dev, g32, s32 = _depth_inputs(grid_wh, s, geom)
+        B = g32.shape[0]
+        Z = geom.sized(B, 0)
+        depth = torch.empty((B, geom.H, geom.W, 1), dtype=torch.float32, device=dev)
+        with _on(dev):
+            rc = N.lib().dpc_depth_loss_fwd(Z.ref, _dp(g32), _dp(s32), geom.kern_ptrs()[1], None, 1, 0.0, None, _dp(depth),
+                                            None, None, _stream(dev))
+        if rc != 0:
+            N.check(rc, "dpc_depth_loss_fwd")
+        ctx.geom, ctx.saved, ctx.metas = geom, (g32, s32, None, None), (_meta(grid_wh), _meta(s))
+        ctx.gt_factor, ctx.max_dataset_depth = 1, 0.0
+        return depth
+
+    @staticmethod
+    def backward(ctx, ddepth):
+        return _depth_backward(ctx, None, ddepth) + (None,)
+
+
+class DepthLoss(torch.autograd.Function):
+    """add_proj_depth_loss on the fused path: grid_wh [B,D,H,W], s [B,1] | None, gt [S,f*H,f*W] depth maps (S = B),
+    weights [S] | None -> (1/2) sum_s w_s^2 sum (g - depth)^2 / S with g the f-fold nearest-neighbour subsample of gt and
+    max_dataset_depth replaced by max_depth.  Two launches forward (column kernel, one-block finalize), one backward."""
+
+    @staticmethod
+    def forward(ctx, grid_wh, s, gt, gt_factor, max_dataset_depth, weights, geom, want_depth=False):
+        """Returns (loss, depth): depth [B,H,W,1] written by the same launch when want_depth (detached: differentiate
+        DepthMap for a gradient through the map itself), else None."""
+        dev, g32, s32 = _depth_inputs(grid_wh, s, geom)
+        N.require_device(g32, gt, weights)
+        B, f = g32.shape[0], int(gt_factor)
+        gt32 = _f32(gt)
+        if gt32.numel() != B * f * geom.H * f * geom.W:
+            raise ValueError("depths must hold %d x %d x %d values, got %s" % (B, f * geom.H, f * geom.W, tuple(gt.shape)))
+        w32 = _weights32(weights, B)
+        Z = geom.sized(B, 0)
+        tiles = torch.empty((B, (geom.H * geom.W + 255) // 256), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        depth = torch.empty((B, geom.H, geom.W, 1), dtype=torch.float32, device=dev) if want_depth else None
+        with _on(dev):
+            rc = N.lib().dpc_depth_loss_fwd(Z.ref, _dp(g32), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), f,
+                                            float(max_dataset_depth), _dp(w32), _dp(depth), _dp(tiles), _dp(loss), _stream(dev))
+        if rc != 0:
+            N.check(rc, "dpc_depth_loss_fwd")
+        ctx.geom, ctx.saved, ctx.metas = geom, (g32, s32, gt32, w32), (_meta(grid_wh), _meta(s))
+        ctx.gt_factor, ctx.max_dataset_depth = f, float(max_dataset_depth)
+        if depth is not None:
+            ctx.mark_non_differentiable(depth)
+        return loss, depth
+
+    @staticmethod
+    def backward(ctx, dloss, _ddepth):
+        return _depth_backward(ctx, dloss, None) + (None,) * 6

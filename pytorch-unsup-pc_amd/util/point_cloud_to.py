@@ -1,6 +1,9 @@
 """Drop-in for the reference's dpc/util/point_cloud_to.py (names as imported at dpc/models/model_pc_to.py:15)."""
 from dpc.render import (pc_perspective_transform, pc_point_dropout, pointcloud2voxels3d_fast,  # noqa: F401
                         pointcloud_project, pointcloud_project_fast, smooth_voxels3d, smoothen_voxels3d)
+# not in the reference's module: the fused depth map and depth loss of the projection's output dict (its torch port leaves
+# add_proj_depth_loss half translated, dpc/util/losses_to.py)
+from dpc.render import proj_depth_loss, project_depth  # noqa: F401
 
 from ._overlay import fall_through as _fall_through  # noqa: E402
 
