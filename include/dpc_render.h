@@ -353,6 +353,62 @@ int dpc_depth_loss_bwd(const DpcParams* p, const float* grid_wh, const float* s,
                        const float* ddepth, float* dgrid_wh, float* ds, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Colour: per-point RGB projected to an image and its loss.  The reference's torch port crashes on this branch
+ * (dpc/util/point_cloud_to.py:64, dpc/util/drc.py:137); the definition is its TF-1 original: pointcloud2voxels3d_fast's rgb
+ * half (dpc/util/point_cloud.py:98-134), the clips, the division by the occupancies and the flip of pointcloud_project_fast
+ * (:244-262, 275-277), project_volume_rgb_integral (dpc/util/drc.py:132-142), add_proj_rgb_loss (dpc/util/losses.py:69-90).
+ * The Gaussian between the splat and the integral is dpc_smooth on the [B*3,D,H,W] view of the colour grid (convolve_rgb,
+ * point_cloud.py:148-154); the pre-convolution clip is the caller's.  All grids fp32; tr [B,N,3] transformed points (z,y,x),
+ * rgb [B,N,3] one row per cloud; colour grids are PLANAR, [B,3,D,H,W].  Stage-level: p->point_replicas <= 1 and
+ * p->point_index == NULL (DPC_ERR_SHAPE otherwise).  p->taps_* are not read.
+ *
+ * dpc_rgb_splat_fwd: out[b, c, iz+k, iy+j, ix+i] += wz[k] wy[j] wx[i] rgb[b,n,c] for every point with all three
+ *   coordinates in [-1/2, 1/2], with the cell, the weights and the dropped out-of-range corners of the occupancy splat
+ *   (dpc_splat_fwd: the same point record), so a point's colour and occupancy land in the same cells with the same weights.
+ *   `out` is zeroed by a launch of the call, then two neighbouring lanes per (cloud, channel, point) add the point's 8
+ *   corners, four each (the pair owns the two x corners, neighbours in memory), with fp32 hardware atomics
+ *   (global_atomic_add_f32, no compare-and-swap loop).  NOT BIT-REPRODUCIBLE: a voxel's sum depends on
+ *   the order its adds arrive in, so two runs on equal inputs may differ in the last bits of the colour grid (and of
+ *   everything computed from it); a reproducible, atomic-free splat is future work.
+ * dpc_rgb_splat_bwd: dC [B,3,D,H,W] -> drgb [B,N,3], drgb_c = sum_corners w dC_c; dtr [B,N,3] | NULL, dpc_splat_bwd's
+ *   formula applied to sum_c rgb_c dC_c[corner] (NULL: pc_rgb_stop_points_gradient, point_cloud.py:112-113).  One thread
+ *   per point, 24 gathers; no atomics; a point outside the cube gets exact zeros.  Every element is written.
+ *
+ * dpc_rgb_loss_fwd: per ray (b, y, x), with y_k = clamp(vox[b,k,y,x], eps, 1 - eps), A_k = prod_{j<k} (1 - y_j),
+ *   p_0 = e^eps y_0, p_k = y_k A_k, p_D = e^eps A_D (dpc_drc_fwd's probabilities, the product in fp64) and
+ *   c_k = C[b,c,k,y,x] / (div[b,k,y,x] + div_eps)  when div is given (pc_rgb_divide_by_occupancies: div is the smoothed RAW
+ *         occupancy splat, a constant of the node -- the reference stops its gradient),
+ *   c_k = clamp(c_k, 0, 1)                          when clip_after (pc_rgb_clip_after_conv),
+ *   proj_rgb[b, H-1-y, x, c] = sum_{k<D} p_k c_k + p_D * 1      (white background; rows flipped like proj).
+ *   Loss, one cloud per sample (S = B):
+ *     g[s, y, x, c] = gt[s, f*y, f*x, c]      f = gt_factor >= 1: TF-1's bilinear resize_images without align_corners
+ *                                             samples exactly at (f*y, f*x) for an integer factor;
+ *     loss = (1/2) sum_s w_s^2 sum_{pix,c} (g - proj_rgb)^2 / S       tf.nn.l2_loss / num_samples; w = weights [S] | NULL (= 1),
+ *                                                                     squared.  The caller applies proj_rgb_weight.
+ *   gt [S,f*H,f*W,3], or [S,3,f*H,f*W] when gt_planar != 0, | NULL (projection only); proj_rgb [B,H,W,3] | NULL;
+ *   loss_tiles [B, ceil(H*W/256)] scratch: the ray tiles' squared errors, added in tile order by a one-block second
+ *   launch (no float atomics: for one and the same colour grid the loss is the same bits on every run); loss [1].
+ * dpc_rgb_loss_bwd: the residual of a ray is r_c = dloss w_s^2 (proj_rgb_c - g_c) / S (dloss: device scalar | NULL = 1;
+ *   nothing when gt is NULL; proj_rgb: what the forward wrote, required with gt) plus dproj_rgb [B,H,W,3] | NULL.  Outputs,
+ *   every element overwritten: dC [B,3,D,H,W], dC_{c,k} = p_k r_c (times 1 / (div + div_eps), and zero where the after-clip
+ *   acted); dvox [B,D,H,W], the DRC backward of dpc_drc_bwd with gp_k = sum_c r_c c_k, gp_D = sum_c r_c:
+ *   dL/dy_m = gp_m E_m A_m - (sum_{k>m} gp_k p_k) / (1 - y_m), through the clamp where eps <= vox <= 1 - eps.  The prefix
+ *   products are parked in dvox by a first pass down the ray and replaced by a second pass up it: no workspace.  One launch.
+ * Any D, one thread per ray.  DPC_ERR_SHAPE, before any launch: gt_factor < 1, f*H or f*W > 1024, gt without loss or
+ * loss_tiles, neither gt nor proj_rgb (fwd), neither gt nor dproj_rgb (bwd).  Nothing synchronises or allocates.
+ * Added without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+int dpc_rgb_splat_fwd(const DpcParams* p, const float* tr, const float* rgb, float* out, void* stream);
+int dpc_rgb_splat_bwd(const DpcParams* p, const float* tr, const float* rgb, const float* dC, float* drgb, float* dtr,
+                      void* stream);
+int dpc_rgb_loss_fwd(const DpcParams* p, const float* vox, const float* C, const float* div, float div_eps, int clip_after,
+                     const float* gt, int gt_factor, int gt_planar, const float* weights, float* proj_rgb, float* loss_tiles,
+                     float* loss, void* stream);
+int dpc_rgb_loss_bwd(const DpcParams* p, const float* vox, const float* C, const float* div, float div_eps, int clip_after,
+                     const float* gt, int gt_factor, int gt_planar, const float* weights, const float* proj_rgb,
+                     const float* dloss, const float* dproj_rgb, float* dvox, float* dC, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Evaluation side: point_cloud_distance (dpc/util/point_cloud_distance.py:25-40), the kernel of
  * the Chamfer evaluation (dpc/run/eval_chamfer_to.py:24-44).  For every source point vs[i] ([ns,3]) the nearest target
  * vt[j] ([nt,3]): idx[i] = first j minimising dist = sqrt(sum((vt[j]-vs[i])^2)) (int64, like torch.argmin),

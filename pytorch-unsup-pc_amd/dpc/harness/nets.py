@@ -2,7 +2,7 @@
 
     reference                                    here
     dpc/nets/img_encoder_to.py:15-67   Encoder   strided 5x5 conv, then (stride-2 3x3, 3x3) blocks down to 4x4, three FCs, pose FC
-    dpc/nets/pc_decoder_to.py:15-56    Decoder   one FC to N*3, tanh (/2 for the unit cube); rgb heads kept for checkpoint parity
+    dpc/nets/pc_decoder_to.py:15-56    Decoder   one FC to N*3, tanh (/2 for the unit cube); rgb heads evaluated under pc_rgb
     dpc/nets/pose_net_to.py:15-86      PoseNet   K candidate MLPs + a student MLP (or a single FC), optional translation FC
     dpc/models/model_pc_to.py:113-130  ScalePredictor  FC + sigmoid * pc_occupancy_scaling_maximum
 
@@ -66,14 +66,29 @@ class Decoder(nn.Module):
         self.num_points, self.unit_cube = cfg.pc_num_points, bool(cfg.pc_unit_cube)
         d = cfg.fc_dim
         self.pts_raw_fc = nn.Linear(d, 3 * self.num_points)
-        # colour heads: dead in the reference's live configuration (pc_rgb: false) but part of its checkpoints
+        # colour heads: off in the reference's live configuration (pc_rgb: false) but part of its checkpoints
         self.rgb_deep_decoder = _stack([d, d, d, d], True)
         self.rgb_raw_dec = nn.Linear(d, 3 * self.num_points)
+        self.with_rgb = bool(cfg.get("pc_rgb", False))
+        self.rgb_deep = bool(cfg.get("pc_rgb_deep_decoder", False))
         _fresh(self)
 
-    def forward(self, code):
+    def forward(self, code, conv_features=None):
+        """Points [B,N,3]; under cfg.pc_rgb the pair (points, colours [B,N,3] in (0,1)): sigmoid of rgb_raw_dec on the code,
+        or on rgb_deep_decoder(conv_features) under pc_rgb_deep_decoder (pc_decoder_to.py:44-55)."""
         xyz = torch.tanh(self.pts_raw_fc(code).reshape(-1, self.num_points, 3))
-        return xyz / 2.0 if self.unit_cube else xyz
+        xyz = xyz / 2.0 if self.unit_cube else xyz
+        if not self.with_rgb:
+            return xyz
+        inp = code
+        if self.rgb_deep:
+            if conv_features is None or conv_features.shape[-1] != self.rgb_raw_dec.in_features:
+                raise ValueError("pc_rgb_deep_decoder: the colour decoder reads the encoder's conv_features, which must be "
+                                 "fc_dim = %d wide (pc_decoder_to.py:25-27, 46-47), got %s"
+                                 % (self.rgb_raw_dec.in_features, None if conv_features is None else tuple(conv_features.shape)))
+            inp = self.rgb_deep_decoder(conv_features)
+        rgb = torch.sigmoid(self.rgb_raw_dec(inp).reshape(-1, self.num_points, 3))
+        return xyz, rgb
 
 
 class _PoseBranch(nn.Module):

@@ -16,6 +16,11 @@ called from get_loss): the renderer's projection (dpc.render.pointcloud_project_
 expected-depth loss (dpc.render.proj_depth_loss) on the same projection,
     total = proj_weight * (proj + student) + proj_depth_weight * depth.
 With the default weight of 0 the step is the one above.
+
+Colour supervision (cfg.pc_rgb and cfg.proj_rgb_weight != 0, one pose candidate per image; add_proj_rgb_loss,
+dpc/util/losses.py:69-90): the decoder's per-point colours, replicated like the points, are projected on the same projection
+(dpc.render.proj_rgb_loss) and compared with the input images,
+    total = proj_weight * (proj + student) + proj_depth_weight * depth + proj_rgb_weight * rgb.
 """
 import numpy as np
 import torch
@@ -100,7 +105,11 @@ class TrainStep:
         cfg, n = self.cfg, self.nets
         enc = n.encoder(images)
         first_view = enc["ids"][::cfg.step_size]  # pool_single_view(cfg, ids, 0), model_base_to.py:8-10
-        out = {"ids": enc["ids"], "points_1": n.decoder(first_view), "scaling_factor": n.scalePred(first_view)}
+        out = {"ids": enc["ids"], "scaling_factor": n.scalePred(first_view)}
+        if cfg.get("pc_rgb", False):   # decoder_out['xyz'], decoder_out['rgb'] (model_pc_to.py:216-219)
+            out["points_1"], out["rgb_1"] = n.decoder(first_view, enc["conv_features"][::cfg.step_size])
+        else:
+            out["points_1"] = n.decoder(first_view)
         out.update(n.poseNet(enc["poses"]))
         return out
 
@@ -108,9 +117,14 @@ class TrainStep:
         """Forward of one step; returns (total loss, dict of the pieces the reference's outputs dict would hold).
         masks [B*V,1,Hm,Wm] go to the renderer as they are (it pools them to the silhouette size inside its kernels);
         valid_samples [B*V] | None weights every view's projection and student terms (cfg.variable_num_views);
-        depths [B*V,Hd,Wd,1] (inputs["depths"]) are needed, and only read, when cfg.proj_depth_weight != 0."""
+        depths [B*V,Hd,Wd,1] (inputs["depths"]) are needed, and only read, when cfg.proj_depth_weight != 0.
+        With cfg.pc_rgb and cfg.proj_rgb_weight != 0 the images themselves are the colour loss's ground truth."""
         cfg = self.cfg
         depth_weight = cfg.get("proj_depth_weight", 0.0)
+        rgb_weight = cfg.get("proj_rgb_weight", 0.0) if cfg.get("pc_rgb", False) else 0.0
+        if rgb_weight != 0 and cfg.pose_predict_num_candidates != 1:
+            raise NotImplementedError("proj_rgb_weight != 0 needs pose_predict_num_candidates == 1: colour for K pose "
+                                      "candidates is not implemented")
         if depth_weight != 0:
             if cfg.pose_predict_num_candidates != 1:
                 raise NotImplementedError("proj_depth_weight != 0 needs pose_predict_num_candidates == 1: with K candidates "
@@ -136,16 +150,23 @@ class TrainStep:
                 host = np.stack([np.random.choice(all_points.shape[1], n_out, replace=False) for _ in range(clouds)])
                 point_index = torch.from_numpy(host.astype(np.int32)).to(all_points.device)
         kernel = R.smoothing_kernel(cfg, R.get_smooth_sigma(cfg, step))
-        if depth_weight != 0:
-            # projection, silhouette loss and depth loss as three nodes on one projection: the depth loss's gradient joins the
-            # silhouette's at the fused node's grid (get_loss, model_pc_to.py:391-408 with losses.py:113-136)
+        if depth_weight != 0 or rgb_weight != 0:
+            # projection, silhouette loss and depth / colour losses as nodes on one projection: their gradients join the
+            # silhouette's at the projection's outputs (get_loss, model_pc_to.py:391-408 with losses.py:69-90, 113-136)
             proj_out = R.pointcloud_project_fast(cfg, all_points, out["poses"], None, None, kernel, scaling_factor=all_scales,
                                                  point_index=point_index, schedule=sched)
             proj_loss, winner = R.silhouette_loss(proj_out["proj"], masks, K, valid_samples)
-            depth_loss, projs_depth = R.proj_depth_loss(cfg, proj_out, depths, valid_samples, return_depth=True)   # one pass
-            total = proj_loss.double() * cfg.proj_weight + depth_loss.double() * depth_weight
-            out.update(projs=proj_out["proj"], min_loss=winner, proj_loss=proj_loss, pooled_masks=pooled_masks(masks, cfg.vox_size),
-                       depth_loss=depth_loss, projs_depth=projs_depth)
+            total = proj_loss.double() * cfg.proj_weight
+            out.update(projs=proj_out["proj"], min_loss=winner, proj_loss=proj_loss, pooled_masks=pooled_masks(masks, cfg.vox_size))
+            if depth_weight != 0:
+                depth_loss, projs_depth = R.proj_depth_loss(cfg, proj_out, depths, valid_samples, return_depth=True)   # one pass
+                total = total + depth_loss.double() * depth_weight
+                out.update(depth_loss=depth_loss, projs_depth=projs_depth)
+            if rgb_weight != 0:
+                all_rgb = R.replicate_rgb(out["rgb_1"], out["poses"].shape[0], point_index)   # model_pc_to.py:254-258, 323-329
+                rgb_loss, projs_rgb = R.proj_rgb_loss(cfg, proj_out, all_rgb, images, kernel, valid_samples, return_rgb=True)
+                total = total + rgb_loss.double() * rgb_weight
+                out.update(all_rgb=all_rgb, rgb_loss=rgb_loss, projs_rgb=projs_rgb)
             return total, out
         proj_loss, proj_out, winner = R.pointcloud_project_loss(cfg, all_points, out["poses"], None, None, kernel,
                                                                 scaling_factor=all_scales, gt=masks, num_candidates=K,
@@ -207,6 +228,8 @@ class TrainStep:
     def _no_captured_depth_step(self):
         if self.cfg.get("proj_depth_weight", 0.0) != 0:
             raise NotImplementedError("proj_depth_weight != 0: the depth-supervised step is eager only (no graph capture)")
+        if self.cfg.get("pc_rgb", False) and self.cfg.get("proj_rgb_weight", 0.0) != 0:
+            raise NotImplementedError("proj_rgb_weight != 0: the colour-supervised step is eager only (no graph capture)")
 
     def capture_compute(self, images, masks, warmup=2, valid_samples=None):
         """The multi-rank variant of capture(): forward, loss and backward as ONE HIP graph whose backward accumulates

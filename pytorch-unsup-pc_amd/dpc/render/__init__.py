@@ -17,8 +17,8 @@ import numpy as np
 import torch
 
 from . import _native
-from ._ops import (DepthLoss, DepthMap, DeviceSchedule, Drc, Geometry, ProjectFused, ProjectLossFused, ProjectLossStep, SilhouetteLoss, Smooth, Splat,
-                   Transform, status_word, taps_bucket)
+from ._ops import (DepthLoss, DepthMap, DeviceSchedule, Drc, Geometry, ProjectFused, ProjectLossFused, ProjectLossStep, RgbLoss, RgbMap, RgbSplat,
+                   SilhouetteLoss, Smooth, Splat, Transform, status_word, taps_bucket)
 from ._ops import _plane as _ops_plane
 from .predictions import chamfer_of_predictions, load_predictions, save_predictions  # noqa: F401
 from .alignment import (alignment_candidates, alignment_to_ground_truth, as_rotation_matrix, from_rotation_matrix,  # noqa: F401
@@ -39,6 +39,7 @@ __all__ = [
     "get_smooth_sigma", "get_dropout_prob", "ProjectionOutputs", "silhouette_loss", "pointcloud_project_loss",
     "point_cloud_distance", "compute_distance", "chamfer_distances", "graphed_project_loss", "prefer_direct_graph_launch", "point_dropout_indices", "save_predictions", "load_predictions", "chamfer_of_predictions",
     "DeviceSchedule", "check_status", "set_debug_checks", "taps_bucket", "project_loss_step", "project_depth", "proj_depth_loss",
+    "project_rgb", "proj_rgb_loss", "replicate_rgb",
     "icp_point_to_point", "alignment_to_ground_truth", "alignment_candidates", "reference_rotation", "quat_w_avg_markley",
     "quaternion_from_campos", "as_rotation_matrix", "from_rotation_matrix", "pose_errors",
     "nearest_batched", "chamfer_batched", "chamfer_loss", "chamfer_of_split", "eval_chamfer", "voxel_down_sample", "downsample_split",
@@ -480,7 +481,8 @@ def pointcloud_project_fast(cfg, point_cloud, transform, predicted_translation, 
     run time -- for a call captured in a HIP graph whose sigma / keep-count follow a schedule; `kernel` then only fixes the
     compiled tap windows (see DeviceSchedule)."""
     if all_rgb is not None:
-        raise NotImplementedError("all_rgb: the rgb branch of the reference is dead (point_cloud_to.py:64 AttributeError)")
+        raise NotImplementedError("all_rgb: the rgb branch of the reference is dead (point_cloud_to.py:64 AttributeError); "
+                                  "colour is a node of its own on the projection: dpc.render.project_rgb / proj_rgb_loss")
     _check_live_branches(cfg)
     _validate_point_index(point_index, point_cloud)
     geom = _geometry(cfg, kernel if smooth else None, schedule if smooth else None)
@@ -520,7 +522,8 @@ def pointcloud_project_loss(cfg, point_cloud, transform, predicted_translation, 
     too long for the fused kernels.  `point_cloud` may hold shared point sets ([B/R,N,3]) and `point_index` per-cloud
     subsets of them (see pointcloud_project_fast)."""
     if all_rgb is not None:
-        raise NotImplementedError("all_rgb: the rgb branch of the reference is dead (point_cloud_to.py:64 AttributeError)")
+        raise NotImplementedError("all_rgb: the rgb branch of the reference is dead (point_cloud_to.py:64 AttributeError); "
+                                  "colour is a node of its own on the projection: dpc.render.project_rgb / proj_rgb_loss")
     if gt is None:
         raise ValueError("gt (masks [S,1,Hm,Wm], or pooled [S,H,W,1]) is required")
     _check_live_branches(cfg)
@@ -708,6 +711,120 @@ def proj_depth_loss(cfg, outputs, depths, valid_samples=None, return_depth=False
         sq = sq * valid_samples.to(sq.dtype) ** 2
     loss = 0.5 * sq.sum() / S
     return (loss, outputs["proj_depth"].detach()) if return_depth else loss
+
+
+# ------------------------------------------------------------------------------------------------------
+# Colour supervision          reference (TF-1 originals): dpc/util/point_cloud.py:98-134, 244-262, 275-277;
+#                             dpc/util/drc.py:132-142; dpc/util/losses.py:69-90
+# ------------------------------------------------------------------------------------------------------
+def replicate_rgb(rgb, num_clouds, point_index=None):
+    """Per-point colours [B/R,N,3] of shared point sets -> one row per cloud [B,n,3]: tf_repeat_0 over views and pose
+    candidates, then the rgb half of pc_point_dropout -- cloud b keeps rgb[b // R][point_index[b]]
+    (dpc/models/model_pc_to.py:254-258, 323-329).  Plain torch, differentiable; the renderer reads shared point sets in
+    place, the colour node wants the replicated tensor."""
+    S = rgb.shape[0]
+    if S == 0 or num_clouds % S:
+        raise ValueError("%d clouds cannot share %d colour sets: the number of clouds must be a multiple" % (num_clouds, S))
+    if num_clouds != S:
+        rgb = rgb.repeat_interleave(num_clouds // S, dim=0)
+    if point_index is not None:
+        if point_index.dim() != 2 or point_index.shape[0] != num_clouds:
+            raise ValueError("point_index must be [%d, n], got %s" % (num_clouds, tuple(point_index.shape)))
+        rgb = rgb.gather(1, point_index.long().unsqueeze(-1).expand(-1, -1, 3))
+    return rgb
+
+
+def _rgb_options(cfg):
+    return (bool(_get(cfg, "pc_rgb_stop_points_gradient", False)), bool(_get(cfg, "pc_rgb_clip_after_conv", False)),
+            bool(_get(cfg, "pc_rgb_divide_by_occupancies", False)), float(_get(cfg, "pc_rgb_divide_by_occupancies_epsilon", 0.01)))
+
+
+def _rgb_grids(cfg, outputs, all_rgb, kernel):
+    """(geom, voxels [B,D,H,W], smoothed colour grid [B,3,D,H,W], occupancies to divide by | None) of a projection."""
+    stop, clip_after, divide, _ = _rgb_options(cfg)
+    tr, vox = outputs["tr_pc"], outputs["voxels"]
+    if tuple(all_rgb.shape) != tuple(tr.shape):
+        raise ValueError("all_rgb must hold one colour per projected point, %s (replicate_rgb makes it from the decoder's "
+                         "colours), got %s" % (tuple(tr.shape), tuple(all_rgb.shape)))
+    B = tr.shape[0]
+    geom = _geometry(cfg, kernel)
+    C = RgbSplat.apply(tr, all_rgb, geom, stop)                      # point_cloud.py:98-134
+    if not clip_after:
+        C = torch.clamp(C, 0.0, 1.0)                                 # :245-246
+    if kernel is not None:
+        C = Smooth.apply(C.reshape(B * 3, geom.D, geom.H, geom.W), geom).reshape(C.shape)   # convolve_rgb, :148-154
+    div = None
+    if divide:                                                       # :255-259: the RAW occupancies, gradient stopped
+        with torch.no_grad():
+            div = Splat.apply(tr.detach(), geom)
+            if kernel is not None:
+                div = Smooth.apply(div, geom)
+    return geom, vox.reshape(B, geom.D, geom.H, geom.W), C, div
+
+
+def _rgb_outputs(outputs):
+    if not isinstance(outputs, ProjectionOutputs):
+        raise TypeError("outputs must be what pointcloud_project_fast returned, got %s" % type(outputs).__name__)
+
+
+def project_rgb(cfg, outputs, all_rgb, kernel=None):
+    """The colour entries of the reference's output dict for the projection `outputs` (what pointcloud_project_fast
+    returned, called with all_rgb=None): {"proj_rgb": [B,H,W,3], "voxels_rgb": [B,D,H,W,3]}.
+
+    all_rgb [B,N,3]: one colour per projected point (rows like outputs["tr_pc"]; replicate_rgb).  The colours are splatted
+    with the points' trilinear weights into the cells of the occupancy splat (dpc/util/point_cloud.py:98-134; no gradient
+    from the weights to the points under pc_rgb_stop_points_gradient), clipped to [0,1] unless pc_rgb_clip_after_conv
+    (:245-246), smoothed per channel with `kernel` (convolve_rgb, :148-154; None: no smoothing), divided by the smoothed raw
+    occupancies + pc_rgb_divide_by_occupancies_epsilon under pc_rgb_divide_by_occupancies (:255-259), clipped under
+    pc_rgb_clip_after_conv (:261-262), flipped along the image rows (:276) and integrated along every ray with the
+    ray-termination probabilities of outputs["voxels"] over a white background (project_volume_rgb_integral,
+    dpc/util/drc.py:132-142).  `kernel` must be the one the projection was made with.  Differentiable to all_rgb, to the
+    points, pose, translation and focal length through outputs["tr_pc"], and to everything behind outputs["voxels"].
+    The colour splat adds with fp32 atomics: results may differ in the last bits from run to run."""
+    _rgb_outputs(outputs)
+    _, clip_after, _, div_eps = _rgb_options(cfg)
+    geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel)
+    proj_rgb = RgbMap.apply(vox, C, div, geom, div_eps, clip_after)
+    Cf = C if div is None else C / (div.unsqueeze(1) + div_eps)
+    if clip_after:
+        Cf = torch.clamp(Cf, 0.0, 1.0)
+    return {"proj_rgb": proj_rgb, "voxels_rgb": torch.flip(Cf.permute(0, 2, 3, 4, 1), [2])}
+
+
+def proj_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None, return_rgb=False):
+    """add_proj_rgb_loss (dpc/util/losses.py:69-90) without its weight: (1/2) sum_s w_s^2 sum_{pix,c} (g - proj_rgb)^2 / S on
+    the colour projection of project_rgb.  return_rgb: (loss, proj_rgb [S,H,W,3] detached) -- the image the loss was
+    formed from, written by the same launch.
+
+    outputs: what pointcloud_project_fast returned for S clouds (one per sample; fused or staged, both provide tr_pc and
+    voxels); all_rgb [S,N,3]; images: inputs["images"], [S,Hi,Wi,3] or [S,3,Hi,Wi] with Hi = f*H, Wi = f*W for an integer
+    f >= 1 -- g[s,y,x,c] = images[s,f*y,f*x,c]: the reference's tf.image.resize_images (bilinear, TF-1, no align_corners)
+    maps output pixel y to source coordinate y * Hi / H = f*y, an integer, so it samples exactly there and this is the
+    reference's value.  valid_samples [S] | None: per-sample weights w, squared like proj_depth_loss's (None, the reference:
+    all ones).  The caller multiplies by cfg.proj_rgb_weight.  Splat and smoothing as in project_rgb; integral, squared
+    error and their backward are one column kernel each way (csrc/dpc_rgb.hip)."""
+    if _get(cfg, "pc_gauss_filter_gt_rgb", False):
+        raise NotImplementedError("pc_gauss_filter_gt_rgb: true -- smoothing of the ground-truth images is not implemented "
+                                  "(gauss_smoothen_image, dpc/util/losses.py:78-83)")
+    _rgb_outputs(outputs)
+    S, H, W = outputs["proj"].shape[0], outputs["proj"].shape[1], outputs["proj"].shape[2]
+    shape = tuple(images.shape)
+    if len(shape) != 4 or (shape[3] != 3 and shape[1] != 3):
+        raise ValueError("images must be [S,Hi,Wi,3] or [S,3,Hi,Wi], got %s" % (shape,))
+    planar = shape[3] != 3
+    Hi, Wi = (shape[2], shape[3]) if planar else (shape[1], shape[2])
+    if shape[0] != S:
+        raise NotImplementedError("pose_predict_num_candidates: %d projections for %d images -- the colour loss needs one "
+                                  "cloud per sample (colour for K pose candidates is not implemented)" % (S, shape[0]))
+    if Hi < H or Wi < W or Hi % H or Wi % W or Hi // H != Wi // W:
+        raise ValueError("images %dx%d are not an integer multiple of the %dx%d projections" % (Hi, Wi, H, W))
+    f = Hi // H
+    if f * H > 1024 or f * W > 1024:
+        raise ValueError("images %dx%d: sides above 1024 are not supported" % (Hi, Wi))
+    _, clip_after, _, div_eps = _rgb_options(cfg)
+    geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel)
+    loss, proj_rgb = RgbLoss.apply(vox, C, div, images, f, planar, valid_samples, geom, div_eps, clip_after)
+    return (loss, proj_rgb) if return_rgb else loss
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -912,3 +912,131 @@ class DepthLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _ddepth):
         return _depth_backward(ctx, dloss, None) + (None,) * 6
+
+
+# ------------------------------------------------------------------------------------------------------
+# Colour: splat, projection and loss (csrc/dpc_rgb.hip)
+# reference (TF-1 originals): dpc/util/point_cloud.py:98-134, 244-262, 275-277; dpc/util/drc.py:132-142; dpc/util/losses.py:69-90
+# ------------------------------------------------------------------------------------------------------
+class RgbSplat(torch.autograd.Function):
+    """The rgb half of pointcloud2voxels3d_fast: tr [B,N,3] (z,y,x), rgb [B,N,3] -> colour grid [B,3,D,H,W] (planar), the
+    points' trilinear weights times their colours, in the cells of the occupancy splat.  fp32 atomics: the grid is not
+    bit-reproducible from run to run.  stop_points_gradient (pc_rgb_stop_points_gradient): no gradient to tr."""
+
+    @staticmethod
+    def forward(ctx, tr, rgb, geom, stop_points_gradient=False):
+        dev = N.require_device(tr, rgb)
+        tr32, rgb32 = _f32(tr), _f32(rgb)
+        if tr32.dim() != 3 or tr32.shape[2] != 3 or tuple(rgb32.shape) != tuple(tr32.shape):
+            raise ValueError("rgb must hold one colour per point, [B,N,3] like the points %s, got %s"
+                             % (tuple(tr.shape), tuple(rgb.shape)))
+        B, Npts = tr32.shape[0], tr32.shape[1]
+        Z = geom.sized(B, Npts)
+        out = torch.empty((B, 3, geom.D, geom.H, geom.W), dtype=torch.float32, device=dev)
+        with _on(dev):
+            rc = N.lib().dpc_rgb_splat_fwd(Z.ref, _dp(tr32), _dp(rgb32), _dp(out), _stream(dev))
+        if rc != 0:
+            N.check(rc, "dpc_rgb_splat_fwd")
+        ctx.geom, ctx.saved, ctx.metas, ctx.stop = geom, (tr32, rgb32), (_meta(tr), _meta(rgb)), bool(stop_points_gradient)
+        return out
+
+    @staticmethod
+    def backward(ctx, dC):
+        tr32, rgb32 = ctx.saved
+        dev, geom = tr32.device, ctx.geom
+        Z = geom.sized(tr32.shape[0], tr32.shape[1])
+        dC32 = _f32(dC)
+        drgb = torch.empty_like(rgb32)
+        dtr = torch.empty_like(tr32) if (ctx.needs_input_grad[0] and not ctx.stop) else None
+        with _on(dev):
+            rc = N.lib().dpc_rgb_splat_bwd(Z.ref, _dp(tr32), _dp(rgb32), _dp(dC32), _dp(drgb), _dp(dtr), _stream(dev))
+        if rc != 0:
+            N.check(rc, "dpc_rgb_splat_bwd")
+        return _like_input(dtr, ctx.metas[0]), _like_input(drgb, ctx.metas[1]), None, None
+
+
+def _rgb_inputs(vox, C, div, geom):
+    dev = N.require_device(vox, C, div)
+    v32, c32, d32 = _f32(vox), _f32(C), _f32(div)
+    B = v32.shape[0]
+    if tuple(v32.shape) != (B, geom.D, geom.H, geom.W):
+        raise ValueError("voxels must be [B,%d,%d,%d], got %s" % (geom.D, geom.H, geom.W, tuple(vox.shape)))
+    if tuple(c32.shape) != (B, 3, geom.D, geom.H, geom.W):
+        raise ValueError("the colour grid must be [%d,3,%d,%d,%d], got %s" % (B, geom.D, geom.H, geom.W, tuple(C.shape)))
+    if d32 is not None and tuple(d32.shape) != tuple(v32.shape):
+        raise ValueError("the occupancies to divide by must be %s, got %s" % (tuple(v32.shape), tuple(div.shape)))
+    return dev, v32, c32, d32
+
+
+def _rgb_backward(ctx, dloss, dproj):
+    """One launch: d voxels and d colour grid (both overwritten) from the gradient arriving at the loss and / or the image."""
+    v32, c32, d32, gt32, w32, proj = ctx.saved
+    geom, dev, B = ctx.geom, v32.device, v32.shape[0]
+    Z = geom.sized(B, 0)
+    dvox, dC = torch.empty_like(v32), torch.empty_like(c32)
+    with _on(dev):
+        rc = N.lib().dpc_rgb_loss_bwd(Z.ref, _dp(v32), _dp(c32), _dp(d32), ctx.div_eps, ctx.clip_after, _dp(gt32), ctx.gt_factor,
+                                      ctx.gt_planar, _dp(w32), _dp(proj), _dp(_f32(dloss)), _dp(_f32(dproj)), _dp(dvox), _dp(dC),
+                                      _stream(dev))
+    if rc != 0:
+        N.check(rc, "dpc_rgb_loss_bwd")
+    return _like_input(dvox, ctx.metas[0]), _like_input(dC, ctx.metas[1])
+
+
+class RgbMap(torch.autograd.Function):
+    """project_volume_rgb_integral on the renderer's grids: voxels [B,D,H,W], colour grid [B,3,D,H,W] (after the
+    Gaussian), div [B,D,H,W] | None (smoothed raw occupancies to divide by, a constant) -> proj_rgb [B,H,W,3], rows flipped
+    like proj, white background.  One launch forward, one backward."""
+
+    @staticmethod
+    def forward(ctx, vox, C, div, geom, div_eps=0.01, clip_after=False):
+        dev, v32, c32, d32 = _rgb_inputs(vox, C, div, geom)
+        B = v32.shape[0]
+        Z = geom.sized(B, 0)
+        proj = torch.empty((B, geom.H, geom.W, 3), dtype=torch.float32, device=dev)
+        with _on(dev):
+            rc = N.lib().dpc_rgb_loss_fwd(Z.ref, _dp(v32), _dp(c32), _dp(d32), float(div_eps), int(bool(clip_after)), None, 1, 0,
+                                          None, _dp(proj), None, None, _stream(dev))
+        if rc != 0:
+            N.check(rc, "dpc_rgb_loss_fwd")
+        ctx.geom, ctx.saved, ctx.metas = geom, (v32, c32, d32, None, None, None), (_meta(vox), _meta(C))
+        ctx.div_eps, ctx.clip_after, ctx.gt_factor, ctx.gt_planar = float(div_eps), int(bool(clip_after)), 1, 0
+        return proj
+
+    @staticmethod
+    def backward(ctx, dproj):
+        return _rgb_backward(ctx, None, dproj) + (None,) * 4
+
+
+class RgbLoss(torch.autograd.Function):
+    """add_proj_rgb_loss on the renderer's grids: (1/2) sum_s w_s^2 sum (g - proj_rgb)^2 / S with g the images sampled at
+    (f*y, f*x).  gt [S,f*H,f*W,3], or [S,3,f*H,f*W] when gt_planar; weights [S] | None.  Returns (loss, proj_rgb [B,H,W,3]
+    detached: differentiate RgbMap for a gradient through the image itself).  Two launches forward (column kernel,
+    one-block finalize), one backward."""
+
+    @staticmethod
+    def forward(ctx, vox, C, div, gt, gt_factor, gt_planar, weights, geom, div_eps=0.01, clip_after=False):
+        dev, v32, c32, d32 = _rgb_inputs(vox, C, div, geom)
+        N.require_device(v32, gt, weights)
+        B, f = v32.shape[0], int(gt_factor)
+        gt32 = _f32(gt)
+        if gt32.numel() != B * 3 * f * geom.H * f * geom.W:
+            raise ValueError("images must hold %d x %d x %d x 3 values, got %s" % (B, f * geom.H, f * geom.W, tuple(gt.shape)))
+        w32 = _weights32(weights, B)
+        Z = geom.sized(B, 0)
+        tiles = torch.empty((B, (geom.H * geom.W + 255) // 256), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        proj = torch.empty((B, geom.H, geom.W, 3), dtype=torch.float32, device=dev)
+        with _on(dev):
+            rc = N.lib().dpc_rgb_loss_fwd(Z.ref, _dp(v32), _dp(c32), _dp(d32), float(div_eps), int(bool(clip_after)), _dp(gt32), f,
+                                          int(bool(gt_planar)), _dp(w32), _dp(proj), _dp(tiles), _dp(loss), _stream(dev))
+        if rc != 0:
+            N.check(rc, "dpc_rgb_loss_fwd")
+        ctx.geom, ctx.saved, ctx.metas = geom, (v32, c32, d32, gt32, w32, proj), (_meta(vox), _meta(C))
+        ctx.div_eps, ctx.clip_after, ctx.gt_factor, ctx.gt_planar = float(div_eps), int(bool(clip_after)), f, int(bool(gt_planar))
+        ctx.mark_non_differentiable(proj)
+        return loss, proj
+
+    @staticmethod
+    def backward(ctx, dloss, _dproj):
+        return _rgb_backward(ctx, dloss, None) + (None,) * 8
