@@ -409,6 +409,56 @@ int dpc_rgb_loss_bwd(const DpcParams* p, const float* vox, const float* C, const
                      const float* dloss, const float* dproj_rgb, float* dvox, float* dC, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Ray-consistency (DRC) losses, fused: the ray potentials sum_k p_k psi_k of the TF-1 original's drc_loss / add_drc_loss and
+ * drc_rgb_loss / add_drc_rgb_loss (dpc/util/losses.py:23-66, 93-110) over the probabilities of drc_event_probabilities
+ * (dpc/util/drc.py:48-106), without the [D+1,B,H,W] tensor.  One cloud per sample (S = B); p_0 = e^eps y_0, p_k = y_k A_k,
+ * p_D = e^eps A_D, A_k = prod_{j<k} (1 - y_j) as above; ray (b, y, x) belongs to image pixel (H-1-y, x); the ground truth is
+ * read at (f*row, f*col), f = gt_factor >= 1 (TF-1 resize_images without align_corners, integer factor); w = weights [S] |
+ * NULL (= 1), squared like the other losses'.  No 1/2 and no square: the caller applies drc_weight / drc_rgb_weight.
+ *
+ * Mask loss, from grid_wh of dpc_project_fwd with y_z as in dpc_depth_loss_fwd (D pass with host_kern_z / p->dev_taps_z,
+ * occupancy scale s [B] | NULL, clamps):
+ *   loss = sum_s w_s^2 sum_rays ((1 - g) sum_{k<D} p_k + g p_D) / S,   g = gt_mask[s, f*row, f*col], gt_mask [S, f*H, f*W].
+ *   sum_{k<D} p_k is summed, not taken as 1 - p_D (the e^eps factors: the probabilities do not add up to one).
+ * fwd: loss_tiles [B, ceil(H*W/256)] scratch, the ray tiles' costs, added in tile order by a one-block second launch (the
+ *   loss is the same bits on every run); loss [1].  Two launches.
+ * bwd: recomputes the column; the gradient arriving at every ray's cost is dloss w_s^2 / S (dloss: device scalar | NULL = 1).
+ *   Outputs: dgrid_wh [B,D,H,W], every element overwritten; ds [B] | NULL, the tiles' partials added in tile order inside
+ *   the launch.  One launch.  workspace: dpc_drc_workspace_bytes(p) bytes with the contract of dpc_depth_loss_bwd's: the first
+ *   4 * B bytes are tickets, ZERO ON ENTRY (zeroed by the caller once) and zero again when the launch has finished.
+ * D = 32, 64, 128 with a z kernel of effective radius <= 15 run with the column in registers; every other depth or kernel
+ * length takes a generic kernel.
+ *
+ * Colour loss, on the renderer's voxels vox [B,D,H,W] (y_k = clamp(vox, eps, 1 - eps)), the smoothed colour grid C
+ * [B,3,D,H,W] and div / div_eps / clip_after as in dpc_rgb_loss_fwd (c_k below is the colour its integral sees):
+ *   psi_k = sum_c (g_c - c_{c,k})^2,  psi_D = sum_c (g_c - 1)^2 (white background),  g = gt[s, f*row, f*col, :],
+ *   loss = sum_s w_s^2 sum_rays sum_k p_k psi_k / S;     gt [S,f*H,f*W,3], or [S,3,f*H,f*W] when gt_planar != 0.
+ * fwd: any D, one thread per ray, two launches (column kernel, one-block finalize); loss_tiles and loss as above.
+ * bwd: with r = dloss w_s^2 / S, every element overwritten: dC [B,3,D,H,W], dC_{c,k} = 2 r p_k (c_{c,k} - g_c) (times
+ *   1 / (div + div_eps), and zero where the after-clip acted); dvox [B,D,H,W], dL/dy_m = r (psi_m E_m A_m -
+ *   (sum_{k>m} psi_k p_k) / (1 - y_m)) through the clamp where eps <= vox <= 1 - eps.  One launch, no workspace: D = 32, 64
+ *   keep y and the prefix products in registers (vox, C, div are read once, dvox and dC written once); other depths park the
+ *   prefix products in dvox like dpc_rgb_loss_bwd.
+ *
+ * Return codes as in dpc_depth_loss_* / dpc_rgb_loss_*, before any launch: DPC_ERR_SHAPE for f < 1, f*H or f*W > 1024, a gt
+ * without loss or loss_tiles (fwd), p->point_replicas > 1 or p->point_index (colour); DPC_ERR_NULL for a missing grid, gt or
+ * output; B == 0: fwd writes a zero loss, bwd does nothing.  Nothing synchronises or allocates.
+ * Added without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_drc_workspace_bytes(const DpcParams* p);
+int dpc_drc_loss_fwd(const DpcParams* p, const float* grid_wh, const float* s, const float* host_kern_z, const float* gt_mask,
+                     int gt_factor, const float* weights, float* loss_tiles, float* loss, void* stream);
+int dpc_drc_loss_bwd(const DpcParams* p, const float* grid_wh, const float* s, const float* host_kern_z, const float* gt_mask,
+                     int gt_factor, const float* weights, const float* dloss, float* dgrid_wh, float* ds, void* workspace,
+                     void* stream);
+int dpc_drc_rgb_loss_fwd(const DpcParams* p, const float* vox, const float* C, const float* div, float div_eps, int clip_after,
+                         const float* gt, int gt_factor, int gt_planar, const float* weights, float* loss_tiles, float* loss,
+                         void* stream);
+int dpc_drc_rgb_loss_bwd(const DpcParams* p, const float* vox, const float* C, const float* div, float div_eps, int clip_after,
+                         const float* gt, int gt_factor, int gt_planar, const float* weights, const float* dloss, float* dvox,
+                         float* dC, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Evaluation side: point_cloud_distance (dpc/util/point_cloud_distance.py:25-40), the kernel of
  * the Chamfer evaluation (dpc/run/eval_chamfer_to.py:24-44).  For every source point vs[i] ([ns,3]) the nearest target
  * vt[j] ([nt,3]): idx[i] = first j minimising dist = sqrt(sum((vt[j]-vs[i])^2)) (int64, like torch.argmin),

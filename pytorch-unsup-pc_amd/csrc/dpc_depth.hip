@@ -29,24 +29,6 @@ __device__ inline float depth_gt(const DepthLoss& dl, const DpcParams& P, int b,
   return (g == dl.max_dataset_depth && dl.max_dataset_depth != P.max_depth) ? P.max_depth : g;
 }
 
-// Tap k of the generic kernels' run-time-length z kernel, read where it lies -- the launch's argument block, or device memory
-// under a DeviceSchedule (DpcParams.dev_taps_z) -- without a private copy of the table (which would live in scratch).
-__device__ inline float dyn_tap(const TapsDyn& host, const float* __restrict__ dev, int k) {
-  return dev != nullptr ? dev[k] : host.w[k];
-}
-
-// this tile's sum over the block -> out[cloud, tile] (no atomics: the tiles are added in order later)
-__device__ inline float tile_sum(float v) {
-  __shared__ float red[kColThreads / DPC_WAVE];
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float tot = 0.f;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < kColThreads / DPC_WAVE; ++i) tot += red[i];
-  return tot;   // valid in thread 0
-}
-
 // Epilogue of the forward kernels: the depth at the row-flipped pixel, this tile's squared error.
 __device__ inline void depth_fwd_epilogue(const DpcParams& P, const Blk& bk, int ray, bool live, double d, float g,
                                           const DepthLoss& dl, float* __restrict__ depth, float* __restrict__ loss_tiles) {
@@ -183,25 +165,6 @@ __global__ __launch_bounds__(256) void k_depth_loss_finalize(const float* __rest
 // gradient arriving at this ray's depth: from the loss, (1/2) w^2 (g - depth)^2 / S times dloss, plus the caller's own
 __device__ inline float depth_grad(const DepthLoss& dl, float w2, float up, float g, float gin, float d) {
   return dl.gt != nullptr ? fmaf(up * w2 * dl.inv_S, d - g, gin) : gin;
-}
-
-// The ds partials of a cloud's ray tiles are handed over inside the launch (the hand-off of camgrad_publish, dpc_kernels.h:
-// write-through store, the storing wave's vmcnt(0), one agent-scope ticket add) and added in tile order by the workgroup
-// that drew the last ticket: ds is the same bits on every run.  The tickets are zero when the launch starts (the caller's
-// workspace contract, dpc_render.h) and the last workgroup leaves its cloud's ticket at zero again for the next launch.
-__device__ inline void depth_ds_publish(float ds_acc, const Blk& bk, float* __restrict__ ds_part, unsigned int* __restrict__ ds_count,
-                                        float* __restrict__ ds) {
-  const float tot = tile_sum(ds_acc);
-  if (threadIdx.x != 0) return;
-  float* mine = ds_part + (size_t)bk.y * bk.nx;
-  __hip_atomic_store(mine + bk.x, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the store has left this wave before the ticket is drawn
-  const unsigned int ticket = __hip_atomic_fetch_add(ds_count + bk.y, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (ticket != (unsigned int)(bk.nx - 1)) return;   // somebody else arrives later and does the sum
-  float sum = 0.f;
-  for (int i = 0; i < bk.nx; ++i) sum += __hip_atomic_load(mine + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  ds[bk.y] = sum;
-  __hip_atomic_store(ds_count + bk.y, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next backward
 }
 
 template <int DD, int RB>
@@ -361,12 +324,6 @@ __global__ __launch_bounds__(kColThreads) void k_depth_bwd_dyn(DpcParams P, RayH
 // Host side.  Workspace of the backward (dpc_depth_workspace_bytes): [tickets B][ds partials B x ntile][dv grid, generic kernel]
 // The tickets come first: they are the part the caller hands over zeroed (the first 4 B bytes, dpc_render.h).
 // ------------------------------------------------------------------------------------------------------
-inline bool column_depth(const DpcParams* p) { return p->D == 32 || p->D == 64 || p->D == 128; }
-// the generic backward may be needed: another depth, or a z kernel that can be longer than the largest compiled window
-inline bool may_need_dv(const DpcParams* p) { return !column_depth(p) || p->taps_z > 2 * 15 + 1; }
-inline size_t ws_ds_bytes(const DpcParams* p) { return ws_round((size_t)p->B * col_tiles(p) * sizeof(float)); }
-inline size_t ws_count_bytes(const DpcParams* p) { return ws_round((size_t)p->B * sizeof(unsigned int)); }
-
 struct DepthCall {
   TapPlan pz;
   DepthLoss dl;

@@ -891,6 +891,103 @@ __device__ inline void camgrad_publish(double tot, int tid, const CameraRaw& raw
   }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Shared by the column kernels of the loss nodes (dpc_depth.hip, dpc_rgb.hip, dpc_drc_loss.hip)
+// ------------------------------------------------------------------------------------------------------
+// Tap k of the generic kernels' run-time-length z kernel, read where it lies -- the launch's argument block, or device memory
+// under a DeviceSchedule (DpcParams.dev_taps_z) -- without a private copy of the table (which would live in scratch).
+__device__ inline float dyn_tap(const TapsDyn& host, const float* __restrict__ dev, int k) {
+  return dev != nullptr ? dev[k] : host.w[k];
+}
+
+// this tile's sum over the block -> out[cloud, tile] (no atomics: the tiles are added in order later)
+__device__ inline float tile_sum(float v) {
+  __shared__ float red[kColThreads / DPC_WAVE];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float tot = 0.f;
+  if (threadIdx.x == 0)
+    for (int i = 0; i < kColThreads / DPC_WAVE; ++i) tot += red[i];
+  return tot;   // valid in thread 0
+}
+
+// The ds partials of a cloud's ray tiles are handed over inside the launch (the hand-off of camgrad_publish above:
+// write-through store, the storing wave's vmcnt(0), one agent-scope ticket add) and added in tile order by the workgroup
+// that drew the last ticket: ds is the same bits on every run.  The tickets are zero when the launch starts (the caller's
+// workspace contract, dpc_render.h) and the last workgroup leaves its cloud's ticket at zero again for the next launch.
+__device__ inline void depth_ds_publish(float ds_acc, const Blk& bk, float* __restrict__ ds_part, unsigned int* __restrict__ ds_count,
+                                        float* __restrict__ ds) {
+  const float tot = tile_sum(ds_acc);
+  if (threadIdx.x != 0) return;
+  float* mine = ds_part + (size_t)bk.y * bk.nx;
+  __hip_atomic_store(mine + bk.x, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the store has left this wave before the ticket is drawn
+  const unsigned int ticket = __hip_atomic_fetch_add(ds_count + bk.y, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (ticket != (unsigned int)(bk.nx - 1)) return;   // somebody else arrives later and does the sum
+  float sum = 0.f;
+  for (int i = 0; i < bk.nx; ++i) sum += __hip_atomic_load(mine + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  ds[bk.y] = sum;
+  __hip_atomic_store(ds_count + bk.y, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next backward
+}
+
+// What the colour column kernels need besides the grids (uniform per launch).
+struct RgbArgs {
+  const float* div;      // [B,D,H,W] smoothed raw occupancies | nullptr: no division (point_cloud.py:255-259)
+  float div_eps;
+  int clip_after;        // clamp(C, 0, 1) after the division (:261-262)
+  const float* gt;       // images [S,f*H,f*W,3], or [S,3,f*H,f*W] when planar | nullptr: projection only
+  int f, planar;
+  const float* weights;  // [S] | nullptr = 1
+  float inv_S;
+};
+
+// ground truth of the image pixel (prow, pcol): images[s, f*prow, f*pcol, :] -- TF-1's bilinear resize_images without
+// align_corners samples exactly there for an integer factor (losses.py:74-77)
+__device__ inline void rgb_gt(const RgbArgs& a, const DpcParams& P, int b, int prow, int pcol, float (&g)[3]) {
+  const size_t Hi = (size_t)a.f * P.H, Wi = (size_t)a.f * P.W, y = (size_t)prow * a.f, x = (size_t)pcol * a.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    g[c] = a.planar ? a.gt[(((size_t)b * 3 + c) * Hi + y) * Wi + x] : a.gt[(((size_t)b * Hi + y) * Wi + x) * 3 + c];
+}
+
+// the colour the integral sees at one voxel: C / (div + eps), clamped when clip_after; `scale` = d value / d C
+__device__ inline float rgb_value(const RgbArgs& a, float c, float dv, float& scale) {
+  scale = 1.0f;
+  if (a.div != nullptr) {
+    scale = 1.0f / (dv + a.div_eps);
+    c *= scale;
+  }
+  if (a.clip_after) {
+    if (!(c >= 0.f && c <= 1.f)) scale = 0.f;   // torch.clamp's backward: the gradient passes inside [0, 1]
+    c = fminf(fmaxf(c, 0.f), 1.f);
+  }
+  return c;
+}
+
+// Workspace of the backwards that reduce ds (dpc_depth_workspace_bytes, dpc_drc_workspace_bytes):
+// [tickets B][ds partials B x ntile][dv grid, generic kernel]
+inline bool column_depth(const DpcParams* p) { return p->D == 32 || p->D == 64 || p->D == 128; }
+// the generic backward may be needed: another depth, or a z kernel that can be longer than the largest compiled window
+inline bool may_need_dv(const DpcParams* p) { return !column_depth(p) || p->taps_z > 2 * 15 + 1; }
+inline size_t ws_ds_bytes(const DpcParams* p) { return ws_round((size_t)p->B * col_tiles(p) * sizeof(float)); }
+inline size_t ws_count_bytes(const DpcParams* p) { return ws_round((size_t)p->B * sizeof(unsigned int)); }
+
+// argument checks shared by the colour entry points
+inline int rgb_validate(const DpcParams* p) {
+  const int rc = validate(p);
+  if (rc != DPC_OK) return rc;
+  if (p->point_replicas > 1 || p->point_index != nullptr) return DPC_ERR_SHAPE;   // one row of points and colours per cloud
+  return DPC_OK;
+}
+
+inline int rgb_check(const DpcParams* p, int gt_factor) {
+  const int rc = rgb_validate(p);
+  if (rc != DPC_OK) return rc;
+  if (gt_factor < 1 || (long long)gt_factor * p->H > 1024 || (long long)gt_factor * p->W > 1024) return DPC_ERR_SHAPE;
+  return DPC_OK;
+}
+
 // ---- launchers defined next to their kernels (bucket = compile-time tap radius bucket chosen by plan_taps) ----
 int launch_locate(const DpcParams* p, int src, const void* pts, const float* q, const float* t, const float* f, float* tr_pc,
                   void* cells, hipStream_t st);

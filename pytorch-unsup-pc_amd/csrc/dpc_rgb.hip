@@ -104,40 +104,6 @@ __global__ __launch_bounds__(kRgbThreads) void k_rgb_splat_bwd(DpcParams P, cons
 // ------------------------------------------------------------------------------------------------------
 // Column kernels.  One thread per ray (b, y, x), x fastest: every plane read and write is coalesced.
 // ------------------------------------------------------------------------------------------------------
-// What the kernels need besides the grids (uniform per launch).
-struct RgbArgs {
-  const float* div;      // [B,D,H,W] smoothed raw occupancies | nullptr: no division (point_cloud.py:255-259)
-  float div_eps;
-  int clip_after;        // clamp(C, 0, 1) after the division (:261-262)
-  const float* gt;       // images [S,f*H,f*W,3], or [S,3,f*H,f*W] when planar | nullptr: projection only
-  int f, planar;
-  const float* weights;  // [S] | nullptr = 1
-  float inv_S;
-};
-
-// ground truth of the image pixel (prow, pcol): images[s, f*prow, f*pcol, :] -- TF-1's bilinear resize_images without
-// align_corners samples exactly there for an integer factor (losses.py:74-77)
-__device__ inline void rgb_gt(const RgbArgs& a, const DpcParams& P, int b, int prow, int pcol, float (&g)[3]) {
-  const size_t Hi = (size_t)a.f * P.H, Wi = (size_t)a.f * P.W, y = (size_t)prow * a.f, x = (size_t)pcol * a.f;
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-    g[c] = a.planar ? a.gt[(((size_t)b * 3 + c) * Hi + y) * Wi + x] : a.gt[(((size_t)b * Hi + y) * Wi + x) * 3 + c];
-}
-
-// the colour the integral sees at one voxel: C / (div + eps), clamped when clip_after; `scale` = d value / d C
-__device__ inline float rgb_value(const RgbArgs& a, float c, float dv, float& scale) {
-  scale = 1.0f;
-  if (a.div != nullptr) {
-    scale = 1.0f / (dv + a.div_eps);
-    c *= scale;
-  }
-  if (a.clip_after) {
-    if (!(c >= 0.f && c <= 1.f)) scale = 0.f;   // torch.clamp's backward: the gradient passes inside [0, 1]
-    c = fminf(fmaxf(c, 0.f), 1.f);
-  }
-  return c;
-}
-
 // this tile's sum over the block (valid in thread 0): no atomics, the tiles are added in order by the finalize
 __device__ inline float rgb_tile_sum(float v) {
   __shared__ float red[kColThreads / DPC_WAVE];
@@ -276,21 +242,6 @@ __global__ __launch_bounds__(kColThreads) void k_rgb_bwd(DpcParams P, double e_e
     gv[at] = (v >= eps && v <= hi) ? (float)dy : 0.f;
     suffix = fma(am, pm, suffix);
   }
-}
-
-// argument checks shared by the entry points
-int rgb_validate(const DpcParams* p) {
-  const int rc = validate(p);
-  if (rc != DPC_OK) return rc;
-  if (p->point_replicas > 1 || p->point_index != nullptr) return DPC_ERR_SHAPE;   // one row of points and colours per cloud
-  return DPC_OK;
-}
-
-int rgb_check(const DpcParams* p, int gt_factor) {
-  const int rc = rgb_validate(p);
-  if (rc != DPC_OK) return rc;
-  if (gt_factor < 1 || (long long)gt_factor * p->H > 1024 || (long long)gt_factor * p->W > 1024) return DPC_ERR_SHAPE;
-  return DPC_OK;
 }
 
 }  // namespace

@@ -31,9 +31,10 @@ def chair_unsupervised(**overrides):
         camera_distance=2.0, focal_length=1.875, drc_logsum_clip_val=1e-5, max_depth=10.0, max_dataset_depth=10.0,
         pc_fast=True, pose_quaternion=True, pc_separable_gauss_filter=True, drc_logsum=True, drc_tf_cumulative=True,
         ptn_max_projection=False,
-        # colour (default_config.yaml:61-66, 94, 113)
+        # colour (default_config.yaml:61-66, 94, 113-114)
         pc_rgb=False, pc_rgb_stop_points_gradient=False, pc_rgb_clip_after_conv=False, pc_rgb_divide_by_occupancies=False,
         pc_rgb_divide_by_occupancies_epsilon=0.01, pc_rgb_deep_decoder=False, pc_gauss_filter_gt_rgb=False, proj_rgb_weight=0.0,
+        drc_rgb_weight=0.0,
         # schedules, loss, optimiser
         pc_point_dropout=0.07, pc_point_dropout_scheduled=True, pc_point_dropout_exponential_schedule=False,
         pc_point_dropout_start_step=0.0, pc_point_dropout_end_step=1.0, max_number_of_steps=600000,

@@ -21,6 +21,14 @@ Colour supervision (cfg.pc_rgb and cfg.proj_rgb_weight != 0, one pose candidate 
 dpc/util/losses.py:69-90): the decoder's per-point colours, replicated like the points, are projected on the same projection
 (dpc.render.proj_rgb_loss) and compared with the input images,
     total = proj_weight * (proj + student) + proj_depth_weight * depth + proj_rgb_weight * rgb.
+
+Ray-consistency terms (one pose candidate per image), further nodes on the same projection:
+    cfg.drc_weight != 0: add_drc_loss (dpc/util/losses.py:49-66; get_loss, model_pc_to.py:396-397) on the pooled masks --
+    add_proj_loss has replaced inputs['masks'] by them when add_drc_loss runs (:354-366) -- dpc.render.drc_loss;
+    cfg.pc_rgb and cfg.drc_rgb_weight != 0: add_drc_rgb_loss (losses.py:93-110), dpc.render.drc_rgb_loss, sharing the colour
+    grids with the colour loss above.  The reference defines that loss and its weight but never calls it from get_loss:
+    this term is the one place where the step goes beyond get_loss.
+    total += drc_weight * drc + drc_rgb_weight * drc_rgb.
 """
 import numpy as np
 import torch
@@ -122,6 +130,12 @@ class TrainStep:
         cfg = self.cfg
         depth_weight = cfg.get("proj_depth_weight", 0.0)
         rgb_weight = cfg.get("proj_rgb_weight", 0.0) if cfg.get("pc_rgb", False) else 0.0
+        drc_weight = cfg.get("drc_weight", 0.0)
+        drc_rgb_weight = cfg.get("drc_rgb_weight", 0.0) if cfg.get("pc_rgb", False) else 0.0
+        for key, weight in (("drc_weight", drc_weight), ("drc_rgb_weight", drc_rgb_weight)):
+            if weight != 0 and cfg.pose_predict_num_candidates != 1:
+                raise NotImplementedError("%s != 0 needs pose_predict_num_candidates == 1: with K candidates the reference's "
+                                          "ray potentials do not broadcast" % key)
         if rgb_weight != 0 and cfg.pose_predict_num_candidates != 1:
             raise NotImplementedError("proj_rgb_weight != 0 needs pose_predict_num_candidates == 1: colour for K pose "
                                       "candidates is not implemented")
@@ -150,9 +164,9 @@ class TrainStep:
                 host = np.stack([np.random.choice(all_points.shape[1], n_out, replace=False) for _ in range(clouds)])
                 point_index = torch.from_numpy(host.astype(np.int32)).to(all_points.device)
         kernel = R.smoothing_kernel(cfg, R.get_smooth_sigma(cfg, step))
-        if depth_weight != 0 or rgb_weight != 0:
-            # projection, silhouette loss and depth / colour losses as nodes on one projection: their gradients join the
-            # silhouette's at the projection's outputs (get_loss, model_pc_to.py:391-408 with losses.py:69-90, 113-136)
+        if depth_weight != 0 or rgb_weight != 0 or drc_weight != 0 or drc_rgb_weight != 0:
+            # projection, silhouette loss and depth / colour / ray-consistency losses as nodes on one projection: their gradients
+            # join the silhouette's at the projection's outputs (get_loss, model_pc_to.py:391-408 with losses.py:23-136)
             proj_out = R.pointcloud_project_fast(cfg, all_points, out["poses"], None, None, kernel, scaling_factor=all_scales,
                                                  point_index=point_index, schedule=sched)
             proj_loss, winner = R.silhouette_loss(proj_out["proj"], masks, K, valid_samples)
@@ -162,11 +176,23 @@ class TrainStep:
                 depth_loss, projs_depth = R.proj_depth_loss(cfg, proj_out, depths, valid_samples, return_depth=True)   # one pass
                 total = total + depth_loss.double() * depth_weight
                 out.update(depth_loss=depth_loss, projs_depth=projs_depth)
-            if rgb_weight != 0:
+            if drc_weight != 0:   # on the masks add_proj_loss pooled (model_pc_to.py:354-366), at their own size
+                drc = R.drc_loss(cfg, proj_out, out["pooled_masks"], valid_samples)
+                total = total + drc.double() * drc_weight
+                out.update(drc_loss=drc)
+            if rgb_weight != 0 or drc_rgb_weight != 0:
                 all_rgb = R.replicate_rgb(out["rgb_1"], out["poses"].shape[0], point_index)   # model_pc_to.py:254-258, 323-329
-                rgb_loss, projs_rgb = R.proj_rgb_loss(cfg, proj_out, all_rgb, images, kernel, valid_samples, return_rgb=True)
+                grids = R.rgb_grids(cfg, proj_out, all_rgb, kernel)   # one colour splat and smoothing for both colour terms
+                out.update(all_rgb=all_rgb)
+            if rgb_weight != 0:
+                rgb_loss, projs_rgb = R.proj_rgb_loss(cfg, proj_out, all_rgb, images, kernel, valid_samples, return_rgb=True,
+                                                      grids=grids)
                 total = total + rgb_loss.double() * rgb_weight
-                out.update(all_rgb=all_rgb, rgb_loss=rgb_loss, projs_rgb=projs_rgb)
+                out.update(rgb_loss=rgb_loss, projs_rgb=projs_rgb)
+            if drc_rgb_weight != 0:
+                drc_rgb = R.drc_rgb_loss(cfg, proj_out, all_rgb, images, kernel, valid_samples, grids=grids)
+                total = total + drc_rgb.double() * drc_rgb_weight
+                out.update(drc_rgb_loss=drc_rgb)
             return total, out
         proj_loss, proj_out, winner = R.pointcloud_project_loss(cfg, all_points, out["poses"], None, None, kernel,
                                                                 scaling_factor=all_scales, gt=masks, num_candidates=K,
@@ -230,6 +256,11 @@ class TrainStep:
             raise NotImplementedError("proj_depth_weight != 0: the depth-supervised step is eager only (no graph capture)")
         if self.cfg.get("pc_rgb", False) and self.cfg.get("proj_rgb_weight", 0.0) != 0:
             raise NotImplementedError("proj_rgb_weight != 0: the colour-supervised step is eager only (no graph capture)")
+        if self.cfg.get("drc_weight", 0.0) != 0:
+            raise NotImplementedError("drc_weight != 0: the step with the ray-consistency loss is eager only (no graph capture)")
+        if self.cfg.get("pc_rgb", False) and self.cfg.get("drc_rgb_weight", 0.0) != 0:
+            raise NotImplementedError("drc_rgb_weight != 0: the step with the ray-consistency colour loss is eager only "
+                                      "(no graph capture)")
 
     def capture_compute(self, images, masks, warmup=2, valid_samples=None):
         """The multi-rank variant of capture(): forward, loss and backward as ONE HIP graph whose backward accumulates

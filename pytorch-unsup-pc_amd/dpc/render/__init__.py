@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _native
-from ._ops import (DepthLoss, DepthMap, DeviceSchedule, Drc, Geometry, ProjectFused, ProjectLossFused, ProjectLossStep, RgbLoss, RgbMap, RgbSplat,
+from ._ops import (DepthLoss, DepthMap, DeviceSchedule, Drc, DrcLoss, DrcRgbLoss, Geometry, ProjectFused, ProjectLossFused, ProjectLossStep, RgbLoss, RgbMap, RgbSplat,
                    SilhouetteLoss, Smooth, Splat, Transform, status_word, taps_bucket)
 from ._ops import _plane as _ops_plane
 from .predictions import chamfer_of_predictions, load_predictions, save_predictions  # noqa: F401
@@ -39,7 +39,7 @@ __all__ = [
     "get_smooth_sigma", "get_dropout_prob", "ProjectionOutputs", "silhouette_loss", "pointcloud_project_loss",
     "point_cloud_distance", "compute_distance", "chamfer_distances", "graphed_project_loss", "prefer_direct_graph_launch", "point_dropout_indices", "save_predictions", "load_predictions", "chamfer_of_predictions",
     "DeviceSchedule", "check_status", "set_debug_checks", "taps_bucket", "project_loss_step", "project_depth", "proj_depth_loss",
-    "project_rgb", "proj_rgb_loss", "replicate_rgb",
+    "project_rgb", "proj_rgb_loss", "replicate_rgb", "rgb_grids", "drc_loss", "drc_rgb_loss",
     "icp_point_to_point", "alignment_to_ground_truth", "alignment_candidates", "reference_rotation", "quat_w_avg_markley",
     "quaternion_from_campos", "as_rotation_matrix", "from_rotation_matrix", "pose_errors",
     "nearest_batched", "chamfer_batched", "chamfer_loss", "chamfer_of_split", "eval_chamfer", "voxel_down_sample", "downsample_split",
@@ -767,7 +767,17 @@ def _rgb_outputs(outputs):
         raise TypeError("outputs must be what pointcloud_project_fast returned, got %s" % type(outputs).__name__)
 
 
-def project_rgb(cfg, outputs, all_rgb, kernel=None):
+def rgb_grids(cfg, outputs, all_rgb, kernel=None):
+    """The grids every colour function starts from, made once: (geom, voxels [B,D,H,W], smoothed colour grid [B,3,D,H,W],
+    occupancies to divide by | None) of the projection `outputs` and the colours all_rgb, as project_rgb describes them
+    (splat, pre-clip, per-channel smoothing; the smoothed raw occupancies under pc_rgb_divide_by_occupancies).  Hand the
+    result to project_rgb, proj_rgb_loss and drc_rgb_loss through `grids=`: they then share one colour splat and one set of
+    smoothing passes (most of a colour node's time) and their gradients add up at the grids."""
+    _rgb_outputs(outputs)
+    return _rgb_grids(cfg, outputs, all_rgb, kernel)
+
+
+def project_rgb(cfg, outputs, all_rgb, kernel=None, grids=None):
     """The colour entries of the reference's output dict for the projection `outputs` (what pointcloud_project_fast
     returned, called with all_rgb=None): {"proj_rgb": [B,H,W,3], "voxels_rgb": [B,D,H,W,3]}.
 
@@ -780,10 +790,11 @@ def project_rgb(cfg, outputs, all_rgb, kernel=None):
     ray-termination probabilities of outputs["voxels"] over a white background (project_volume_rgb_integral,
     dpc/util/drc.py:132-142).  `kernel` must be the one the projection was made with.  Differentiable to all_rgb, to the
     points, pose, translation and focal length through outputs["tr_pc"], and to everything behind outputs["voxels"].
-    The colour splat adds with fp32 atomics: results may differ in the last bits from run to run."""
+    The colour splat adds with fp32 atomics: results may differ in the last bits from run to run.
+    grids: what rgb_grids(cfg, outputs, all_rgb, kernel) returned, to share it with other colour functions (None: made here)."""
     _rgb_outputs(outputs)
     _, clip_after, _, div_eps = _rgb_options(cfg)
-    geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel)
+    geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel) if grids is None else grids
     proj_rgb = RgbMap.apply(vox, C, div, geom, div_eps, clip_after)
     Cf = C if div is None else C / (div.unsqueeze(1) + div_eps)
     if clip_after:
@@ -791,7 +802,26 @@ def project_rgb(cfg, outputs, all_rgb, kernel=None):
     return {"proj_rgb": proj_rgb, "voxels_rgb": torch.flip(Cf.permute(0, 2, 3, 4, 1), [2])}
 
 
-def proj_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None, return_rgb=False):
+def _image_factor(outputs, images, what):
+    """(planar, f) of images [S,Hi,Wi,3] or [S,3,Hi,Wi] against the projection's [S,H,W]: Hi = f*H, Wi = f*W, integer f >= 1."""
+    S, H, W = outputs["proj"].shape[0], outputs["proj"].shape[1], outputs["proj"].shape[2]
+    shape = tuple(images.shape)
+    if len(shape) != 4 or (shape[3] != 3 and shape[1] != 3):
+        raise ValueError("images must be [S,Hi,Wi,3] or [S,3,Hi,Wi], got %s" % (shape,))
+    planar = shape[3] != 3
+    Hi, Wi = (shape[2], shape[3]) if planar else (shape[1], shape[2])
+    if shape[0] != S:
+        raise NotImplementedError("pose_predict_num_candidates: %d projections for %d images -- the %s needs one "
+                                  "cloud per sample (colour for K pose candidates is not implemented)" % (S, shape[0], what))
+    if Hi < H or Wi < W or Hi % H or Wi % W or Hi // H != Wi // W:
+        raise ValueError("images %dx%d are not an integer multiple of the %dx%d projections" % (Hi, Wi, H, W))
+    f = Hi // H
+    if f * H > 1024 or f * W > 1024:
+        raise ValueError("images %dx%d: sides above 1024 are not supported" % (Hi, Wi))
+    return planar, f
+
+
+def proj_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None, return_rgb=False, grids=None):
     """add_proj_rgb_loss (dpc/util/losses.py:69-90) without its weight: (1/2) sum_s w_s^2 sum_{pix,c} (g - proj_rgb)^2 / S on
     the colour projection of project_rgb.  return_rgb: (loss, proj_rgb [S,H,W,3] detached) -- the image the loss was
     formed from, written by the same launch.
@@ -802,29 +832,91 @@ def proj_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None
     maps output pixel y to source coordinate y * Hi / H = f*y, an integer, so it samples exactly there and this is the
     reference's value.  valid_samples [S] | None: per-sample weights w, squared like proj_depth_loss's (None, the reference:
     all ones).  The caller multiplies by cfg.proj_rgb_weight.  Splat and smoothing as in project_rgb; integral, squared
-    error and their backward are one column kernel each way (csrc/dpc_rgb.hip)."""
+    error and their backward are one column kernel each way (csrc/dpc_rgb.hip).  grids: as in project_rgb."""
     if _get(cfg, "pc_gauss_filter_gt_rgb", False):
         raise NotImplementedError("pc_gauss_filter_gt_rgb: true -- smoothing of the ground-truth images is not implemented "
                                   "(gauss_smoothen_image, dpc/util/losses.py:78-83)")
     _rgb_outputs(outputs)
-    S, H, W = outputs["proj"].shape[0], outputs["proj"].shape[1], outputs["proj"].shape[2]
-    shape = tuple(images.shape)
-    if len(shape) != 4 or (shape[3] != 3 and shape[1] != 3):
-        raise ValueError("images must be [S,Hi,Wi,3] or [S,3,Hi,Wi], got %s" % (shape,))
-    planar = shape[3] != 3
-    Hi, Wi = (shape[2], shape[3]) if planar else (shape[1], shape[2])
-    if shape[0] != S:
-        raise NotImplementedError("pose_predict_num_candidates: %d projections for %d images -- the colour loss needs one "
-                                  "cloud per sample (colour for K pose candidates is not implemented)" % (S, shape[0]))
-    if Hi < H or Wi < W or Hi % H or Wi % W or Hi // H != Wi // W:
-        raise ValueError("images %dx%d are not an integer multiple of the %dx%d projections" % (Hi, Wi, H, W))
-    f = Hi // H
-    if f * H > 1024 or f * W > 1024:
-        raise ValueError("images %dx%d: sides above 1024 are not supported" % (Hi, Wi))
+    planar, f = _image_factor(outputs, images, "colour loss")
     _, clip_after, _, div_eps = _rgb_options(cfg)
-    geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel)
+    geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel) if grids is None else grids
     loss, proj_rgb = RgbLoss.apply(vox, C, div, images, f, planar, valid_samples, geom, div_eps, clip_after)
     return (loss, proj_rgb) if return_rgb else loss
+
+
+# ------------------------------------------------------------------------------------------------------
+# Ray-consistency (DRC) losses         reference (TF-1 originals): dpc/util/losses.py:23-66, 93-110
+# ------------------------------------------------------------------------------------------------------
+def _check_drc_grid(cfg):
+    vz = int(_get(cfg, "vox_size_z", -1))
+    if vz != -1 and vz != int(cfg.vox_size):
+        raise NotImplementedError("vox_size_z: %d with vox_size %d -- the reference's ray potentials tile the ground truth "
+                                  "cfg.vox_size times along the ray and do not broadcast against %d probabilities "
+                                  "(dpc/util/losses.py:25, 35)" % (vz, int(cfg.vox_size), vz + 1))
+
+
+def drc_loss(cfg, outputs, masks, valid_samples=None):
+    """add_drc_loss (dpc/util/losses.py:23-29, 49-66) without its weight: sum_s w_s^2 sum_rays ((1 - g) sum_{k<D} p_k + g p_D) / S,
+    the ray-consistency cost of the masks under the ray-termination probabilities p of outputs["drc_probs"] -- a ray that
+    ends in a voxel pays 1 - g, one that escapes pays g.  No 1/2 and no square.
+
+    outputs: what pointcloud_project_fast returned for S clouds (one per sample); masks [S,1,Hm,Wm], [S,Hm,Wm,1] or [S,Hm,Wm]
+    with Hm = f*H, Wm = f*W for an integer f >= 1 -- g[s,y,x] = masks[s,f*y,f*x], where the reference's
+    tf.image.resize_images (bilinear, TF-1, no align_corners) samples for an integer factor (proj_rgb_loss explains).
+    The reference's caller hands over the masks add_proj_loss pooled (model_pc_to.py:354-366, 396-397): pool them first for
+    its numbers (f = 1).  valid_samples [S] | None: per-sample weights w, squared like the other losses'.  The caller
+    multiplies by cfg.drc_weight.  On the fused path the loss is two launches forward and one backward on the fused node's
+    grid (csrc/dpc_drc_loss.hip), a node on (grid_wh, scaling_factor); outputs of the staged fallback get the same numbers
+    from outputs["drc_probs"] with torch."""
+    if _get(cfg, "pc_gauss_filter_gt", False):
+        raise NotImplementedError("pc_gauss_filter_gt: true -- smoothing of the ground-truth masks is not implemented "
+                                  "(the reference's torch port prints 'Not implemented' there, model_pc_to.py:355-356)")
+    _check_drc_grid(cfg)
+    fused = _fused_parts(outputs)
+    S, H, W = outputs["proj"].shape[0], outputs["proj"].shape[1], outputs["proj"].shape[2]
+    plane = _ops_plane(tuple(masks.shape))
+    if plane is None:
+        raise ValueError("masks must be [S,1,Hm,Wm], [S,Hm,Wm,1] or [S,Hm,Wm], got %s" % (tuple(masks.shape),))
+    if masks.shape[0] != S:
+        raise NotImplementedError("pose_predict_num_candidates: %d projections for %d masks -- the drc loss needs one cloud "
+                                  "per sample (with K candidates the reference's shapes do not broadcast)" % (S, masks.shape[0]))
+    Hm, Wm = plane
+    if Hm < H or Wm < W or Hm % H or Wm % W or Hm // H != Wm // W:
+        raise ValueError("masks %dx%d are not an integer multiple of the %dx%d projections" % (Hm, Wm, H, W))
+    f = Hm // H
+    if f * H > 1024 or f * W > 1024:
+        raise ValueError("masks %dx%d: sides above 1024 are not supported" % (Hm, Wm))
+    if fused is not None:
+        geom, grid_wh, s = fused
+        return DrcLoss.apply(grid_wh, s, masks, f, valid_samples, geom)
+    p = outputs["drc_probs"][..., 0]                                   # [D+1,S,H,W], rows in image order
+    g = masks.reshape(S, Hm, Wm)[:, ::f, ::f].to(p.dtype)
+    cost = ((1.0 - g) * p[:-1].sum(0) + g * p[-1]).sum((1, 2))
+    if valid_samples is not None:
+        cost = cost * valid_samples.to(cost.dtype) ** 2
+    return cost.sum() / S
+
+
+def drc_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None, grids=None):
+    """add_drc_rgb_loss (dpc/util/losses.py:32-46, 93-110) without its weight: sum_s w_s^2 sum_rays sum_k p_k psi_k / S with
+    psi_k = sum_c (g_c - voxels_rgb_{k,c})^2 the squared distance of the colour of voxel k on the ray from the image's pixel,
+    psi_D = sum_c (g_c - 1)^2 for the white background, and p the ray-termination probabilities of outputs["voxels"].
+
+    outputs, all_rgb, images, kernel, valid_samples and the options read from cfg are proj_rgb_loss's (voxels_rgb is
+    project_rgb's: division by the occupancies, clip after the convolution); images are read at (f*y, f*x).  The reference
+    defines this loss and its weight key (drc_rgb_weight) but never calls it from get_loss; the caller multiplies by the
+    weight.  A node on (voxels, colour grid): one column kernel each way (csrc/dpc_drc_loss.hip), nothing of the size of
+    [D+1,B,H,W] or [B,D,H,W,3] is built.  grids: as in project_rgb -- shared with proj_rgb_loss, the two losses cost one
+    splat and one set of smoothing passes."""
+    if _get(cfg, "pc_gauss_filter_gt_rgb", False):
+        raise NotImplementedError("pc_gauss_filter_gt_rgb: true -- smoothing of the ground-truth images is not implemented "
+                                  "(gauss_smoothen_image, dpc/util/losses.py:78-83)")
+    _check_drc_grid(cfg)
+    _rgb_outputs(outputs)
+    planar, f = _image_factor(outputs, images, "drc colour loss")
+    _, clip_after, _, div_eps = _rgb_options(cfg)
+    geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel) if grids is None else grids
+    return DrcRgbLoss.apply(vox, C, div, images, f, planar, valid_samples, geom, div_eps, clip_after)
 
 
 # ------------------------------------------------------------------------------------------------------

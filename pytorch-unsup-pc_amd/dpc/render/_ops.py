@@ -1040,3 +1040,90 @@ class RgbLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dproj):
         return _rgb_backward(ctx, dloss, None) + (None,) * 8
+
+
+# ------------------------------------------------------------------------------------------------------
+# Ray-consistency (DRC) mask and colour losses (csrc/dpc_drc_loss.hip)
+# reference (TF-1 originals): dpc/util/losses.py:23-66, 93-110 on dpc/util/drc.py:48-106
+# ------------------------------------------------------------------------------------------------------
+class DrcLoss(torch.autograd.Function):
+    """add_drc_loss on the fused path: grid_wh [B,D,H,W], s [B,1] | None, gt [S,f*H,f*W] masks (S = B), weights [S] | None ->
+    sum_s w_s^2 sum_rays ((1 - g) sum_{k<D} p_k + g p_D) / S with g the mask at (f*row, f*col).  Two launches forward (column
+    kernel, one-block finalize), one backward; the backward's workspace is the depth loss's (same contract, kept per stream)."""
+
+    @staticmethod
+    def forward(ctx, grid_wh, s, gt, gt_factor, weights, geom):
+        dev, g32, s32 = _depth_inputs(grid_wh, s, geom)
+        N.require_device(g32, gt, weights)
+        B, f = g32.shape[0], int(gt_factor)
+        gt32 = _f32(gt)
+        if gt32.numel() != B * f * geom.H * f * geom.W:
+            raise ValueError("masks must hold %d x %d x %d values, got %s" % (B, f * geom.H, f * geom.W, tuple(gt.shape)))
+        w32 = _weights32(weights, B)
+        Z = geom.sized(B, 0)
+        tiles = torch.empty((B, (geom.H * geom.W + 255) // 256), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        with _on(dev):
+            rc = N.lib().dpc_drc_loss_fwd(Z.ref, _dp(g32), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), f, _dp(w32), _dp(tiles),
+                                          _dp(loss), _stream(dev))
+        if rc != 0:
+            N.check(rc, "dpc_drc_loss_fwd")
+        ctx.geom, ctx.saved, ctx.metas, ctx.gt_factor = geom, (g32, s32, gt32, w32), (_meta(grid_wh), _meta(s)), f
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        grid_wh, s32, gt32, w32 = ctx.saved
+        geom, dev, B = ctx.geom, grid_wh.device, grid_wh.shape[0]
+        L = N.lib()
+        Z = geom.sized(B, 0)
+        dgrid = torch.empty_like(grid_wh)
+        ds = None if s32 is None else torch.empty((B,), dtype=torch.float32, device=dev)
+        with _on(dev):
+            ws = _depth_workspace(dev, max(L.dpc_drc_workspace_bytes(Z.ref), 16))
+            rc = L.dpc_drc_loss_bwd(Z.ref, _dp(grid_wh), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), ctx.gt_factor, _dp(w32),
+                                    _dp(_f32(dloss)), _dp(dgrid), _dp(ds), _dp(ws), _stream(dev))
+        if rc != 0:
+            N.check(rc, "dpc_drc_loss_bwd")
+        return _like_input(dgrid, ctx.metas[0]), _like_input(ds, ctx.metas[1]), None, None, None, None
+
+
+class DrcRgbLoss(torch.autograd.Function):
+    """add_drc_rgb_loss on the renderer's grids: sum_s w_s^2 sum_rays sum_k p_k psi_k / S, psi_k the squared distance of the
+    voxel's colour (the background's white) from the image at (f*row, f*col).  Inputs as RgbLoss's.  Two launches forward
+    (column kernel, one-block finalize), one backward."""
+
+    @staticmethod
+    def forward(ctx, vox, C, div, gt, gt_factor, gt_planar, weights, geom, div_eps=0.01, clip_after=False):
+        dev, v32, c32, d32 = _rgb_inputs(vox, C, div, geom)
+        N.require_device(v32, gt, weights)
+        B, f = v32.shape[0], int(gt_factor)
+        gt32 = _f32(gt)
+        if gt32.numel() != B * 3 * f * geom.H * f * geom.W:
+            raise ValueError("images must hold %d x %d x %d x 3 values, got %s" % (B, f * geom.H, f * geom.W, tuple(gt.shape)))
+        w32 = _weights32(weights, B)
+        Z = geom.sized(B, 0)
+        tiles = torch.empty((B, (geom.H * geom.W + 255) // 256), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        with _on(dev):
+            rc = N.lib().dpc_drc_rgb_loss_fwd(Z.ref, _dp(v32), _dp(c32), _dp(d32), float(div_eps), int(bool(clip_after)), _dp(gt32),
+                                              f, int(bool(gt_planar)), _dp(w32), _dp(tiles), _dp(loss), _stream(dev))
+        if rc != 0:
+            N.check(rc, "dpc_drc_rgb_loss_fwd")
+        ctx.geom, ctx.saved, ctx.metas = geom, (v32, c32, d32, gt32, w32), (_meta(vox), _meta(C))
+        ctx.div_eps, ctx.clip_after, ctx.gt_factor, ctx.gt_planar = float(div_eps), int(bool(clip_after)), f, int(bool(gt_planar))
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        v32, c32, d32, gt32, w32 = ctx.saved
+        geom, dev, B = ctx.geom, v32.device, v32.shape[0]
+        Z = geom.sized(B, 0)
+        dvox, dC = torch.empty_like(v32), torch.empty_like(c32)
+        with _on(dev):
+            rc = N.lib().dpc_drc_rgb_loss_bwd(Z.ref, _dp(v32), _dp(c32), _dp(d32), ctx.div_eps, ctx.clip_after, _dp(gt32),
+                                              ctx.gt_factor, ctx.gt_planar, _dp(w32), _dp(_f32(dloss)), _dp(dvox), _dp(dC),
+                                              _stream(dev))
+        if rc != 0:
+            N.check(rc, "dpc_drc_rgb_loss_bwd")
+        return (_like_input(dvox, ctx.metas[0]), _like_input(dC, ctx.metas[1])) + (None,) * 8
