@@ -892,7 +892,8 @@ __device__ inline void camgrad_publish(double tot, int tid, const CameraRaw& raw
 }
 
 // ------------------------------------------------------------------------------------------------------
-// Shared by the column kernels of the loss nodes (dpc_depth.hip, dpc_rgb.hip, dpc_drc_loss.hip)
+// Shared by the column kernels of the loss nodes (dpc_depth.hip, dpc_rgb.hip, dpc_drc_loss.hip); the column skeleton of the
+// ray potentials on grid_wh and its host side: dpc_ray_column.h
 // ------------------------------------------------------------------------------------------------------
 // Tap k of the generic kernels' run-time-length z kernel, read where it lies -- the launch's argument block, or device memory
 // under a DeviceSchedule (DpcParams.dev_taps_z) -- without a private copy of the table (which would live in scratch).
@@ -965,14 +966,6 @@ __device__ inline float rgb_value(const RgbArgs& a, float c, float dv, float& sc
   return c;
 }
 
-// Workspace of the backwards that reduce ds (dpc_depth_workspace_bytes, dpc_drc_workspace_bytes):
-// [tickets B][ds partials B x ntile][dv grid, generic kernel]
-inline bool column_depth(const DpcParams* p) { return p->D == 32 || p->D == 64 || p->D == 128; }
-// the generic backward may be needed: another depth, or a z kernel that can be longer than the largest compiled window
-inline bool may_need_dv(const DpcParams* p) { return !column_depth(p) || p->taps_z > 2 * 15 + 1; }
-inline size_t ws_ds_bytes(const DpcParams* p) { return ws_round((size_t)p->B * col_tiles(p) * sizeof(float)); }
-inline size_t ws_count_bytes(const DpcParams* p) { return ws_round((size_t)p->B * sizeof(unsigned int)); }
-
 // argument checks shared by the colour entry points
 inline int rgb_validate(const DpcParams* p) {
   const int rc = validate(p);
@@ -1007,6 +1000,9 @@ int launch_zcol_bwd(const DpcParams* p, const float* host_kern_z, const TapPlan&
                     unsigned int* cg_count, const float* dgrid_extra, const LossArgs& la, hipStream_t st);
 int launch_loss_finalize(const float* sse_tiles, int ntile, float* sse, int S, int K, float inv_S, const float* weights, float* loss,
                          int32_t* winner, hipStream_t st);
+// dpc_depth.hip: loss = scale sum_s w_s^2 (the sample's loss_tiles [B, col_tiles], in tile order), one block (k_tile_loss_finalize)
+int launch_tile_loss_finalize(const DpcParams* p, const float* loss_tiles, float scale, const float* weights, float* loss,
+                              hipStream_t st);
 // dpc_slab_xl.hip: the x-in-lanes slab kernels (64 x 64 planes, radius bucket 1..6); DPC_NO_XL builds keep the older kernels
 bool xl_applies(const DpcParams* p, int bucket);
 int launch_splat_xl(int bucket, const DpcParams* p, Cells cells, const float* kxy, const TapPlan& pxy, float* Tbuf, uint64_t* mask,

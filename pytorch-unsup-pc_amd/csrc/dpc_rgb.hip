@@ -1,7 +1,7 @@
 // Colour node of the projection: per-point RGB splatted with the points' trilinear weights (k_rgb_splat, its gather
 // backward k_rgb_splat_bwd), and column kernels that integrate the colour grid along each ray with the ray-termination
-// probabilities over a white background, with the squared-error loss against the input image (k_rgb_fwd, the loss's
-// one-block finalize k_rgb_loss_finalize, the hand-written backward k_rgb_bwd).
+// probabilities over a white background, with the squared-error loss against the input image (k_rgb_fwd, the hand-written
+// backward k_rgb_bwd; the tile sum and the loss's one-block finalize are the loss nodes' shared ones, dpc_kernels.h).
 // Reference (TF-1 originals): pointcloud2voxels3d_fast's rgb half (dpc/util/point_cloud.py:98-134), the clips, the division
 // by the occupancies and the flip of pointcloud_project_fast (:244-262, 275-277), project_volume_rgb_integral
 // (dpc/util/drc.py:132-142), add_proj_rgb_loss (dpc/util/losses.py:69-90).  Design notes: DESIGN.md section 4.
@@ -104,18 +104,6 @@ __global__ __launch_bounds__(kRgbThreads) void k_rgb_splat_bwd(DpcParams P, cons
 // ------------------------------------------------------------------------------------------------------
 // Column kernels.  One thread per ray (b, y, x), x fastest: every plane read and write is coalesced.
 // ------------------------------------------------------------------------------------------------------
-// this tile's sum over the block (valid in thread 0): no atomics, the tiles are added in order by the finalize
-__device__ inline float rgb_tile_sum(float v) {
-  __shared__ float red[kColThreads / DPC_WAVE];
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float tot = 0.f;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < kColThreads / DPC_WAVE; ++i) tot += red[i];
-  return tot;
-}
-
 // Forward: p_0 = e^eps y_0, p_k = y_k A_k, p_D = e^eps A_D (k_drc_fwd, dpc_stages.hip);
 //   proj_rgb[b, H-1-y, x, c] = sum_{k<D} p_k C[b,c,k,y,x] + p_D * 1                 grid (ceil(HW/256) * B)
 __global__ __launch_bounds__(kColThreads) void k_rgb_fwd(DpcParams P, double e_eps, const float* __restrict__ vox,
@@ -158,28 +146,8 @@ __global__ __launch_bounds__(kColThreads) void k_rgb_fwd(DpcParams P, double e_e
     }
   }
   if (a.gt != nullptr) {   // block-uniform
-    const float tot = rgb_tile_sum(sq);
+    const float tot = tile_sum(sq);
     if (threadIdx.x == 0) loss_tiles[(size_t)bk.y * bk.nx + bk.x] = tot;
-  }
-}
-
-// loss = (1/2) sum_s w_s^2 (sum of the sample's tiles, in tile order) / S.  One block; the same bits on every run.
-__global__ __launch_bounds__(256) void k_rgb_loss_finalize(const float* __restrict__ loss_tiles, int ntile, int S, float half_inv_S,
-                                                           const float* __restrict__ weights, float* __restrict__ loss) {
-  __shared__ float red[256 / DPC_WAVE];
-  float acc = 0.f;
-  for (int smp = threadIdx.x; smp < S; smp += blockDim.x) {
-    float v = 0.f;
-    for (int i = 0; i < ntile; ++i) v += loss_tiles[(size_t)smp * ntile + i];
-    acc += v * ::sample_weight2(weights, smp);
-  }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-    for (int i = 0; i < 256 / DPC_WAVE; ++i) tot += red[i];
-    *loss = tot * half_inv_S;
   }
 }
 
@@ -287,9 +255,7 @@ int dpc_rgb_loss_fwd(const DpcParams* p, const float* vox, const float* C, const
              exp((double)p->clip_val), vox, C, a, proj_rgb, loss_tiles);
   if (launch_ok() != DPC_OK) return DPC_ERR_LAUNCH;
   if (!gt) return DPC_OK;
-  DPC_LAUNCH("k_rgb_loss_finalize", dpc_kid("k_rgb_loss_finalize"), k_rgb_loss_finalize, dim3(1), dim3(256), 0, st, loss_tiles,
-             col_tiles(p), p->B, 0.5f * a.inv_S, weights, loss);
-  return launch_ok();
+  return launch_tile_loss_finalize(p, loss_tiles, 0.5f * a.inv_S, weights, loss, st);
 }
 
 int dpc_rgb_loss_bwd(const DpcParams* p, const float* vox, const float* C, const float* div, float div_eps, int clip_after,

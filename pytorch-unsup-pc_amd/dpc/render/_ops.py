@@ -826,22 +826,48 @@ def _depth_workspace(dev, nbytes):
     return ws
 
 
-def _depth_backward(ctx, dloss, ddepth):
-    """One launch: d grid_wh (overwritten) and d s from the gradient arriving at the loss and / or the depth map."""
+def _call(dev, entry, *args):
+    """One entry point of the library on `dev` and its current stream (every entry's last argument); raises on a return code."""
+    with _on(dev):
+        rc = getattr(N.lib(), entry)(*args, _stream(dev))
+    if rc != 0:
+        N.check(rc, entry)
+
+
+def _loss_targets(x32, gt, weights, f, geom, what, rgb=False):
+    """Ground truth [S,f*H,f*W] ([.., 3] values per sample when rgb) and weights [S] | None of a loss on the B = S clouds of
+    x32, as fp32: (gt32, w32)."""
+    N.require_device(x32, gt, weights)
+    B, gt32 = x32.shape[0], _f32(gt)
+    if gt32.numel() != B * f * geom.H * f * geom.W * (3 if rgb else 1):
+        raise ValueError("%s must hold %d x %d x %d%s values, got %s"
+                         % (what, B, f * geom.H, f * geom.W, " x 3" if rgb else "", tuple(gt.shape)))
+    return gt32, _weights32(weights, B)
+
+
+def _loss_buffers(B, geom, dev):
+    """(per-tile partial sums [B, ray tiles], scalar loss) of a column kernel and its one-block finalize."""
+    return (torch.empty((B, (geom.H * geom.W + 255) // 256), dtype=torch.float32, device=dev),
+            torch.empty((), dtype=torch.float32, device=dev))
+
+
+def _column_backward(ctx, entry, ws_entry, extra, *grads):
+    """One launch: d grid_wh (overwritten) and d s from the gradients arriving at the node's outputs (`grads`, None = absent).
+    `extra`: the entry's scalars between gt_factor and the weights; `ws_entry` sizes its workspace."""
     grid_wh, s32, gt32, w32 = ctx.saved
     geom, dev, B = ctx.geom, grid_wh.device, grid_wh.shape[0]
-    L = N.lib()
     Z = geom.sized(B, 0)
     dgrid = torch.empty_like(grid_wh)
     ds = None if s32 is None else torch.empty((B,), dtype=torch.float32, device=dev)
     with _on(dev):
-        ws = _depth_workspace(dev, max(L.dpc_depth_workspace_bytes(Z.ref), 16))
-        rc = L.dpc_depth_loss_bwd(Z.ref, _dp(grid_wh), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), ctx.gt_factor,
-                                  ctx.max_dataset_depth, _dp(w32), _dp(_f32(dloss)), _dp(_f32(ddepth)), _dp(dgrid), _dp(ds),
-                                  _dp(ws), _stream(dev))
-    if rc != 0:
-        N.check(rc, "dpc_depth_loss_bwd")
+        ws = _depth_workspace(dev, max(getattr(N.lib(), ws_entry)(Z.ref), 16))
+    _call(dev, entry, Z.ref, _dp(grid_wh), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), ctx.gt_factor, *extra, _dp(w32),
+          *[_dp(_f32(g)) for g in grads], _dp(dgrid), _dp(ds), _dp(ws))
     return _like_input(dgrid, ctx.metas[0]), _like_input(ds, ctx.metas[1])
+
+
+def _depth_backward(ctx, dloss, ddepth):
+    return _column_backward(ctx, "dpc_depth_loss_bwd", "dpc_depth_workspace_bytes", (ctx.max_dataset_depth,), dloss, ddepth)
 
 
 def _depth_inputs(grid_wh, s, geom):
@@ -862,13 +888,9 @@ class DepthMap(torch.autograd.Function):
     def forward(ctx, grid_wh, s, geom):
         dev, g32, s32 = _depth_inputs(grid_wh, s, geom)
         B = g32.shape[0]
-        Z = geom.sized(B, 0)
         depth = torch.empty((B, geom.H, geom.W, 1), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = N.lib().dpc_depth_loss_fwd(Z.ref, _dp(g32), _dp(s32), geom.kern_ptrs()[1], None, 1, 0.0, None, _dp(depth),
-                                            None, None, _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_depth_loss_fwd")
+        _call(dev, "dpc_depth_loss_fwd", geom.sized(B, 0).ref, _dp(g32), _dp(s32), geom.kern_ptrs()[1], None, 1, 0.0, None,
+              _dp(depth), None, None)
         ctx.geom, ctx.saved, ctx.metas = geom, (g32, s32, None, None), (_meta(grid_wh), _meta(s))
         ctx.gt_factor, ctx.max_dataset_depth = 1, 0.0
         return depth
@@ -888,21 +910,12 @@ class DepthLoss(torch.autograd.Function):
         """Returns (loss, depth): depth [B,H,W,1] written by the same launch when want_depth (detached: differentiate
         DepthMap for a gradient through the map itself), else None."""
         dev, g32, s32 = _depth_inputs(grid_wh, s, geom)
-        N.require_device(g32, gt, weights)
         B, f = g32.shape[0], int(gt_factor)
-        gt32 = _f32(gt)
-        if gt32.numel() != B * f * geom.H * f * geom.W:
-            raise ValueError("depths must hold %d x %d x %d values, got %s" % (B, f * geom.H, f * geom.W, tuple(gt.shape)))
-        w32 = _weights32(weights, B)
-        Z = geom.sized(B, 0)
-        tiles = torch.empty((B, (geom.H * geom.W + 255) // 256), dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
+        gt32, w32 = _loss_targets(g32, gt, weights, f, geom, "depths")
+        tiles, loss = _loss_buffers(B, geom, dev)
         depth = torch.empty((B, geom.H, geom.W, 1), dtype=torch.float32, device=dev) if want_depth else None
-        with _on(dev):
-            rc = N.lib().dpc_depth_loss_fwd(Z.ref, _dp(g32), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), f,
-                                            float(max_dataset_depth), _dp(w32), _dp(depth), _dp(tiles), _dp(loss), _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_depth_loss_fwd")
+        _call(dev, "dpc_depth_loss_fwd", geom.sized(B, 0).ref, _dp(g32), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), f,
+              float(max_dataset_depth), _dp(w32), _dp(depth), _dp(tiles), _dp(loss))
         ctx.geom, ctx.saved, ctx.metas = geom, (g32, s32, gt32, w32), (_meta(grid_wh), _meta(s))
         ctx.gt_factor, ctx.max_dataset_depth = f, float(max_dataset_depth)
         if depth is not None:
@@ -968,18 +981,36 @@ def _rgb_inputs(vox, C, div, geom):
     return dev, v32, c32, d32
 
 
-def _rgb_backward(ctx, dloss, dproj):
-    """One launch: d voxels and d colour grid (both overwritten) from the gradient arriving at the loss and / or the image."""
-    v32, c32, d32, gt32, w32, proj = ctx.saved
-    geom, dev, B = ctx.geom, v32.device, v32.shape[0]
-    Z = geom.sized(B, 0)
+def _rgb_options(ctx, div_eps, clip_after, gt_factor, gt_planar):
+    """The colour entries' scalars as the bindings take them, kept on ctx for the backward: (div_eps, clip_after)."""
+    ctx.div_eps, ctx.clip_after = float(div_eps), int(bool(clip_after))
+    ctx.gt_factor, ctx.gt_planar = int(gt_factor), int(bool(gt_planar))
+    return ctx.div_eps, ctx.clip_after
+
+
+def _rgb_loss_forward(ctx, entry, with_proj, vox, C, div, gt, gt_factor, gt_planar, weights, geom, div_eps, clip_after):
+    """Forward of a loss on the renderer's grids against images (column kernel, one-block finalize): (loss, proj_rgb [B,H,W,3] |
+    None), proj_rgb where the entry writes one (with_proj)."""
+    dev, v32, c32, d32 = _rgb_inputs(vox, C, div, geom)
+    B = v32.shape[0]
+    eps, clip = _rgb_options(ctx, div_eps, clip_after, gt_factor, gt_planar)
+    gt32, w32 = _loss_targets(v32, gt, weights, ctx.gt_factor, geom, "images", rgb=True)
+    tiles, loss = _loss_buffers(B, geom, dev)
+    proj = torch.empty((B, geom.H, geom.W, 3), dtype=torch.float32, device=dev) if with_proj else None
+    _call(dev, entry, geom.sized(B, 0).ref, _dp(v32), _dp(c32), _dp(d32), eps, clip, _dp(gt32), ctx.gt_factor, ctx.gt_planar,
+          _dp(w32), *([_dp(proj)] if with_proj else []), _dp(tiles), _dp(loss))
+    ctx.geom, ctx.saved, ctx.metas = geom, (v32, c32, d32, gt32, w32, proj), (_meta(vox), _meta(C))
+    return loss, proj
+
+
+def _rgb_backward(ctx, entry, *grads):
+    """One launch: d voxels and d colour grid (both overwritten).  `grads`: what the entry takes between the weights and the
+    outputs -- the saved image where it needs one, the gradients arriving at the node's outputs (None = absent)."""
+    v32, c32, d32, gt32, w32, _ = ctx.saved
+    geom, dev = ctx.geom, v32.device
     dvox, dC = torch.empty_like(v32), torch.empty_like(c32)
-    with _on(dev):
-        rc = N.lib().dpc_rgb_loss_bwd(Z.ref, _dp(v32), _dp(c32), _dp(d32), ctx.div_eps, ctx.clip_after, _dp(gt32), ctx.gt_factor,
-                                      ctx.gt_planar, _dp(w32), _dp(proj), _dp(_f32(dloss)), _dp(_f32(dproj)), _dp(dvox), _dp(dC),
-                                      _stream(dev))
-    if rc != 0:
-        N.check(rc, "dpc_rgb_loss_bwd")
+    _call(dev, entry, geom.sized(v32.shape[0], 0).ref, _dp(v32), _dp(c32), _dp(d32), ctx.div_eps, ctx.clip_after, _dp(gt32),
+          ctx.gt_factor, ctx.gt_planar, _dp(w32), *[_dp(_f32(g)) for g in grads], _dp(dvox), _dp(dC))
     return _like_input(dvox, ctx.metas[0]), _like_input(dC, ctx.metas[1])
 
 
@@ -992,20 +1023,16 @@ class RgbMap(torch.autograd.Function):
     def forward(ctx, vox, C, div, geom, div_eps=0.01, clip_after=False):
         dev, v32, c32, d32 = _rgb_inputs(vox, C, div, geom)
         B = v32.shape[0]
-        Z = geom.sized(B, 0)
+        eps, clip = _rgb_options(ctx, div_eps, clip_after, 1, 0)
         proj = torch.empty((B, geom.H, geom.W, 3), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = N.lib().dpc_rgb_loss_fwd(Z.ref, _dp(v32), _dp(c32), _dp(d32), float(div_eps), int(bool(clip_after)), None, 1, 0,
-                                          None, _dp(proj), None, None, _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_rgb_loss_fwd")
+        _call(dev, "dpc_rgb_loss_fwd", geom.sized(B, 0).ref, _dp(v32), _dp(c32), _dp(d32), eps, clip, None, 1, 0, None, _dp(proj),
+              None, None)
         ctx.geom, ctx.saved, ctx.metas = geom, (v32, c32, d32, None, None, None), (_meta(vox), _meta(C))
-        ctx.div_eps, ctx.clip_after, ctx.gt_factor, ctx.gt_planar = float(div_eps), int(bool(clip_after)), 1, 0
         return proj
 
     @staticmethod
     def backward(ctx, dproj):
-        return _rgb_backward(ctx, None, dproj) + (None,) * 4
+        return _rgb_backward(ctx, "dpc_rgb_loss_bwd", None, None, dproj) + (None,) * 4
 
 
 class RgbLoss(torch.autograd.Function):
@@ -1016,30 +1043,14 @@ class RgbLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vox, C, div, gt, gt_factor, gt_planar, weights, geom, div_eps=0.01, clip_after=False):
-        dev, v32, c32, d32 = _rgb_inputs(vox, C, div, geom)
-        N.require_device(v32, gt, weights)
-        B, f = v32.shape[0], int(gt_factor)
-        gt32 = _f32(gt)
-        if gt32.numel() != B * 3 * f * geom.H * f * geom.W:
-            raise ValueError("images must hold %d x %d x %d x 3 values, got %s" % (B, f * geom.H, f * geom.W, tuple(gt.shape)))
-        w32 = _weights32(weights, B)
-        Z = geom.sized(B, 0)
-        tiles = torch.empty((B, (geom.H * geom.W + 255) // 256), dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        proj = torch.empty((B, geom.H, geom.W, 3), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = N.lib().dpc_rgb_loss_fwd(Z.ref, _dp(v32), _dp(c32), _dp(d32), float(div_eps), int(bool(clip_after)), _dp(gt32), f,
-                                          int(bool(gt_planar)), _dp(w32), _dp(proj), _dp(tiles), _dp(loss), _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_rgb_loss_fwd")
-        ctx.geom, ctx.saved, ctx.metas = geom, (v32, c32, d32, gt32, w32, proj), (_meta(vox), _meta(C))
-        ctx.div_eps, ctx.clip_after, ctx.gt_factor, ctx.gt_planar = float(div_eps), int(bool(clip_after)), f, int(bool(gt_planar))
+        loss, proj = _rgb_loss_forward(ctx, "dpc_rgb_loss_fwd", True, vox, C, div, gt, gt_factor, gt_planar, weights, geom,
+                                       div_eps, clip_after)
         ctx.mark_non_differentiable(proj)
         return loss, proj
 
     @staticmethod
     def backward(ctx, dloss, _dproj):
-        return _rgb_backward(ctx, dloss, None) + (None,) * 8
+        return _rgb_backward(ctx, "dpc_rgb_loss_bwd", ctx.saved[5], dloss, None) + (None,) * 8
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1054,38 +1065,17 @@ class DrcLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, grid_wh, s, gt, gt_factor, weights, geom):
         dev, g32, s32 = _depth_inputs(grid_wh, s, geom)
-        N.require_device(g32, gt, weights)
         B, f = g32.shape[0], int(gt_factor)
-        gt32 = _f32(gt)
-        if gt32.numel() != B * f * geom.H * f * geom.W:
-            raise ValueError("masks must hold %d x %d x %d values, got %s" % (B, f * geom.H, f * geom.W, tuple(gt.shape)))
-        w32 = _weights32(weights, B)
-        Z = geom.sized(B, 0)
-        tiles = torch.empty((B, (geom.H * geom.W + 255) // 256), dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = N.lib().dpc_drc_loss_fwd(Z.ref, _dp(g32), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), f, _dp(w32), _dp(tiles),
-                                          _dp(loss), _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_drc_loss_fwd")
+        gt32, w32 = _loss_targets(g32, gt, weights, f, geom, "masks")
+        tiles, loss = _loss_buffers(B, geom, dev)
+        _call(dev, "dpc_drc_loss_fwd", geom.sized(B, 0).ref, _dp(g32), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), f, _dp(w32),
+              _dp(tiles), _dp(loss))
         ctx.geom, ctx.saved, ctx.metas, ctx.gt_factor = geom, (g32, s32, gt32, w32), (_meta(grid_wh), _meta(s)), f
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
-        grid_wh, s32, gt32, w32 = ctx.saved
-        geom, dev, B = ctx.geom, grid_wh.device, grid_wh.shape[0]
-        L = N.lib()
-        Z = geom.sized(B, 0)
-        dgrid = torch.empty_like(grid_wh)
-        ds = None if s32 is None else torch.empty((B,), dtype=torch.float32, device=dev)
-        with _on(dev):
-            ws = _depth_workspace(dev, max(L.dpc_drc_workspace_bytes(Z.ref), 16))
-            rc = L.dpc_drc_loss_bwd(Z.ref, _dp(grid_wh), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), ctx.gt_factor, _dp(w32),
-                                    _dp(_f32(dloss)), _dp(dgrid), _dp(ds), _dp(ws), _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_drc_loss_bwd")
-        return _like_input(dgrid, ctx.metas[0]), _like_input(ds, ctx.metas[1]), None, None, None, None
+        return _column_backward(ctx, "dpc_drc_loss_bwd", "dpc_drc_workspace_bytes", (), dloss) + (None,) * 4
 
 
 class DrcRgbLoss(torch.autograd.Function):
@@ -1095,35 +1085,9 @@ class DrcRgbLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vox, C, div, gt, gt_factor, gt_planar, weights, geom, div_eps=0.01, clip_after=False):
-        dev, v32, c32, d32 = _rgb_inputs(vox, C, div, geom)
-        N.require_device(v32, gt, weights)
-        B, f = v32.shape[0], int(gt_factor)
-        gt32 = _f32(gt)
-        if gt32.numel() != B * 3 * f * geom.H * f * geom.W:
-            raise ValueError("images must hold %d x %d x %d x 3 values, got %s" % (B, f * geom.H, f * geom.W, tuple(gt.shape)))
-        w32 = _weights32(weights, B)
-        Z = geom.sized(B, 0)
-        tiles = torch.empty((B, (geom.H * geom.W + 255) // 256), dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = N.lib().dpc_drc_rgb_loss_fwd(Z.ref, _dp(v32), _dp(c32), _dp(d32), float(div_eps), int(bool(clip_after)), _dp(gt32),
-                                              f, int(bool(gt_planar)), _dp(w32), _dp(tiles), _dp(loss), _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_drc_rgb_loss_fwd")
-        ctx.geom, ctx.saved, ctx.metas = geom, (v32, c32, d32, gt32, w32), (_meta(vox), _meta(C))
-        ctx.div_eps, ctx.clip_after, ctx.gt_factor, ctx.gt_planar = float(div_eps), int(bool(clip_after)), f, int(bool(gt_planar))
-        return loss
+        return _rgb_loss_forward(ctx, "dpc_drc_rgb_loss_fwd", False, vox, C, div, gt, gt_factor, gt_planar, weights, geom,
+                                 div_eps, clip_after)[0]
 
     @staticmethod
     def backward(ctx, dloss):
-        v32, c32, d32, gt32, w32 = ctx.saved
-        geom, dev, B = ctx.geom, v32.device, v32.shape[0]
-        Z = geom.sized(B, 0)
-        dvox, dC = torch.empty_like(v32), torch.empty_like(c32)
-        with _on(dev):
-            rc = N.lib().dpc_drc_rgb_loss_bwd(Z.ref, _dp(v32), _dp(c32), _dp(d32), ctx.div_eps, ctx.clip_after, _dp(gt32),
-                                              ctx.gt_factor, ctx.gt_planar, _dp(w32), _dp(_f32(dloss)), _dp(dvox), _dp(dC),
-                                              _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_drc_rgb_loss_bwd")
-        return (_like_input(dvox, ctx.metas[0]), _like_input(dC, ctx.metas[1])) + (None,) * 8
+        return _rgb_backward(ctx, "dpc_drc_rgb_loss_bwd", dloss) + (None,) * 8

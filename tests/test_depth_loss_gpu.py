@@ -321,7 +321,7 @@ def test_bits_repeat_and_launch_counts(c):
     assert torch.equal(loss1, loss2) and torch.equal(dgrid1, dgrid2) and torch.equal(ds1, ds2)
     assert torch.isfinite(dgrid1).all() and torch.isfinite(ds1).all()
     fwd, bwd = launches
-    assert len(fwd) == 2 and fwd[1] == "k_depth_loss_finalize" and len(bwd) == 1, launches
+    assert len(fwd) == 2 and fwd[1] == "k_tile_loss_finalize" and len(bwd) == 1, launches
     assert bwd[0] == c.kernel and fwd[0] == c.kernel.replace("bwd", "fwd"), launches
 
 

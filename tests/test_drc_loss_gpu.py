@@ -164,7 +164,7 @@ def test_mask_abi_parity(c):
                                    N.ptr(ds), N.ptr(ws), st), "dpc_drc_loss_bwd")
 
     lf, lb = launch_list(fwd), launch_list(bwd)
-    assert lf == [c.kernel.replace("bwd", "fwd"), "k_drc_loss_finalize"] and lb == [c.kernel], (lf, lb)
+    assert lf == [c.kernel.replace("bwd", "fwd"), "k_tile_loss_finalize"] and lb == [c.kernel], (lf, lb)
     close(loss[0], rloss, what=c.name + " loss")
     close(dgrid, rdgrid, what=c.name + " dgrid_wh")
     if c.has_s:
@@ -283,7 +283,7 @@ def test_rgb_abi_parity(c):
                                        int(c.planar), N.ptr(w), N.ptr(dloss), N.ptr(dvox), N.ptr(dC), st), "dpc_drc_rgb_loss_bwd")
 
     lf, lb = launch_list(fwd), launch_list(bwd)
-    assert lf == ["k_drcrgb_fwd", "k_drc_loss_finalize"] and lb == [c.kernel], (lf, lb)
+    assert lf == ["k_drcrgb_fwd", "k_tile_loss_finalize"] and lb == [c.kernel], (lf, lb)
     close(loss[0], rloss, what=c.name + " loss")
     close(dvox, rdvox, what=c.name + " dvox")
     close(dC, rdC, what=c.name + " dC")
