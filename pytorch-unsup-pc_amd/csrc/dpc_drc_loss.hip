@@ -4,8 +4,9 @@
 // renderer's voxels and colour grid (k_drcrgb_fwd / k_drcrgb_bwd, the inputs and options of k_rgb_* in dpc_rgb.hip).
 // Reference (TF-1 originals): drc_loss, drc_rgb_loss, add_drc_loss, add_drc_rgb_loss (dpc/util/losses.py:23-66, 93-110) on
 // drc_event_probabilities (dpc/util/drc.py:48-106) and the flip of pointcloud_project_fast (dpc/util/point_cloud.py:269-276).
-// Design notes: DESIGN.md section 4.  The tile sum, the finalize, the images' reads and the colour value are those of
-// dpc_depth.hip and dpc_rgb.hip (dpc_kernels.h); loss = sum_s w_s^2 (the sample's tiles) / S: no 1/2 (losses.py:29, 46, 62, 106).
+// Design notes: DESIGN.md section 4.  The tile sum and the finalize are those of dpc_depth.hip and dpc_rgb.hip (dpc_kernels.h), the
+// images' reads, the colour value and the entries' checks those of dpc_rgb.hip (dpc_colour_column.h); loss = sum_s w_s^2 (the sample's tiles) / S: no 1/2 (losses.py:29, 46, 62, 106).
+#include "dpc_colour_column.h"
 #include "dpc_ray_column.h"
 
 namespace dpck {
@@ -318,26 +319,25 @@ int dpc_drc_rgb_loss_fwd(const DpcParams* p, const float* vox, const float* C, c
                          const float* gt, int gt_factor, int gt_planar, const float* weights, float* loss_tiles, float* loss,
                          void* stream) {
   if (p && gt && (!loss || !loss_tiles)) return DPC_ERR_SHAPE;   // a loss nobody can receive
-  const int rc = rgb_check(p, gt_factor);
+  RgbArgs a;
+  const int rc = colour_check(p, vox, C, div, div_eps, clip_after, gt, ColourGt::required, gt_factor, gt_planar, weights, a);
   if (rc != DPC_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (p->B == 0) return (!loss || zero_words_async(loss, 1, st)) ? DPC_OK : DPC_ERR_LAUNCH;  // the loss of nothing is 0
-  if (!vox || !C || !gt) return DPC_ERR_NULL;
-  const RgbArgs a{div, div_eps, clip_after != 0, gt, gt_factor, gt_planar != 0, weights, 1.0f / (float)p->B};
   DPC_LAUNCH("k_drcrgb_fwd", dpc_kid("k_drcrgb_fwd"), k_drcrgb_fwd, dim3(col_tiles(p) * p->B), dim3(kColThreads), 0, st, *p,
              exp((double)p->clip_val), vox, C, a, loss_tiles);
   if (launch_ok() != DPC_OK) return DPC_ERR_LAUNCH;
-  return launch_tile_loss_finalize(p, loss_tiles, 1.0f / (float)p->B, weights, loss, st);
+  return launch_tile_loss_finalize(p, loss_tiles, a.inv_S, weights, loss, st);
 }
 
 int dpc_drc_rgb_loss_bwd(const DpcParams* p, const float* vox, const float* C, const float* div, float div_eps, int clip_after,
                          const float* gt, int gt_factor, int gt_planar, const float* weights, const float* dloss, float* dvox,
                          float* dC, void* stream) {
-  const int rc = rgb_check(p, gt_factor);
+  RgbArgs a;
+  const int rc = colour_check(p, vox, C, div, div_eps, clip_after, gt, ColourGt::required, gt_factor, gt_planar, weights, a);
   if (rc != DPC_OK || p->B == 0) return rc;
-  if (!vox || !C || !gt || !dvox || !dC) return DPC_ERR_NULL;
+  if (!dvox || !dC) return DPC_ERR_NULL;
   hipStream_t st = (hipStream_t)stream;
-  const RgbArgs a{div, div_eps, clip_after != 0, gt, gt_factor, gt_planar != 0, weights, 1.0f / (float)p->B};
   const dim3 gcol(col_tiles(p) * p->B);
   const double e_eps = exp((double)p->clip_val);
   if (p->D == 32)

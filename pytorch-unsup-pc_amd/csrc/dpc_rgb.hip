@@ -5,7 +5,7 @@
 // Reference (TF-1 originals): pointcloud2voxels3d_fast's rgb half (dpc/util/point_cloud.py:98-134), the clips, the division
 // by the occupancies and the flip of pointcloud_project_fast (:244-262, 275-277), project_volume_rgb_integral
 // (dpc/util/drc.py:132-142), add_proj_rgb_loss (dpc/util/losses.py:69-90).  Design notes: DESIGN.md section 4.
-#include "dpc_kernels.h"
+#include "dpc_colour_column.h"
 
 namespace dpck {
 namespace {
@@ -245,12 +245,11 @@ int dpc_rgb_loss_fwd(const DpcParams* p, const float* vox, const float* C, const
                      const float* gt, int gt_factor, int gt_planar, const float* weights, float* proj_rgb, float* loss_tiles,
                      float* loss, void* stream) {
   if (p && ((gt && (!loss || !loss_tiles)) || (!gt && !proj_rgb))) return DPC_ERR_SHAPE;  // a loss nobody can receive / nothing asked for
-  const int rc = rgb_check(p, gt_factor);
+  RgbArgs a;
+  const int rc = colour_check(p, vox, C, div, div_eps, clip_after, gt, ColourGt::optional, gt_factor, gt_planar, weights, a);
   if (rc != DPC_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (p->B == 0) return (!loss || zero_words_async(loss, 1, st)) ? DPC_OK : DPC_ERR_LAUNCH;  // the loss of nothing is 0
-  if (!vox || !C) return DPC_ERR_NULL;
-  const RgbArgs a{div, div_eps, clip_after != 0, gt, gt_factor, gt_planar != 0, weights, 1.0f / (float)p->B};
   DPC_LAUNCH("k_rgb_fwd", dpc_kid("k_rgb_fwd"), k_rgb_fwd, dim3(col_tiles(p) * p->B), dim3(kColThreads), 0, st, *p,
              exp((double)p->clip_val), vox, C, a, proj_rgb, loss_tiles);
   if (launch_ok() != DPC_OK) return DPC_ERR_LAUNCH;
@@ -262,10 +261,10 @@ int dpc_rgb_loss_bwd(const DpcParams* p, const float* vox, const float* C, const
                      const float* gt, int gt_factor, int gt_planar, const float* weights, const float* proj_rgb,
                      const float* dloss, const float* dproj_rgb, float* dvox, float* dC, void* stream) {
   if (p && !gt && !dproj_rgb) return DPC_ERR_SHAPE;   // no gradient arrives anywhere
-  const int rc = rgb_check(p, gt_factor);
+  RgbArgs a;
+  const int rc = colour_check(p, vox, C, div, div_eps, clip_after, gt, ColourGt::optional, gt_factor, gt_planar, weights, a);
   if (rc != DPC_OK || p->B == 0) return rc;
-  if (!vox || !C || !dvox || !dC || (gt && !proj_rgb)) return DPC_ERR_NULL;
-  const RgbArgs a{div, div_eps, clip_after != 0, gt, gt_factor, gt_planar != 0, weights, 1.0f / (float)p->B};
+  if (!dvox || !dC || (gt && !proj_rgb)) return DPC_ERR_NULL;
   DPC_LAUNCH("k_rgb_bwd", dpc_kid("k_rgb_bwd"), k_rgb_bwd, dim3(col_tiles(p) * p->B), dim3(kColThreads), 0, (hipStream_t)stream, *p,
              exp((double)p->clip_val), vox, C, a, proj_rgb, dloss, dproj_rgb, dvox, dC);
   return launch_ok();
