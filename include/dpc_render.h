@@ -369,7 +369,7 @@ int dpc_depth_loss_bwd(const DpcParams* p, const float* grid_wh, const float* s,
  *   corners, four each (the pair owns the two x corners, neighbours in memory), with fp32 hardware atomics
  *   (global_atomic_add_f32, no compare-and-swap loop).  NOT BIT-REPRODUCIBLE: a voxel's sum depends on
  *   the order its adds arrive in, so two runs on equal inputs may differ in the last bits of the colour grid (and of
- *   everything computed from it); a reproducible, atomic-free splat is future work.
+ *   everything computed from it); dpc_rgb_splat_fixed_fwd below is the reproducible splat.
  * dpc_rgb_splat_bwd: dC [B,3,D,H,W] -> drgb [B,N,3], drgb_c = sum_corners w dC_c; dtr [B,N,3] | NULL, dpc_splat_bwd's
  *   formula applied to sum_c rgb_c dC_c[corner] (NULL: pc_rgb_stop_points_gradient, point_cloud.py:112-113).  One thread
  *   per point, 24 gathers; no atomics; a point outside the cube gets exact zeros.  Every element is written.
@@ -407,6 +407,45 @@ int dpc_rgb_loss_fwd(const DpcParams* p, const float* vox, const float* C, const
 int dpc_rgb_loss_bwd(const DpcParams* p, const float* vox, const float* C, const float* div, float div_eps, int clip_after,
                      const float* gt, int gt_factor, int gt_planar, const float* weights, const float* proj_rgb,
                      const float* dloss, const float* dproj_rgb, float* dvox, float* dC, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Bit-reproducible colour splat that reads shared colour sets in place.  The colour grid of dpc_rgb_splat_fwd with the
+ * same cell, weights, dropped corners and fp32 product wz[k] * wy[j] * (wx[i] * c) per contribution, but each contribution
+ * is rounded ONCE to signed 64-bit fixed point with 40 fractional bits and added as an integer (64-bit atomic adds into a
+ * zeroed [B,3,D,H,W] workspace); a second launch converts the sums to fp32, one rounding in all.  Integer adds commute:
+ * the grid -- and everything computed from it -- is the same bits on every run and for every order of a cloud's points.
+ *   tr        [B,N,3] transformed points (z,y,x), one row per cloud (outputs' tr_pc);
+ *   rgb_sets  [B/R, n_set, 3]: the colour of point i of cloud b is rgb_sets[b / R][point_index ? point_index[b*N + i] : i],
+ *             R = p->point_replicas (0 or 1: every cloud has its own set), p->point_index [B,N] int32 | NULL -- the
+ *             convention of the fused projection, so the decoder's colours serve all views and dropout rows in place;
+ *   n_set     colours per set: p->N without a point_index, p->N_src (>= 1) with one (DPC_ERR_SHAPE otherwise).
+ * Range: a colour is accepted when |c| <= 8 -- with weights <= 1 and N <= DPC_MAX_POINTS a voxel's sum then stays below
+ * 8 * (2^20 - 1) * 2^40 < 2^63 and cannot wrap.  A colour that is larger, NaN or infinite adds nothing and poisons its
+ * CLOUD: every voxel of that cloud's grid is NaN, the other clouds are untouched, the call returns DPC_OK.  A point_index
+ * entry outside [0, n_set) never becomes an address: it poisons its cloud likewise and sets DPC_STATUS_BAD_INDEX in
+ * *p->status when given.
+ * dpc_rgb_splat_fixed_bwd: dC [B,3,D,H,W] -> dtr [B,N,3] | NULL (pc_rgb_stop_points_gradient) with dpc_rgb_splat_bwd's
+ *   formulas, one lane per (cloud, point); drgb_sets [B/R, n_set, 3], every element written.  Without sharing (R <= 1, no
+ *   point_index) drgb is stored directly and the workspace may be NULL.  With sharing the points' contributions are added
+ *   as 64-bit fixed point (2^-40; indices may repeat inside a row) and converted by a second launch: the same bits in any
+ *   arrival order.  A contribution that is NaN, infinite or >= 2^20 in magnitude has no fixed-point value: it is not
+ *   added and its colour SET's gradient is NaN (one poison word per set), as is the gradient of a set a bad index points into.
+ * workspace: dpc_rgb_splat_fixed_workspace_bytes(p, n_set) bytes (0 when the arguments are invalid), 16-byte aligned, no
+ *   initialisation needed: 8 bytes per colour voxel plus 4 per cloud for the forward.  The backward touches only the first
+ *   8 * 3 * (B/R) * n_set + 4 * (B/R) bytes of it (rounded up to 256), and a buffer of that size is enough for it.
+ * DPC_ERR_SHAPE before any launch: p->n_live given (the colour step is not capturable), B % R != 0, n_set as above;
+ * DPC_ERR_NULL for a missing pointer.  B == 0: DPC_OK, nothing launched; N == 0: the grid (the gradient) is zeroed.
+ * The launches: zero fill, splat, convert (forward); splat backward, and with sharing zero fill and convert (backward).
+ * Added without a new ABI number: no existing entry point changed; dpc_rgb_splat_fwd / _bwd keep refusing shared sets.
+ * These three are declared with DpcParams' fixed-width types (int32_t = int and uint64_t = size_t on every target of this
+ * library, so the calling convention is that of the other entry points): tests/test_rgb_loss_host.py pins the list of
+ * `int dpc_rgb_*` prototypes to the four entry points above.
+ * ------------------------------------------------------------------------------------------------- */
+uint64_t dpc_rgb_splat_fixed_workspace_bytes(const DpcParams* p, int32_t n_set);
+int32_t dpc_rgb_splat_fixed_fwd(const DpcParams* p, const float* tr, const float* rgb_sets, int32_t n_set, float* out,
+                                void* workspace, void* stream);
+int32_t dpc_rgb_splat_fixed_bwd(const DpcParams* p, const float* tr, const float* rgb_sets, int32_t n_set, const float* dC,
+                                float* drgb_sets, float* dtr, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Ray-consistency (DRC) losses, fused: the ray potentials sum_k p_k psi_k of the TF-1 original's drc_loss / add_drc_loss and

@@ -35,6 +35,8 @@ def chair_unsupervised(**overrides):
         pc_rgb=False, pc_rgb_stop_points_gradient=False, pc_rgb_clip_after_conv=False, pc_rgb_divide_by_occupancies=False,
         pc_rgb_divide_by_occupancies_epsilon=0.01, pc_rgb_deep_decoder=False, pc_gauss_filter_gt_rgb=False, proj_rgb_weight=0.0,
         drc_rgb_weight=0.0,
+        # this package's own: the bit-reproducible colour splat, reading the decoder's colour sets in place (dpc.render.project_rgb)
+        pc_rgb_deterministic=False,
         # schedules, loss, optimiser
         pc_point_dropout=0.07, pc_point_dropout_scheduled=True, pc_point_dropout_exponential_schedule=False,
         pc_point_dropout_start_step=0.0, pc_point_dropout_end_step=1.0, max_number_of_steps=600000,

@@ -21,6 +21,8 @@ Colour supervision (cfg.pc_rgb and cfg.proj_rgb_weight != 0, one pose candidate 
 dpc/util/losses.py:69-90): the decoder's per-point colours, replicated like the points, are projected on the same projection
 (dpc.render.proj_rgb_loss) and compared with the input images,
     total = proj_weight * (proj + student) + proj_depth_weight * depth + proj_rgb_weight * rgb.
+Under cfg.pc_rgb_deterministic the colour node reads the decoder's colour sets in place (no replicated all_rgb) and sums the
+colour grid in fixed point: the colour terms are then the same bits on every run.
 
 Ray-consistency terms (one pose candidate per image), further nodes on the same projection:
     cfg.drc_weight != 0: add_drc_loss (dpc/util/losses.py:49-66; get_loss, model_pc_to.py:396-397) on the pooled masks --
@@ -180,7 +182,11 @@ class TrainStep:
                 drc = R.drc_loss(cfg, proj_out, out["pooled_masks"], valid_samples)
                 total = total + drc.double() * drc_weight
                 out.update(drc_loss=drc)
-            if rgb_weight != 0 or drc_rgb_weight != 0:
+            if (rgb_weight != 0 or drc_rgb_weight != 0) and cfg.get("pc_rgb_deterministic", False):
+                # the decoder's colour sets, read in place through the projection's own replica / dropout addressing
+                all_rgb = out["rgb_1"]
+                grids = R.rgb_grids(cfg, proj_out, all_rgb, kernel, point_index=point_index)
+            elif rgb_weight != 0 or drc_rgb_weight != 0:
                 all_rgb = R.replicate_rgb(out["rgb_1"], out["poses"].shape[0], point_index)   # model_pc_to.py:254-258, 323-329
                 grids = R.rgb_grids(cfg, proj_out, all_rgb, kernel)   # one colour splat and smoothing for both colour terms
                 out.update(all_rgb=all_rgb)

@@ -17,9 +17,10 @@ import numpy as np
 import torch
 
 from . import _native
-from ._ops import (DepthLoss, DepthMap, DeviceSchedule, Drc, DrcLoss, DrcRgbLoss, Geometry, ProjectFused, ProjectLossFused, ProjectLossStep, RgbLoss, RgbMap, RgbSplat,
+from ._ops import (DepthLoss, DepthMap, DeviceSchedule, Drc, DrcLoss, DrcRgbLoss, Geometry, ProjectFused, ProjectLossFused, ProjectLossStep, RgbLoss, RgbMap, RgbSplat, RgbSplatFixed,
                    SilhouetteLoss, Smooth, Splat, Transform, status_word, taps_bucket)
 from ._ops import _plane as _ops_plane
+from ._ops import colour_sets as _ops_colour_sets
 from .predictions import chamfer_of_predictions, load_predictions, save_predictions  # noqa: F401
 from .alignment import (alignment_candidates, alignment_to_ground_truth, as_rotation_matrix, from_rotation_matrix,  # noqa: F401
                         icp_point_to_point, pose_errors, quat_w_avg_markley, quaternion_from_campos, reference_rotation)
@@ -721,7 +722,8 @@ def replicate_rgb(rgb, num_clouds, point_index=None):
     """Per-point colours [B/R,N,3] of shared point sets -> one row per cloud [B,n,3]: tf_repeat_0 over views and pose
     candidates, then the rgb half of pc_point_dropout -- cloud b keeps rgb[b // R][point_index[b]]
     (dpc/models/model_pc_to.py:254-258, 323-329).  Plain torch, differentiable; the renderer reads shared point sets in
-    place, the colour node wants the replicated tensor."""
+    place, and so does the colour node under cfg.pc_rgb_deterministic (rgb_grids with point_index=); without the key it
+    wants the replicated tensor."""
     S = rgb.shape[0]
     if S == 0 or num_clouds % S:
         raise ValueError("%d clouds cannot share %d colour sets: the number of clouds must be a multiple" % (num_clouds, S))
@@ -739,16 +741,23 @@ def _rgb_options(cfg):
             bool(_get(cfg, "pc_rgb_divide_by_occupancies", False)), float(_get(cfg, "pc_rgb_divide_by_occupancies_epsilon", 0.01)))
 
 
-def _rgb_grids(cfg, outputs, all_rgb, kernel):
+def _rgb_grids(cfg, outputs, all_rgb, kernel, point_index=None):
     """(geom, voxels [B,D,H,W], smoothed colour grid [B,3,D,H,W], occupancies to divide by | None) of a projection."""
     stop, clip_after, divide, _ = _rgb_options(cfg)
+    deterministic = bool(_get(cfg, "pc_rgb_deterministic", False))
     tr, vox = outputs["tr_pc"], outputs["voxels"]
-    if tuple(all_rgb.shape) != tuple(tr.shape):
+    if deterministic:
+        _ops_colour_sets(tr.shape, all_rgb.shape, point_index)   # per cloud, or colour sets read in place
+    elif point_index is not None or tuple(all_rgb.shape) != tuple(tr.shape):
         raise ValueError("all_rgb must hold one colour per projected point, %s (replicate_rgb makes it from the decoder's "
-                         "colours), got %s" % (tuple(tr.shape), tuple(all_rgb.shape)))
+                         "colours; colour sets and a point_index are read in place under pc_rgb_deterministic: true only), "
+                         "got %s%s" % (tuple(tr.shape), tuple(all_rgb.shape), "" if point_index is None else " and a point_index"))
     B = tr.shape[0]
     geom = _geometry(cfg, kernel)
-    C = RgbSplat.apply(tr, all_rgb, geom, stop)                      # point_cloud.py:98-134
+    if deterministic:                                                # point_cloud.py:98-134
+        C = RgbSplatFixed.apply(tr, all_rgb, geom, stop, point_index)
+    else:
+        C = RgbSplat.apply(tr, all_rgb, geom, stop)
     if not clip_after:
         C = torch.clamp(C, 0.0, 1.0)                                 # :245-246
     if kernel is not None:
@@ -762,22 +771,30 @@ def _rgb_grids(cfg, outputs, all_rgb, kernel):
     return geom, vox.reshape(B, geom.D, geom.H, geom.W), C, div
 
 
+def _make_rgb_grids(cfg, outputs, all_rgb, kernel, point_index):
+    """_rgb_grids, called the way it always was when there is no point_index."""
+    if point_index is None:
+        return _rgb_grids(cfg, outputs, all_rgb, kernel)
+    return _rgb_grids(cfg, outputs, all_rgb, kernel, point_index)
+
+
 def _rgb_outputs(outputs):
     if not isinstance(outputs, ProjectionOutputs):
         raise TypeError("outputs must be what pointcloud_project_fast returned, got %s" % type(outputs).__name__)
 
 
-def rgb_grids(cfg, outputs, all_rgb, kernel=None):
+def rgb_grids(cfg, outputs, all_rgb, kernel=None, point_index=None):
     """The grids every colour function starts from, made once: (geom, voxels [B,D,H,W], smoothed colour grid [B,3,D,H,W],
     occupancies to divide by | None) of the projection `outputs` and the colours all_rgb, as project_rgb describes them
     (splat, pre-clip, per-channel smoothing; the smoothed raw occupancies under pc_rgb_divide_by_occupancies).  Hand the
     result to project_rgb, proj_rgb_loss and drc_rgb_loss through `grids=`: they then share one colour splat and one set of
-    smoothing passes (most of a colour node's time) and their gradients add up at the grids."""
+    smoothing passes (most of a colour node's time) and their gradients add up at the grids.
+    point_index and the forms all_rgb may take: as in project_rgb."""
     _rgb_outputs(outputs)
-    return _rgb_grids(cfg, outputs, all_rgb, kernel)
+    return _make_rgb_grids(cfg, outputs, all_rgb, kernel, point_index)
 
 
-def project_rgb(cfg, outputs, all_rgb, kernel=None, grids=None):
+def project_rgb(cfg, outputs, all_rgb, kernel=None, grids=None, point_index=None):
     """The colour entries of the reference's output dict for the projection `outputs` (what pointcloud_project_fast
     returned, called with all_rgb=None): {"proj_rgb": [B,H,W,3], "voxels_rgb": [B,D,H,W,3]}.
 
@@ -790,11 +807,19 @@ def project_rgb(cfg, outputs, all_rgb, kernel=None, grids=None):
     ray-termination probabilities of outputs["voxels"] over a white background (project_volume_rgb_integral,
     dpc/util/drc.py:132-142).  `kernel` must be the one the projection was made with.  Differentiable to all_rgb, to the
     points, pose, translation and focal length through outputs["tr_pc"], and to everything behind outputs["voxels"].
-    The colour splat adds with fp32 atomics: results may differ in the last bits from run to run.
+    By default the colour splat adds with fp32 atomics: results may differ in the last bits from run to run.
+
+    cfg.pc_rgb_deterministic: true takes the bit-reproducible splat instead (64-bit fixed-point sums, RgbSplatFixed): the
+    colour grid and everything computed from it are the same bits on every run and for every order of the points.  all_rgb
+    may then also be the decoder's colour sets [B/R,N,3], read in place: cloud b takes rgb[b // R][point_index[b]] with
+    point_index [B,n] (the dropout rows handed to the projection), or rgb[b // R] when N == n and there is no index -- what
+    replicate_rgb would build, without building it; the gradient comes back in the sets' layout.  On this route colours must
+    satisfy |c| <= 8: a larger, NaN or infinite colour turns every voxel of its cloud's colour grid into NaN (the other
+    clouds are untouched).  Without the key, colour sets or a point_index raise ValueError.
     grids: what rgb_grids(cfg, outputs, all_rgb, kernel) returned, to share it with other colour functions (None: made here)."""
     _rgb_outputs(outputs)
     _, clip_after, _, div_eps = _rgb_options(cfg)
-    geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel) if grids is None else grids
+    geom, vox, C, div = _make_rgb_grids(cfg, outputs, all_rgb, kernel, point_index) if grids is None else grids
     proj_rgb = RgbMap.apply(vox, C, div, geom, div_eps, clip_after)
     Cf = C if div is None else C / (div.unsqueeze(1) + div_eps)
     if clip_after:
@@ -821,7 +846,8 @@ def _image_factor(outputs, images, what):
     return planar, f
 
 
-def proj_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None, return_rgb=False, grids=None):
+def proj_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None, return_rgb=False, grids=None,
+                  point_index=None):
     """add_proj_rgb_loss (dpc/util/losses.py:69-90) without its weight: (1/2) sum_s w_s^2 sum_{pix,c} (g - proj_rgb)^2 / S on
     the colour projection of project_rgb.  return_rgb: (loss, proj_rgb [S,H,W,3] detached) -- the image the loss was
     formed from, written by the same launch.
@@ -832,14 +858,15 @@ def proj_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None
     maps output pixel y to source coordinate y * Hi / H = f*y, an integer, so it samples exactly there and this is the
     reference's value.  valid_samples [S] | None: per-sample weights w, squared like proj_depth_loss's (None, the reference:
     all ones).  The caller multiplies by cfg.proj_rgb_weight.  Splat and smoothing as in project_rgb; integral, squared
-    error and their backward are one column kernel each way (csrc/dpc_rgb.hip).  grids: as in project_rgb."""
+    error and their backward are one column kernel each way (csrc/dpc_rgb.hip).  grids, point_index and
+    cfg.pc_rgb_deterministic (colour sets [S/R,N,3] read in place, |c| <= 8, a bit-reproducible loss): as in project_rgb."""
     if _get(cfg, "pc_gauss_filter_gt_rgb", False):
         raise NotImplementedError("pc_gauss_filter_gt_rgb: true -- smoothing of the ground-truth images is not implemented "
                                   "(gauss_smoothen_image, dpc/util/losses.py:78-83)")
     _rgb_outputs(outputs)
     planar, f = _image_factor(outputs, images, "colour loss")
     _, clip_after, _, div_eps = _rgb_options(cfg)
-    geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel) if grids is None else grids
+    geom, vox, C, div = _make_rgb_grids(cfg, outputs, all_rgb, kernel, point_index) if grids is None else grids
     loss, proj_rgb = RgbLoss.apply(vox, C, div, images, f, planar, valid_samples, geom, div_eps, clip_after)
     return (loss, proj_rgb) if return_rgb else loss
 
@@ -897,7 +924,7 @@ def drc_loss(cfg, outputs, masks, valid_samples=None):
     return cost.sum() / S
 
 
-def drc_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None, grids=None):
+def drc_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None, grids=None, point_index=None):
     """add_drc_rgb_loss (dpc/util/losses.py:32-46, 93-110) without its weight: sum_s w_s^2 sum_rays sum_k p_k psi_k / S with
     psi_k = sum_c (g_c - voxels_rgb_{k,c})^2 the squared distance of the colour of voxel k on the ray from the image's pixel,
     psi_D = sum_c (g_c - 1)^2 for the white background, and p the ray-termination probabilities of outputs["voxels"].
@@ -907,7 +934,7 @@ def drc_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None,
     defines this loss and its weight key (drc_rgb_weight) but never calls it from get_loss; the caller multiplies by the
     weight.  A node on (voxels, colour grid): one column kernel each way (csrc/dpc_drc_loss.hip), nothing of the size of
     [D+1,B,H,W] or [B,D,H,W,3] is built.  grids: as in project_rgb -- shared with proj_rgb_loss, the two losses cost one
-    splat and one set of smoothing passes."""
+    splat and one set of smoothing passes.  point_index and cfg.pc_rgb_deterministic: as in project_rgb."""
     if _get(cfg, "pc_gauss_filter_gt_rgb", False):
         raise NotImplementedError("pc_gauss_filter_gt_rgb: true -- smoothing of the ground-truth images is not implemented "
                                   "(gauss_smoothen_image, dpc/util/losses.py:78-83)")
@@ -915,7 +942,7 @@ def drc_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None,
     _rgb_outputs(outputs)
     planar, f = _image_factor(outputs, images, "drc colour loss")
     _, clip_after, _, div_eps = _rgb_options(cfg)
-    geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel) if grids is None else grids
+    geom, vox, C, div = _make_rgb_grids(cfg, outputs, all_rgb, kernel, point_index) if grids is None else grids
     return DrcRgbLoss.apply(vox, C, div, images, f, planar, valid_samples, geom, div_eps, clip_after)
 
 

@@ -74,6 +74,9 @@ _FUNCTIONS = (
     ("dpc_rgb_splat_bwd", _i, [_pp] + [_vp] * 6),
     ("dpc_rgb_loss_fwd", _i, [_pp] + [_vp] * 3 + [ctypes.c_float, _i, _vp, _i, _i] + [_vp] * 5),
     ("dpc_rgb_loss_bwd", _i, [_pp] + [_vp] * 3 + [ctypes.c_float, _i, _vp, _i, _i] + [_vp] * 7),
+    ("dpc_rgb_splat_fixed_workspace_bytes", _sz, [_pp, _i]),
+    ("dpc_rgb_splat_fixed_fwd", _i, [_pp, _vp, _vp, _i, _vp, _vp, _vp]),
+    ("dpc_rgb_splat_fixed_bwd", _i, [_pp, _vp, _vp, _i] + [_vp] * 5),
     ("dpc_drc_workspace_bytes", _sz, [_pp]),
     ("dpc_drc_loss_fwd", _i, [_pp] + [_vp] * 4 + [_i] + [_vp] * 4),
     ("dpc_drc_loss_bwd", _i, [_pp] + [_vp] * 4 + [_i] + [_vp] * 6),

@@ -968,6 +968,76 @@ class RgbSplat(torch.autograd.Function):
         return _like_input(dtr, ctx.metas[0]), _like_input(drgb, ctx.metas[1]), None, None
 
 
+def colour_sets(tr_shape, rgb_shape, point_index=None):
+    """Layout check of colours that are read through the shared-set convention (RgbSplatFixed): tr [B,n,3], colours
+    [B/R,N,3], point_index [B,n] | None (then N == n).  Returns R.  Host only: shapes in, ValueError out."""
+    tr_shape, rgb_shape = tuple(tr_shape), tuple(rgb_shape)
+    if len(tr_shape) != 3 or tr_shape[2] != 3:
+        raise ValueError("the transformed points must be [B,n,3], got %s" % (tr_shape,))
+    B, n = tr_shape[0], tr_shape[1]
+    if point_index is not None and tuple(point_index.shape) != (B, n):
+        raise ValueError("point_index must be [%d, %d] (one colour index per projected point), got %s"
+                         % (B, n, tuple(point_index.shape)))
+    sets = len(rgb_shape) == 3 and rgb_shape[2] == 3 and (rgb_shape[0] == B or (rgb_shape[0] > 0 and B % rgb_shape[0] == 0))
+    if sets and point_index is None:
+        sets = rgb_shape[1] == n
+    elif sets:
+        sets = rgb_shape[1] >= 1 or B == 0
+    if not sets:
+        raise ValueError("all_rgb must hold one colour per projected point, %s, or colour sets [B/R,N,3] shared by R consecutive "
+                         "clouds each (N = %d, or any N >= 1 with a point_index [%d,%d]), got %s"
+                         % (tr_shape, n, B, n, rgb_shape))
+    return 1 if rgb_shape[0] == B else B // rgb_shape[0]
+
+
+class RgbSplatFixed(torch.autograd.Function):
+    """RgbSplat with a bit-reproducible sum, reading shared colour sets in place: tr [B,n,3] (z,y,x), rgb [B/R,N,3] ->
+    colour grid [B,3,D,H,W] (planar).  The colour of point i of cloud b is rgb[b // R][point_index[b, i]] (point_index
+    [B,n] | None: N == n and the index is i) -- what replicate_rgb would materialise.  Every contribution is k_rgb_splat's
+    fp32 product, rounded once to 64-bit fixed point (2^-40) and added as an integer: the grid is the same bits on every
+    run and for every order of the points.  Colours must satisfy |c| <= 8; a larger, NaN or infinite colour makes every voxel
+    of its cloud NaN (other clouds are untouched).  Backward: d(tr) per cloud (none under stop_points_gradient), d(rgb) in
+    the sets' own layout, summed in fixed point where clouds share a set; a contribution with no fixed-point value (NaN,
+    Inf, magnitude >= 2^20) makes that set's gradient NaN.  Workspaces come from torch's allocator."""
+
+    @staticmethod
+    def forward(ctx, tr, rgb, geom, stop_points_gradient=False, point_index=None):
+        reps = colour_sets(tr.shape, rgb.shape, point_index)
+        dev = N.require_device(tr, rgb, point_index)
+        tr32, rgb32 = _f32(tr), _f32(rgb)
+        idx = None if point_index is None else point_index.detach().to(torch.int32).contiguous()
+        B, Npts, n_set = tr32.shape[0], tr32.shape[1], rgb32.shape[1]
+        Z = geom.sized(B, Npts, reps, idx, n_set if idx is not None else 0)
+        out = torch.empty((B, 3, geom.D, geom.H, geom.W), dtype=torch.float32, device=dev)
+        with _on(dev):
+            ws = torch.empty((max(N.lib().dpc_rgb_splat_fixed_workspace_bytes(Z.ref, n_set), 16),), dtype=torch.uint8, device=dev)
+            rc = N.lib().dpc_rgb_splat_fixed_fwd(Z.ref, _dp(tr32), _dp(rgb32), n_set, _dp(out), _dp(ws), _stream(dev))
+        if rc != 0:
+            N.check(rc, "dpc_rgb_splat_fixed_fwd")
+        ctx.geom, ctx.saved, ctx.metas = geom, (tr32, rgb32, idx), (_meta(tr), _meta(rgb))
+        ctx.stop, ctx.reps = bool(stop_points_gradient), reps
+        return out
+
+    @staticmethod
+    def backward(ctx, dC):
+        tr32, rgb32, idx = ctx.saved
+        dev, geom, reps = tr32.device, ctx.geom, ctx.reps
+        n_set, sets = rgb32.shape[1], rgb32.shape[0]
+        Z = geom.sized(tr32.shape[0], tr32.shape[1], reps, idx, n_set if idx is not None else 0)
+        dC32 = _f32(dC)
+        drgb = torch.empty_like(rgb32)
+        dtr = torch.empty_like(tr32) if (ctx.needs_input_grad[0] and not ctx.stop) else None
+        ws = None
+        if reps > 1 or idx is not None:   # the sets' 64-bit sums and poison words (include/dpc_render.h)
+            ws = torch.empty(((24 * sets * n_set + 4 * sets + 255) // 256 * 256 + 16,), dtype=torch.uint8, device=dev)
+        with _on(dev):
+            rc = N.lib().dpc_rgb_splat_fixed_bwd(Z.ref, _dp(tr32), _dp(rgb32), n_set, _dp(dC32), _dp(drgb), _dp(dtr), _dp(ws),
+                                                 _stream(dev))
+        if rc != 0:
+            N.check(rc, "dpc_rgb_splat_fixed_bwd")
+        return _like_input(dtr, ctx.metas[0]), _like_input(drgb, ctx.metas[1]), None, None, None
+
+
 def _rgb_inputs(vox, C, div, geom):
     dev = N.require_device(vox, C, div)
     v32, c32, d32 = _f32(vox), _f32(C), _f32(div)
@@ -995,6 +1065,11 @@ def _rgb_loss_forward(ctx, entry, with_proj, vox, C, div, gt, gt_factor, gt_plan
     B = v32.shape[0]
     eps, clip = _rgb_options(ctx, div_eps, clip_after, gt_factor, gt_planar)
     gt32, w32 = _loss_targets(v32, gt, weights, ctx.gt_factor, geom, "images", rgb=True)
+    if B == 0:   # an empty shard: nothing to launch (empty tensors have no address to hand over), the loss of nothing is 0
+        ctx.empty, ctx.dev, ctx.saved, ctx.metas = True, dev, (None,) * 6, (_meta(vox), _meta(C))
+        return (torch.zeros((), dtype=torch.float32, device=dev),
+                torch.zeros((0, geom.H, geom.W, 3), dtype=torch.float32, device=dev) if with_proj else None)
+    ctx.empty = False
     tiles, loss = _loss_buffers(B, geom, dev)
     proj = torch.empty((B, geom.H, geom.W, 3), dtype=torch.float32, device=dev) if with_proj else None
     _call(dev, entry, geom.sized(B, 0).ref, _dp(v32), _dp(c32), _dp(d32), eps, clip, _dp(gt32), ctx.gt_factor, ctx.gt_planar,
@@ -1006,6 +1081,8 @@ def _rgb_loss_forward(ctx, entry, with_proj, vox, C, div, gt, gt_factor, gt_plan
 def _rgb_backward(ctx, entry, *grads):
     """One launch: d voxels and d colour grid (both overwritten).  `grads`: what the entry takes between the weights and the
     outputs -- the saved image where it needs one, the gradients arriving at the node's outputs (None = absent)."""
+    if getattr(ctx, "empty", False):
+        return _zero_grads(ctx.metas, ctx.dev)
     v32, c32, d32, gt32, w32, _ = ctx.saved
     geom, dev = ctx.geom, v32.device
     dvox, dC = torch.empty_like(v32), torch.empty_like(c32)

@@ -11,10 +11,17 @@ occupancies are leaves, and what is timed is the colour node on top of them, dow
 transformed points and the occupancies.
 
     python tools/bench_rgb_loss.py [--clouds 32] [--points 8000] [--grid 64] [--reps 50] [--warmup 10] [--route both]
-                                   [--config all] [--out FILE]
+                                   [--config all] [--out FILE] [--deterministic [--set-replicas 4]]
 
 GPU time by device events around `reps` back-to-back calls after `warmup` calls of the same shape; the two routes alternate
-in windows.  --route new|torch with --reps small: one route alone, for a run under rocprofv3 --kernel-trace --stats."""
+in windows.  --route new|torch with --reps small: one route alone, for a run under rocprofv3 --kernel-trace --stats.
+
+--deterministic: the second route is not the torch composition but the package's own bit-reproducible colour splat
+(cfg.pc_rgb_deterministic: 64-bit fixed-point sums), "fixed" -- the default route ("new", fp32 atomics) and "fixed" alternate
+in windows on the same inputs.  Two more pairs of figures say what reading colour sets in place saves: "fixed_sets", the
+deterministic route fed colour sets [clouds / set-replicas, points, 3] and a point_index [clouds, points] (a permutation per
+cloud), and "replicate_rgb", the replicate_rgb call (and its autograd backward) that the default route needs in front of it
+for the same sets and index.  --route new|fixed: one route alone.  Lines go to profiles/rgb_splat_fixed_bench.jsonl."""
 import argparse
 import json
 import os
@@ -130,18 +137,41 @@ def run_config(a, name, dev):
             fn().backward()
         return run
 
-    fns = {"new_forward_ms": forward(new_loss), "torch_forward_ms": forward(torch_loss),
-           "new_forward_backward_ms": both(new_loss), "torch_forward_backward_ms": both(torch_loss)}
+    other = "fixed" if a.deterministic else "torch"
+    if a.deterministic:
+        det = Cfg(cfg, pc_rgb_deterministic=True)
+        sets_n = B // a.set_replicas
+        rgb_sets = (0.05 + 0.9 * torch.rand(sets_n, N, 3, generator=gen)).float().to(dev).requires_grad_(True)
+        index = torch.stack([torch.randperm(N, generator=gen) for _ in range(B)]).to(torch.int32).to(dev)
+        leaves = leaves + (rgb_sets,)
+
+        def other_loss():
+            return R.proj_rgb_loss(det, outputs(), rgb, images, kernel)
+
+        def sets_loss():
+            return R.proj_rgb_loss(det, outputs(), rgb_sets, images, kernel, point_index=index)
+
+        def replicate():
+            return R.replicate_rgb(rgb_sets, B, index).sum()
+    else:
+        other_loss = torch_loss
+    fns = {"new_forward_ms": forward(new_loss), other + "_forward_ms": forward(other_loss),
+           "new_forward_backward_ms": both(new_loss), other + "_forward_backward_ms": both(other_loss)}
     if a.route != "both":
-        fns = {k: v for k, v in fns.items() if k.startswith(a.route)}
+        fns = {k: v for k, v in fns.items() if k.startswith(a.route + "_forward")}
+    elif a.deterministic:
+        fns.update({"fixed_sets_forward_ms": forward(sets_loss), "fixed_sets_forward_backward_ms": both(sets_loss),
+                    "replicate_rgb_forward_ms": forward(replicate), "replicate_rgb_forward_backward_ms": both(replicate)})
     agree = None
     if a.route == "both":     # the two routes compute the same thing
         fns["new_forward_backward_ms"]()
-        g_new, l_new = [x.grad.clone() for x in leaves], float(fns["new_forward_ms"]())
-        fns["torch_forward_backward_ms"]()
-        agree = {"loss_rel_diff": abs(l_new - float(fns["torch_forward_ms"]())) / abs(l_new)}
+        g_new, l_new = [x.grad.clone() for x in leaves[:3]], float(fns["new_forward_ms"]())
+        fns[other + "_forward_backward_ms"]()
+        agree = {"loss_rel_diff": abs(l_new - float(fns[other + "_forward_ms"]())) / abs(l_new)}
         for nm, gn, x in zip(("dtr", "drgb", "dvox"), g_new, leaves):
             agree[nm + "_max_abs_diff_over_scale"] = float((gn - x.grad).abs().max()) / max(1.0, float(x.grad.abs().max()))
+        if a.deterministic:   # the point of the route: the same bits from call to call
+            agree["fixed_loss_bit_equal_on_repeat"] = bool(torch.equal(fns["fixed_forward_ms"](), fns["fixed_forward_ms"]()))
     for fn in fns.values():          # every shape the timed windows use
         for _ in range(a.warmup):
             fn()
@@ -151,14 +181,17 @@ def run_config(a, name, dev):
         for k, fn in fns.items():
             times[k].append(event_ms(fn, a.reps))
     med = {k: round(sorted(v)[len(v) // 2], 4) for k, v in times.items()}
-    res = {"bench": "rgb_loss", "config": name, "clouds": B, "points": N, "grid": G, "gt_factor": f, "sigma_rel": 1.5, "taps": 11,
+    res = {"bench": "rgb_splat_fixed" if a.deterministic else "rgb_loss", "config": name, "clouds": B, "points": N, "grid": G, "gt_factor": f, "sigma_rel": 1.5, "taps": 11,
            "reps": a.reps, "warmup": a.warmup, "windows": a.windows, "route": a.route, "timing": "device events, median window",
-           "colour_grid_mb": round(B * 3 * G * G * G * 4 / 1e6, 1), "splat_atomic_mb": round(B * N * 8 * 3 * 4 / 1e6, 1), **med,
+           "colour_grid_mb": round(B * 3 * G * G * G * 4 / 1e6, 1), "splat_atomic_mb": round(B * N * 8 * 3 * 4 / 1e6, 1),
+           **({"fixed_workspace_mb": round((B * 3 * G * G * G * 8 + B * 4) / 1e6, 1), "fixed_atomic_mb": round(B * N * 8 * 3 * 8 / 1e6, 1),
+               "set_replicas": a.set_replicas} if a.deterministic else {}), **med,
            "spread_ms": {k: [round(min(v), 4), round(max(v), 4)] for k, v in times.items()},
            "device": torch.cuda.get_device_name(0)}
     if a.route == "both":
-        res["speedup_forward"] = round(med["torch_forward_ms"] / med["new_forward_ms"], 2)
-        res["speedup_forward_backward"] = round(med["torch_forward_backward_ms"] / med["new_forward_backward_ms"], 2)
+        if not a.deterministic:
+            res["speedup_forward"] = round(med["torch_forward_ms"] / med["new_forward_ms"], 2)
+            res["speedup_forward_backward"] = round(med["torch_forward_backward_ms"] / med["new_forward_backward_ms"], 2)
         res["agreement"] = agree
     line = json.dumps(res)
     print(line)
@@ -175,10 +208,19 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--route", default="both", choices=["both", "new", "torch"])
+    ap.add_argument("--route", default="both", choices=["both", "new", "torch", "fixed"])
+    ap.add_argument("--deterministic", action="store_true",
+                    help="compare the default route with the bit-reproducible one (pc_rgb_deterministic) instead of with torch")
+    ap.add_argument("--set-replicas", type=int, default=4, help="--deterministic: clouds per colour set of the sets figures")
     ap.add_argument("--config", default="all", choices=["all"] + list(CONFIGS))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rgb_loss_bench.jsonl"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "rgb_splat_fixed_bench.jsonl" if a.deterministic else "rgb_loss_bench.jsonl")
+    if (a.route == "fixed" and not a.deterministic) or (a.route == "torch" and a.deterministic):
+        ap.error("--route fixed goes with --deterministic, --route torch without it")
+    if a.deterministic and (a.set_replicas < 1 or a.clouds % a.set_replicas):
+        ap.error("--set-replicas must divide --clouds")
     if not torch.cuda.is_available():
         raise SystemExit("bench_rgb_loss.py measures on a GPU; none is visible")
     for name in (CONFIGS if a.config == "all" else [a.config]):
