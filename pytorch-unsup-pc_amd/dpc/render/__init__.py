@@ -771,13 +771,6 @@ def _rgb_grids(cfg, outputs, all_rgb, kernel, point_index=None):
     return geom, vox.reshape(B, geom.D, geom.H, geom.W), C, div
 
 
-def _make_rgb_grids(cfg, outputs, all_rgb, kernel, point_index):
-    """_rgb_grids, called the way it always was when there is no point_index."""
-    if point_index is None:
-        return _rgb_grids(cfg, outputs, all_rgb, kernel)
-    return _rgb_grids(cfg, outputs, all_rgb, kernel, point_index)
-
-
 def _rgb_outputs(outputs):
     if not isinstance(outputs, ProjectionOutputs):
         raise TypeError("outputs must be what pointcloud_project_fast returned, got %s" % type(outputs).__name__)
@@ -791,7 +784,7 @@ def rgb_grids(cfg, outputs, all_rgb, kernel=None, point_index=None):
     smoothing passes (most of a colour node's time) and their gradients add up at the grids.
     point_index and the forms all_rgb may take: as in project_rgb."""
     _rgb_outputs(outputs)
-    return _make_rgb_grids(cfg, outputs, all_rgb, kernel, point_index)
+    return _rgb_grids(cfg, outputs, all_rgb, kernel, point_index)
 
 
 def project_rgb(cfg, outputs, all_rgb, kernel=None, grids=None, point_index=None):
@@ -819,7 +812,7 @@ def project_rgb(cfg, outputs, all_rgb, kernel=None, grids=None, point_index=None
     grids: what rgb_grids(cfg, outputs, all_rgb, kernel) returned, to share it with other colour functions (None: made here)."""
     _rgb_outputs(outputs)
     _, clip_after, _, div_eps = _rgb_options(cfg)
-    geom, vox, C, div = _make_rgb_grids(cfg, outputs, all_rgb, kernel, point_index) if grids is None else grids
+    geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel, point_index) if grids is None else grids
     proj_rgb = RgbMap.apply(vox, C, div, geom, div_eps, clip_after)
     Cf = C if div is None else C / (div.unsqueeze(1) + div_eps)
     if clip_after:
@@ -866,7 +859,7 @@ def proj_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None
     _rgb_outputs(outputs)
     planar, f = _image_factor(outputs, images, "colour loss")
     _, clip_after, _, div_eps = _rgb_options(cfg)
-    geom, vox, C, div = _make_rgb_grids(cfg, outputs, all_rgb, kernel, point_index) if grids is None else grids
+    geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel, point_index) if grids is None else grids
     loss, proj_rgb = RgbLoss.apply(vox, C, div, images, f, planar, valid_samples, geom, div_eps, clip_after)
     return (loss, proj_rgb) if return_rgb else loss
 
@@ -942,7 +935,7 @@ def drc_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None,
     _rgb_outputs(outputs)
     planar, f = _image_factor(outputs, images, "drc colour loss")
     _, clip_after, _, div_eps = _rgb_options(cfg)
-    geom, vox, C, div = _make_rgb_grids(cfg, outputs, all_rgb, kernel, point_index) if grids is None else grids
+    geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel, point_index) if grids is None else grids
     return DrcRgbLoss.apply(vox, C, div, images, f, planar, valid_samples, geom, div_eps, clip_after)
 
 

@@ -928,9 +928,28 @@ class DepthLoss(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------------
-# Colour: splat, projection and loss (csrc/dpc_rgb.hip)
+# Colour: splat (csrc/dpc_rgb_splat.hip), projection and loss (csrc/dpc_rgb.hip)
 # reference (TF-1 originals): dpc/util/point_cloud.py:98-134, 244-262, 275-277; dpc/util/drc.py:132-142; dpc/util/losses.py:69-90
 # ------------------------------------------------------------------------------------------------------
+def _splat_forward(ctx, entry, tr, rgb, Z, geom, stop, n_set=(), ws=()):
+    """Forward of a colour splat, the grid [B,3,D,H,W]; n_set / ws: the fixed-point entry's own arguments, as tuples."""
+    tr32, rgb32 = _f32(tr), _f32(rgb)
+    out = torch.empty((tr32.shape[0], 3, geom.D, geom.H, geom.W), dtype=torch.float32, device=tr32.device)
+    _call(tr32.device, entry, Z.ref, _dp(tr32), _dp(rgb32), *n_set, _dp(out), *ws)
+    ctx.Z, ctx.saved, ctx.metas, ctx.stop = Z, (tr32, rgb32), (_meta(tr), _meta(rgb)), bool(stop)
+    return out
+
+
+def _splat_backward(ctx, entry, dC, n_set=(), ws=()):
+    """Backward of a colour splat: (d tr | None, d rgb) in the inputs' dtypes and shapes."""
+    tr32, rgb32 = ctx.saved
+    dC32 = _f32(dC)
+    drgb = torch.empty_like(rgb32)
+    dtr = torch.empty_like(tr32) if (ctx.needs_input_grad[0] and not ctx.stop) else None
+    _call(tr32.device, entry, ctx.Z.ref, _dp(tr32), _dp(rgb32), *n_set, _dp(dC32), _dp(drgb), _dp(dtr), *ws)
+    return _like_input(dtr, ctx.metas[0]), _like_input(drgb, ctx.metas[1])
+
+
 class RgbSplat(torch.autograd.Function):
     """The rgb half of pointcloud2voxels3d_fast: tr [B,N,3] (z,y,x), rgb [B,N,3] -> colour grid [B,3,D,H,W] (planar), the
     points' trilinear weights times their colours, in the cells of the occupancy splat.  fp32 atomics: the grid is not
@@ -938,34 +957,15 @@ class RgbSplat(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tr, rgb, geom, stop_points_gradient=False):
-        dev = N.require_device(tr, rgb)
-        tr32, rgb32 = _f32(tr), _f32(rgb)
-        if tr32.dim() != 3 or tr32.shape[2] != 3 or tuple(rgb32.shape) != tuple(tr32.shape):
+        N.require_device(tr, rgb)
+        if tr.dim() != 3 or tr.shape[2] != 3 or tuple(rgb.shape) != tuple(tr.shape):
             raise ValueError("rgb must hold one colour per point, [B,N,3] like the points %s, got %s"
                              % (tuple(tr.shape), tuple(rgb.shape)))
-        B, Npts = tr32.shape[0], tr32.shape[1]
-        Z = geom.sized(B, Npts)
-        out = torch.empty((B, 3, geom.D, geom.H, geom.W), dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = N.lib().dpc_rgb_splat_fwd(Z.ref, _dp(tr32), _dp(rgb32), _dp(out), _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_rgb_splat_fwd")
-        ctx.geom, ctx.saved, ctx.metas, ctx.stop = geom, (tr32, rgb32), (_meta(tr), _meta(rgb)), bool(stop_points_gradient)
-        return out
+        return _splat_forward(ctx, "dpc_rgb_splat_fwd", tr, rgb, geom.sized(tr.shape[0], tr.shape[1]), geom, stop_points_gradient)
 
     @staticmethod
     def backward(ctx, dC):
-        tr32, rgb32 = ctx.saved
-        dev, geom = tr32.device, ctx.geom
-        Z = geom.sized(tr32.shape[0], tr32.shape[1])
-        dC32 = _f32(dC)
-        drgb = torch.empty_like(rgb32)
-        dtr = torch.empty_like(tr32) if (ctx.needs_input_grad[0] and not ctx.stop) else None
-        with _on(dev):
-            rc = N.lib().dpc_rgb_splat_bwd(Z.ref, _dp(tr32), _dp(rgb32), _dp(dC32), _dp(drgb), _dp(dtr), _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_rgb_splat_bwd")
-        return _like_input(dtr, ctx.metas[0]), _like_input(drgb, ctx.metas[1]), None, None
+        return _splat_backward(ctx, "dpc_rgb_splat_bwd", dC) + (None, None)
 
 
 def colour_sets(tr_shape, rgb_shape, point_index=None):
@@ -1004,38 +1004,19 @@ class RgbSplatFixed(torch.autograd.Function):
     def forward(ctx, tr, rgb, geom, stop_points_gradient=False, point_index=None):
         reps = colour_sets(tr.shape, rgb.shape, point_index)
         dev = N.require_device(tr, rgb, point_index)
-        tr32, rgb32 = _f32(tr), _f32(rgb)
-        idx = None if point_index is None else point_index.detach().to(torch.int32).contiguous()
-        B, Npts, n_set = tr32.shape[0], tr32.shape[1], rgb32.shape[1]
-        Z = geom.sized(B, Npts, reps, idx, n_set if idx is not None else 0)
-        out = torch.empty((B, 3, geom.D, geom.H, geom.W), dtype=torch.float32, device=dev)
-        with _on(dev):
-            ws = torch.empty((max(N.lib().dpc_rgb_splat_fixed_workspace_bytes(Z.ref, n_set), 16),), dtype=torch.uint8, device=dev)
-            rc = N.lib().dpc_rgb_splat_fixed_fwd(Z.ref, _dp(tr32), _dp(rgb32), n_set, _dp(out), _dp(ws), _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_rgb_splat_fixed_fwd")
-        ctx.geom, ctx.saved, ctx.metas = geom, (tr32, rgb32, idx), (_meta(tr), _meta(rgb))
-        ctx.stop, ctx.reps = bool(stop_points_gradient), reps
-        return out
+        ctx.idx = idx = None if point_index is None else point_index.detach().to(torch.int32).contiguous()   # Z points at it
+        ctx.shared, n_set = reps > 1 or idx is not None, rgb.shape[1]
+        Z = geom.sized(tr.shape[0], tr.shape[1], reps, idx, n_set if idx is not None else 0)
+        ws = torch.empty((max(N.lib().dpc_rgb_splat_fixed_workspace_bytes(Z.ref, n_set), 16),), dtype=torch.uint8, device=dev)
+        return _splat_forward(ctx, "dpc_rgb_splat_fixed_fwd", tr, rgb, Z, geom, stop_points_gradient, (n_set,), (_dp(ws),))
 
     @staticmethod
     def backward(ctx, dC):
-        tr32, rgb32, idx = ctx.saved
-        dev, geom, reps = tr32.device, ctx.geom, ctx.reps
-        n_set, sets = rgb32.shape[1], rgb32.shape[0]
-        Z = geom.sized(tr32.shape[0], tr32.shape[1], reps, idx, n_set if idx is not None else 0)
-        dC32 = _f32(dC)
-        drgb = torch.empty_like(rgb32)
-        dtr = torch.empty_like(tr32) if (ctx.needs_input_grad[0] and not ctx.stop) else None
+        sets, n_set = ctx.saved[1].shape[:2]
         ws = None
-        if reps > 1 or idx is not None:   # the sets' 64-bit sums and poison words (include/dpc_render.h)
-            ws = torch.empty(((24 * sets * n_set + 4 * sets + 255) // 256 * 256 + 16,), dtype=torch.uint8, device=dev)
-        with _on(dev):
-            rc = N.lib().dpc_rgb_splat_fixed_bwd(Z.ref, _dp(tr32), _dp(rgb32), n_set, _dp(dC32), _dp(drgb), _dp(dtr), _dp(ws),
-                                                 _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_rgb_splat_fixed_bwd")
-        return _like_input(dtr, ctx.metas[0]), _like_input(drgb, ctx.metas[1]), None, None, None
+        if ctx.shared:   # the sets' 64-bit sums and poison words (include/dpc_render.h)
+            ws = torch.empty(((24 * sets * n_set + 4 * sets + 255) // 256 * 256 + 16,), dtype=torch.uint8, device=dC.device)
+        return _splat_backward(ctx, "dpc_rgb_splat_fixed_bwd", dC, (n_set,), (_dp(ws),)) + (None,) * 3
 
 
 def _rgb_inputs(vox, C, div, geom):

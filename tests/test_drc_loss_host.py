@@ -230,7 +230,7 @@ def test_the_three_colour_functions_accept_shared_grids(monkeypatch):
     made = []
     sentinel = ("geom", torch.zeros(2, 8, 8, 8), torch.zeros(2, 3, 8, 8, 8), torch.ones(2, 8, 8, 8))
 
-    def fake_grids(cfg_, outputs, all_rgb, kernel):
+    def fake_grids(cfg_, outputs, all_rgb, kernel, point_index=None):
         made.append((outputs, all_rgb, kernel))
         return sentinel
 

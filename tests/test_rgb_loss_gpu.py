@@ -1,4 +1,4 @@
-"""The colour node on the GPU (csrc/dpc_rgb.hip, dpc.render.project_rgb / proj_rgb_loss) against the fp64 oracle of
+"""The colour node on the GPU (csrc/dpc_rgb_splat.hip, csrc/dpc_rgb.hip, dpc.render.project_rgb / proj_rgb_loss) against the fp64 oracle of
 tests/rgb_oracle.py.
 
 Every comparison uses the parity rule of tests/test_gpu_parity.py, max |device - reference| <= 1e-5 * max(1, max |reference|).

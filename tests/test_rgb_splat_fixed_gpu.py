@@ -1,4 +1,4 @@
-"""The bit-reproducible colour splat on the GPU (csrc/dpc_rgb_fixed.hip, cfg.pc_rgb_deterministic) against the fp64 oracle of
+"""The bit-reproducible colour splat on the GPU (csrc/dpc_rgb_splat.hip, cfg.pc_rgb_deterministic) against the fp64 oracle of
 tests/rgb_oracle.py, and against itself: bit for bit under a permutation of the points, from call to call, and between
 colour sets read in place and the replicated tensor.
 
@@ -257,7 +257,32 @@ def test_range_guard_set_gradients():
     assert torch.equal(hot[1], clean[1])
 
 
-# ------------------------------------------------------------------------------------------------ 6. drc_rgb_loss
+# ------------------------------------------------------------------------------------------------ 6. the two backwards
+def test_backward_bits_equal_the_default_route():
+    """Per-cloud colours (no sets, no point_index): both routes' backward is a pure gather through one body, so d(tr) and
+    d(rgb) of RgbSplat and RgbSplatFixed are the same bits, with and without stop_points_gradient."""
+    import dpc.render as R
+    from dpc.render._ops import RgbSplat, RgbSplatFixed
+
+    c = A_CUBE
+    tr, rgb, _, _, _, _ = node_inputs(c)
+    geom = R._geometry(c.cfg(), None)
+    dC = torch.randn(c.B, 3, c.D, c.G, c.G, generator=torch.Generator().manual_seed(7300)).cuda()
+    for stop in (False, True):
+        grads = []
+        for node in (RgbSplat, RgbSplatFixed):
+            leaves = [dev(tr, True), dev(rgb, True)]
+            node.apply(leaves[0], leaves[1], geom, stop).backward(dC)
+            grads.append([x.grad for x in leaves])
+        (dtr, drgb), (dtr_fixed, drgb_fixed) = grads
+        assert torch.equal(drgb, drgb_fixed) and float(drgb.abs().max()) > 1e-3, stop
+        if stop:
+            assert dtr is None and dtr_fixed is None
+        else:
+            assert torch.equal(dtr, dtr_fixed) and float(dtr.abs().max()) > 1e-3
+
+
+# ------------------------------------------------------------------------------------------------ 7. drc_rgb_loss
 def test_drc_rgb_loss_through_shared_grids():
     import dpc.render as R
 
@@ -280,7 +305,7 @@ def test_drc_rgb_loss_through_shared_grids():
     assert torch.equal(losses[0], losses[1])
 
 
-# ------------------------------------------------------------------------------------------------ 7. empty inputs
+# ------------------------------------------------------------------------------------------------ 8. empty inputs
 def test_empty_inputs():
     import dpc.render as R
 
@@ -308,7 +333,7 @@ def test_empty_inputs():
     assert rgb.grad is None or rgb.grad.shape == (2, 0, 3)
 
 
-# ------------------------------------------------------------------------------------------------ 8. harness
+# ------------------------------------------------------------------------------------------------ 9. harness
 def test_harness_reads_colour_sets_in_place():
     from dpc.harness.config import chair_unsupervised
     from dpc.harness.step import TrainStep
