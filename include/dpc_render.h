@@ -315,6 +315,35 @@ int dpc_silhouette_loss(const float* gt, int gt_factor, const float* weights, co
                         float* loss_part, int32_t* winner, float* dpred, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The exact Gaussian occupancy renderer: pointcloud2voxels of the TF-1 original (dpc/util/point_cloud.py:17-57), the
+ * branch of cfg.pc_fast == false (dpc/models/model_pc.py:239-250).  Added without a new ABI number.
+ *   c_i = -1 + 2 i / (G-1) (tf.linspace(-1, 1, G): the grid spans [-1,1] although the points live in [-1/2,1/2]),
+ *   e_a[n,i] = exp(-(tr[n,a] - c_i)^2 / (2 sigma^2)),  raw[b,z,y,x] = k sum_n e_0[n,z] e_1[n,y] e_2[n,x],  vox = clip(raw, 0, 1)
+ * with tr [B,N,3] the transformed points in (z,y,x) order and G = D = H = W.  There is no outlier filter (a point outside
+ * the cube adds its tail), no occupancy scale, no translation and no learned focal length on this path.  `normalise`:
+ *   DPC_GAUSS_NORM_NONE        k = 1
+ *   DPC_GAUSS_NORM_ANALYTICAL  k = 1 / (1.78984352254 (sigma G)^3)                       (pc_normalise_gauss_analytical)
+ *   DPC_GAUSS_NORM_PER_POINT   k = 1 and every e_a[n,:] is divided by its own sum over i  (pc_normalise_gauss, which wins)
+ * Both directions are fp32 matrix products over the three 1-D tables (csrc/dpc_gauss_voxels.hip): nothing larger than the
+ * grid is stored, there is no float atomic, and equal inputs give equal bits on every run.  sigma is a launch argument, so
+ * a captured graph cannot follow a sigma schedule on this path.
+ * forward:  raw [B,G,G,G] | NULL (the sums before the clip: what the backward takes its pass-through set from; a caller
+ *           that wants no gradient passes NULL), vox [B,G,G,G].  N == 0 writes a zero grid.
+ * backward: raw as written by the forward, dvox [B,G,G,G] -> dtr [B,N,3]; the pass-through set is the inclusive one of
+ *           tf.clip_by_value and torch.clamp, 0 <= raw <= 1.  One launch.  N == 0: nothing to write.
+ * DPC_ERR_SHAPE before any launch for D != H or H != W, point_replicas > 1, a point_index, sigma <= 0 or not finite, an
+ * unknown `normalise`; DPC_ERR_LDS for G > DPC_GAUSS_MAX_SIDE (the backward keeps three [G,32] tables per wave and two
+ * 32 x G tiles of the gradient in LDS); DPC_ERR_NULL for a missing pointer; B == 0 returns DPC_OK with nothing launched.
+ * Nothing allocates or synchronises. */
+#define DPC_GAUSS_NORM_NONE 0
+#define DPC_GAUSS_NORM_ANALYTICAL 1
+#define DPC_GAUSS_NORM_PER_POINT 2
+#define DPC_GAUSS_MAX_SIDE 64
+int dpc_gauss_voxels_fwd(const DpcParams* p, const float* tr, double sigma, int normalise, float* raw, float* vox, void* stream);
+int dpc_gauss_voxels_bwd(const DpcParams* p, const float* tr, double sigma, int normalise, const float* raw, const float* dvox,
+                         float* dtr, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Expected depth and its loss, fused (add_proj_depth_loss, dpc/util/losses.py:113-136, on drc_depth_projection,
  * dpc/util/drc.py:145-160): from grid_wh of dpc_project_fwd (the grid after the clamp and the W, H passes) in one column
  * kernel -- D pass, occupancy scale + clamp, DRC recurrence, depth, squared error -- instead of a smoothed grid, a

@@ -31,6 +31,12 @@ Ray-consistency terms (one pose candidate per image), further nodes on the same 
     grids with the colour loss above.  The reference defines that loss and its weight but never calls it from get_loss:
     this term is the one place where the step goes beyond get_loss.
     total += drc_weight * drc + drc_rgb_weight * drc_rgb.
+
+cfg.pc_fast == false (compute_projection's else-branch, dpc/models/model_pc.py:249-252): the exact Gaussian renderer
+dpc.render.pointcloud_project_exact with sigma = get_smooth_sigma(step) / vox_size as a launch argument, the min-of-K
+silhouette loss on its projection and the student term; no occupancy scale (the reference passes none on this path).  The
+depth, colour and ray-consistency losses are nodes on the fast path's grids and raise NotImplementedError naming pc_fast, and
+so do capture() / capture_compute(): a captured graph freezes launch arguments, sigma among them.
 """
 import numpy as np
 import torch
@@ -134,6 +140,13 @@ class TrainStep:
         rgb_weight = cfg.get("proj_rgb_weight", 0.0) if cfg.get("pc_rgb", False) else 0.0
         drc_weight = cfg.get("drc_weight", 0.0)
         drc_rgb_weight = cfg.get("drc_rgb_weight", 0.0) if cfg.get("pc_rgb", False) else 0.0
+        if not cfg.get("pc_fast", True):
+            for key, weight in (("proj_depth_weight", depth_weight), ("proj_rgb_weight", rgb_weight), ("drc_weight", drc_weight),
+                                ("drc_rgb_weight", drc_rgb_weight)):
+                if weight != 0:
+                    raise NotImplementedError("%s != 0 with pc_fast: false: the supervised losses are nodes on the fast "
+                                              "renderer's grids; the exact renderer returns the silhouette only" % key)
+            return self._loss_exact(self.predict(images), masks, self.global_step if global_step is None else global_step, valid_samples)
         for key, weight in (("drc_weight", drc_weight), ("drc_rgb_weight", drc_rgb_weight)):
             if weight != 0 and cfg.pose_predict_num_candidates != 1:
                 raise NotImplementedError("%s != 0 needs pose_predict_num_candidates == 1: with K candidates the reference's "
@@ -214,6 +227,30 @@ class TrainStep:
         out.update(projs=proj_out["proj"], min_loss=winner, proj_loss=proj_loss, pooled_masks=gt)
         return total, out
 
+    def _loss_exact(self, out, masks, step, valid_samples):
+        """The step of cfg.pc_fast == false (model_pc.py:233-252): every cloud its own copy of the points (tf_repeat_0,
+        then the point dropout), pointcloud_project(cfg, all_points, poses, sigma_rel / vox_size), the projection loss."""
+        cfg = self.cfg
+        K, V = cfg.pose_predict_num_candidates, cfg.step_size
+        all_points = out["points_1"].repeat_interleave(V * K, dim=0)
+        if cfg.pc_point_dropout != 1:
+            keep = R.get_dropout_prob(cfg, step)
+            if self.device_dropout:
+                all_points = device_point_dropout(all_points, keep)
+            else:
+                all_points, _ = R.pc_point_dropout(all_points, None, keep)
+        sigma = R.get_smooth_sigma(cfg, step) / cfg.vox_size
+        proj, _ = R.pointcloud_project_exact(cfg, all_points, out["poses"], sigma)
+        proj_loss, winner = R.silhouette_loss(proj, masks, K, valid_samples)
+        total = proj_loss.double()
+        if K > 1 and cfg.pose_predictor_student:
+            out["student_loss"] = student_loss(out["poses"], out["pose_student"], winner, K, cfg.pose_predictor_student_loss_weight,
+                                               valid_samples)
+            total = total + out["student_loss"]
+        total = total * cfg.proj_weight
+        out.update(projs=proj, min_loss=winner, proj_loss=proj_loss, pooled_masks=pooled_masks(masks, cfg.vox_size))
+        return total, out
+
     def __call__(self, images, masks, valid_samples=None, depths=None):
         """zero_grad, forward, loss, backward, Adam step (train_to.py:112-131).  Returns the loss tensor (no host sync).
         With `grad_sync` set (dpc.render.parallel.OverlappedGradAllReduce) the ranks' gradients are summed while the
@@ -258,6 +295,9 @@ class TrainStep:
             self._captured_schedule.update(kxy, kz, n_live)
 
     def _no_captured_depth_step(self):
+        if not self.cfg.get("pc_fast", True):
+            raise NotImplementedError("pc_fast: false: the exact renderer takes sigma as a launch argument, which a captured "
+                                      "graph would freeze; the step is eager only")
         if self.cfg.get("proj_depth_weight", 0.0) != 0:
             raise NotImplementedError("proj_depth_weight != 0: the depth-supervised step is eager only (no graph capture)")
         if self.cfg.get("pc_rgb", False) and self.cfg.get("proj_rgb_weight", 0.0) != 0:

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _native
-from ._ops import (DepthLoss, DepthMap, DeviceSchedule, Drc, DrcLoss, DrcRgbLoss, Geometry, ProjectFused, ProjectLossFused, ProjectLossStep, RgbLoss, RgbMap, RgbSplat, RgbSplatFixed,
+from ._ops import (DepthLoss, DepthMap, DeviceSchedule, Drc, DrcLoss, DrcRgbLoss, GaussVoxels, Geometry, ProjectFused, ProjectLossFused, ProjectLossStep, RgbLoss, RgbMap, RgbSplat, RgbSplatFixed,
                    SilhouetteLoss, Smooth, Splat, Transform, status_word, taps_bucket)
 from ._ops import _plane as _ops_plane
 from ._ops import colour_sets as _ops_colour_sets
@@ -34,6 +34,7 @@ from .meshviews import (ShadedScene, camera_extrinsic, features_of_views, load_o
 
 __all__ = [
     "pointcloud_project_fast", "pointcloud_project", "pc_perspective_transform", "pointcloud2voxels3d_fast",
+    "pointcloud2voxels", "pointcloud_project_exact",
     "smoothen_voxels3d", "smooth_voxels3d", "smoothing_kernel", "gauss_kernel_1d", "separable_kernels",
     "drc_projection", "drc_event_probabilities", "drc_depth_projection", "drc_depth_grid", "pc_point_dropout",
     "quaternion_rotate", "quaternion_multiply", "quaternion_conjugate", "quaternion_normalise",
@@ -504,6 +505,70 @@ def pointcloud_project_fast(cfg, point_cloud, transform, predicted_translation, 
 
 
 pointcloud_project = pointcloud_project_fast
+
+
+# ------------------------------------------------------------------------------------------------------
+# The exact Gaussian occupancy (cfg.pc_fast == false)   reference: dpc/util/point_cloud.py:17-57, 219-226 (TF-1 original)
+# ------------------------------------------------------------------------------------------------------
+def _gauss_normalise(cfg):
+    """point_cloud.py:43-51: pc_normalise_gauss wins, then pc_normalise_gauss_analytical (the default), then neither."""
+    if _get(cfg, "pc_normalise_gauss", False):
+        return _native.DPC_GAUSS_NORM_PER_POINT
+    if _get(cfg, "pc_normalise_gauss_analytical", True):
+        return _native.DPC_GAUSS_NORM_ANALYTICAL
+    return _native.DPC_GAUSS_NORM_NONE
+
+
+def _gauss_sigma(sigma):
+    """sigma is a launch argument of this path: a number, or a one-element tensor on the host."""
+    if isinstance(sigma, torch.Tensor):
+        if sigma.is_cuda:
+            raise ValueError("sigma must be a number or a host tensor: the exact renderer takes it as a launch argument")
+        sigma = sigma.item()
+    sigma = float(sigma)
+    if not (sigma > 0.0) or sigma == float("inf"):
+        raise ValueError("sigma must be positive and finite, got %r" % sigma)
+    return sigma
+
+
+def _gauss_grid(cfg):
+    if int(_get(cfg, "vox_size_z", -1)) != -1:
+        raise NotImplementedError("vox_size_z: pointcloud2voxels reads vox_size only (point_cloud.py:23-26), a grid with "
+                                  "its own depth cannot broadcast in the reference")
+    return int(cfg.vox_size)
+
+
+def _gauss_voxels(cfg, tr, sigma):
+    """[B,D,H,W] with axes following components 0, 1, 2 of tr: the kernels' layout."""
+    return GaussVoxels.apply(tr, _gauss_grid(cfg), _gauss_sigma(sigma), _gauss_normalise(cfg))
+
+
+def pointcloud2voxels(cfg, input_pc, sigma):
+    """Every point an isotropic Gaussian evaluated at every voxel centre of the grid linspace(-1, 1, vox_size)^3, summed
+    over the points and clipped to [0,1] (dpc/util/point_cloud.py:17-57): [B,N,3] -> [B,G,G,G,1].
+
+    The grid axes follow (input_pc[...,1], input_pc[...,0], input_pc[...,2]), the effect of tf.meshgrid's default 'xy'
+    indexing; the kernels write axes following components 0, 1, 2, and this returns the transposed VIEW of that grid, not a
+    copy.  cfg.pc_normalise_gauss / pc_normalise_gauss_analytical pick the normalisation like there.  No outlier filter:
+    a point outside the cube adds its tail.  sigma: a number (absolute, the caller divides sigma_rel by vox_size)."""
+    return _gauss_voxels(cfg, input_pc, sigma).transpose(1, 2).unsqueeze(-1)
+
+
+def pointcloud_project_exact(cfg, point_cloud, transform, sigma):
+    """pointcloud_project of the TF-1 original (dpc/util/point_cloud.py:219-226), the renderer of cfg.pc_fast == false:
+    perspective transform, exact Gaussian occupancy, DRC silhouette.  Returns (proj [B,G,G,1], voxels [B,G,G,G,1]) like
+    there.  Against pointcloud_project_fast: the grid spans [-1,1]^3, there is no outlier filter, no occupancy scale, no
+    translation and no learned focal length (the reference passes none of them on this path), and sigma is a launch
+    argument, so the call cannot follow a sigma schedule inside a captured graph."""
+    _check_live_branches(cfg)
+    G = _gauss_grid(cfg)
+    geom = _geometry(cfg)
+    tr_pc = Transform.apply(point_cloud, transform, None, None, geom)            # :220
+    voxels = pointcloud2voxels(cfg, tr_pc, sigma)                                # :221
+    voxels = voxels.permute(0, 2, 1, 3, 4)                                       # :222, the kernels' own layout again
+    proj, _, _ = Drc.apply(voxels.squeeze(-1), Geometry(G, G, G, None, None, geom.camera_distance, geom.focal_length,
+                                                        geom.clip_val, geom.max_depth))   # :224
+    return torch.flip(proj, [1]).unsqueeze(-1), voxels                           # :225
 
 
 def pointcloud_project_loss(cfg, point_cloud, transform, predicted_translation, all_rgb, kernel=None,

@@ -29,6 +29,8 @@ DPC_STATUS_KEY_OVERFLOW = 4
 DPC_STATUS_NONFINITE = 8
 DPC_STATUS_DENSIFY_ORDER = 16
 DPC_STATUS_NEAR = 32
+DPC_GAUSS_NORM_NONE, DPC_GAUSS_NORM_ANALYTICAL, DPC_GAUSS_NORM_PER_POINT = 0, 1, 2
+DPC_GAUSS_MAX_SIDE = 64
 DPC_MESH_NEAR = 1e-3
 DPC_MESH_AMBIENT, DPC_MESH_DIFFUSE = 0.25, 0.75
 
@@ -67,6 +69,8 @@ _FUNCTIONS = (
     ("dpc_drc_fwd", _i, [_pp] + [_vp] * 5),
     ("dpc_drc_bwd", _i, [_pp] + [_vp] * 6),
     ("dpc_silhouette_loss", _i, [_vp, _i, _vp, _vp] + [_i] * 4 + [_vp, _vp, _vp, _vp]),
+    ("dpc_gauss_voxels_fwd", _i, [_pp, _vp, _d, _i, _vp, _vp, _vp]),
+    ("dpc_gauss_voxels_bwd", _i, [_pp, _vp, _d, _i, _vp, _vp, _vp, _vp]),
     ("dpc_depth_workspace_bytes", _sz, [_pp]),
     ("dpc_depth_loss_fwd", _i, [_pp] + [_vp] * 4 + [_i, ctypes.c_float] + [_vp] * 5),
     ("dpc_depth_loss_bwd", _i, [_pp] + [_vp] * 4 + [_i, ctypes.c_float] + [_vp] * 7),

@@ -764,6 +764,43 @@ class Drc(torch.autograd.Function):
         return _like_input(dvox, ctx.vox), None
 
 
+class GaussVoxels(torch.autograd.Function):
+    """pointcloud2voxels of the TF-1 original (dpc/util/point_cloud.py:17-57), the exact Gaussian occupancy: tr [B,N,3]
+    (z,y,x) -> voxels [B,G,G,G] with axes following components 0, 1, 2.  sigma is a launch argument (a Python float);
+    normalise one of N.DPC_GAUSS_NORM_*.  The sums before the clip are kept for the backward's pass-through set."""
+
+    @staticmethod
+    def forward(ctx, tr, G, sigma, normalise):
+        dev = N.require_device(tr)
+        tr32 = _f32(tr)
+        if tr32.dim() != 3 or tr32.shape[2] != 3:
+            raise ValueError("transformed points must be [B,N,3], got %s" % (tuple(tr.shape),))
+        B, Npts = tr32.shape[0], tr32.shape[1]
+        geom = Geometry(G, G, G)
+        P = geom.params(B, Npts)
+        vox = torch.empty((B, G, G, G), dtype=torch.float32, device=dev)
+        raw = torch.empty_like(vox) if ctx.needs_input_grad[0] else None
+        with _on(dev):
+            rc = N.lib().dpc_gauss_voxels_fwd(ctypes.byref(P), _dp(tr32), float(sigma), int(normalise), _dp(raw), _dp(vox),
+                                              _stream(dev))
+        N.check(rc, "dpc_gauss_voxels_fwd")
+        ctx.geom, ctx.tr, ctx.tr32, ctx.raw, ctx.sigma, ctx.normalise = geom, _meta(tr), tr32, raw, float(sigma), int(normalise)
+        return vox
+
+    @staticmethod
+    def backward(ctx, dvox):
+        tr32 = ctx.tr32
+        dev = tr32.device
+        P = ctx.geom.params(tr32.shape[0], tr32.shape[1])
+        dvox32 = dvox.detach().to(torch.float32).contiguous()
+        dtr = torch.empty(tr32.shape, dtype=torch.float32, device=dev)
+        with _on(dev):
+            rc = N.lib().dpc_gauss_voxels_bwd(ctypes.byref(P), _dp(tr32), ctx.sigma, ctx.normalise, _dp(ctx.raw), _dp(dvox32),
+                                              _dp(dtr), _stream(dev))
+        N.check(rc, "dpc_gauss_voxels_bwd")
+        return _like_input(dtr, ctx.tr), None, None, None
+
+
 class SilhouetteLoss(torch.autograd.Function):
     """add_proj_loss / proj_loss_pose_candidates fused with its gradient (one launch, gradient precomputed in
     the forward; backward scales it by the incoming scalar).  gt: pooled masks (as many values per sample as pred has per
