@@ -540,6 +540,10 @@ def _gauss_grid(cfg):
 
 def _gauss_voxels(cfg, tr, sigma):
     """[B,D,H,W] with axes following components 0, 1, 2 of tr: the kernels' layout."""
+    if not torch.is_grad_enabled():
+        # ctx.needs_input_grad follows requires_grad alone, also where no graph is recorded: detached, the node neither
+        # allocates nor writes the sums before the clip, which only a backward reads
+        tr = tr.detach()
     return GaussVoxels.apply(tr, _gauss_grid(cfg), _gauss_sigma(sigma), _gauss_normalise(cfg))
 
 

@@ -79,18 +79,27 @@ def scale(G, sigma, mode):
     return 1.0 / (MAGIC * (sigma * G) ** 3) if mode == ANALYTICAL else 1.0
 
 
-def tables(tr, G, sigma, mode):
+def tables(tr, G, sigma, mode, shifted=True):
     """(P [3][B,N,G], dP [3][B,N,G]): the 1-D tables and their derivatives to the coordinate.  P_a = e_a (divided by its sum
-    over the grid under PER_POINT); dP_a = P_a (w - wbar), w = -(t - c_i) / sigma^2, wbar = sum_i P_a w (PER_POINT) or 0."""
+    over the grid under PER_POINT); dP_a = P_a (w - wbar), w = -(t - c_i) / sigma^2, wbar = sum_i P_a w (PER_POINT) or 0.
+
+    Under PER_POINT the exponent is taken minus its largest value over the grid, per point and axis: the quotient e / sum e
+    is the same number, and a point whose Gaussians all underflow (exp's argument below about -745: a point well outside
+    the grid under a narrow sigma) keeps its table instead of 0 / 0.  shifted=False is the quotient as the reference writes
+    it, kept for tests/test_gauss_voxels_host.py to compare the two where the plain one is finite."""
     tr = np.asarray(tr, dtype=np.float64)
     c = np.linspace(-1.0, 1.0, G)
     P, dP = [], []
     for a in range(3):
         d = tr[:, :, a, None] - c
-        e = np.exp(-d * d / (2.0 * sigma * sigma))
+        arg = -d * d / (2.0 * sigma * sigma)
+        if mode == PER_POINT and shifted:
+            arg = arg - arg.max(-1, keepdims=True)
+        e = np.exp(arg)
         w = -d / (sigma * sigma)
         if mode == PER_POINT:
-            e = e / e.sum(-1, keepdims=True)
+            with np.errstate(invalid="ignore"):      # shifted=False: 0 / 0 where every Gaussian of a point underflows
+                e = e / e.sum(-1, keepdims=True)
             w = w - (e * w).sum(-1, keepdims=True)
         P.append(e)
         dP.append(e * w)
@@ -123,6 +132,37 @@ def clip_margin(raw):
     return (float(raw.min()), float(np.abs(raw - 1.0).min())) if raw.size else (0.0, 1.0)
 
 
+def raw_fp32_chain(tr, G, sigma, mode):
+    """What an honest fp32 implementation gives for raw, [B,D,H,W] fp32: the tables' arguments formed in fp64 and rounded
+    once, exp, the normalisation and the products in fp32, and the sum over the points as one fp32 chain in index order
+    (what np.cumsum(..., dtype=float32) over the points gives).  Not a model of the kernels (theirs is a chain of fused multiply-adds): it says how
+    much of the parity bound fp32 itself uses up at a shape, so that a case is asserted only where a correct kernel has room."""
+    tr = np.asarray(tr, dtype=np.float64)
+    c = np.linspace(-1.0, 1.0, G)
+    P = []
+    for a in range(3):
+        d = tr[:, :, a, None] - c
+        arg = -d * d / (2.0 * sigma * sigma)
+        if mode == PER_POINT:
+            arg = arg - arg.max(-1, keepdims=True)
+        e = np.exp(arg.astype(np.float32))
+        if mode == PER_POINT:
+            e = e / e.sum(-1, keepdims=True, dtype=np.float32)
+        P.append(e)
+    B, N = tr.shape[:2]
+    out = np.zeros((B, G, G, G), dtype=np.float32)
+    for b in range(B):
+        for n in range(N):    # one fp32 addition per point and voxel, in index order
+            out[b] += (P[0][b, n, :, None] * P[1][b, n])[:, :, None] * P[2][b, n]
+    return np.float32(scale(G, sigma, mode)) * out
+
+
+def fraction_of_bound(dev, ref, tol=1e-5):
+    """max|dev - ref| as a fraction of the parity bound tol * max(1, max|ref|)."""
+    dev, ref = np.asarray(dev, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    return float(np.abs(dev - ref).max()) / (tol * max(1.0, float(np.abs(ref).max()))) if ref.size else 0.0
+
+
 # ------------------------------------------------------------------------------------------------------
 # pointcloud_project (point_cloud.py:219-226) on the project's torch fp64 oracle of the transform and the DRC
 # ------------------------------------------------------------------------------------------------------
@@ -139,12 +179,16 @@ def pointcloud_project(cfg, point_cloud, transform, sigma):
     return proj, voxels, raw
 
 
-def points(rng, B, N):
-    """Test clouds [B,N,3] fp32: most points inside the cube [-1/2,1/2]^3, and, when there is room, some exactly on its
-    faces, some between the cube and the grid's edge, and some beyond +-1 (no outlier filter on this path)."""
+SPECIAL = np.array([[0.5, -0.5, 0.25], [-0.5, 0.5, 0.5], [0.7, -0.1, -0.8], [-0.93, 0.62, 0.1],
+                    [1.25, 0.0, -0.2], [0.1, -1.4, 0.3], [0.2, 0.3, 1.05]])
+OUTSIDE = (4, 5, 6)     # the rows of SPECIAL beyond +-1
+
+
+def points(rng, B, N, special=True):
+    """Test clouds [B,N,3] fp32: most points inside the cube [-1/2,1/2]^3, and, when there is room (and unless special is
+    false), some exactly on its faces, some between the cube and the grid's edge, and some beyond +-1 (no outlier filter on
+    this path)."""
     tr = np.tanh(0.6 * rng.standard_normal((B, N, 3))) / 2
-    special = np.array([[0.5, -0.5, 0.25], [-0.5, 0.5, 0.5], [0.7, -0.1, -0.8], [-0.93, 0.62, 0.1],
-                        [1.25, 0.0, -0.2], [0.1, -1.4, 0.3], [0.2, 0.3, 1.05]])
-    if N >= 2 * len(special):
-        tr[:, :len(special)] = special
+    if special and N >= 2 * len(SPECIAL):
+        tr[:, :len(SPECIAL)] = SPECIAL
     return tr.astype(np.float32)

@@ -82,6 +82,84 @@ def test_oracle_reproduces_the_fixture(golden):
     assert np.abs(got - t.grad.numpy()).max() <= 1e-12 * np.abs(got).max()
 
 
+def _table_clouds(golden):
+    """(tr, G, sigma) of the fixture and of the GPU file's underflow and width cases."""
+    import test_gauss_voxels_gpu as TG
+
+    g = golden("f23_gauss_voxels.npz")
+    yield g["tr_pc"], int(g["voxels"].shape[1]), float(g["sigma"])
+    for tag in TG.ids(TG.UNDERFLOW) + ["w1_pp", "w2_pp", "w3_pp", "w16", "w33", "t40_n2", "t24_n128", "g24_n257", "g40"]:
+        _, _, G, sigma, _, tr, _ = TG.case_inputs(tag)
+        yield tr, G, sigma
+
+
+def test_shifted_tables_equal_the_plain_quotient_where_that_is_finite(golden):
+    """Element by element to 1e-12 relative, wherever the plain form is finite and well defined: its numerator exp(arg)
+    must be a normal fp64 number with digits to spare (above 1e-290); below that the plain quotient has lost digits, or is
+    0 where the shifted one is not, through no fault of the shift.  dP = P (w - wbar) is a difference that cancels where a
+    point's table sits on one voxel, so its scale is P max|w|, not |dP|."""
+    rows = nans = 0
+    for tr, G, sigma in _table_clouds(golden):
+        Ps, dPs = GO.tables(tr, G, sigma, GO.PER_POINT)
+        Pp, dPp = GO.tables(tr, G, sigma, GO.PER_POINT, shifted=False)
+        for a in range(3):
+            assert np.isfinite(Ps[a]).all() and np.isfinite(dPs[a]).all()
+            assert np.abs(Ps[a].sum(-1) - 1.0).max() <= 1e-14
+            d = np.asarray(tr, dtype=np.float64)[:, :, a, None] - np.linspace(-1.0, 1.0, G)
+            normal = np.exp(-d * d / (2.0 * sigma * sigma)) > 1e-290
+            wmax = np.abs(d / (sigma * sigma)).max(-1, keepdims=True)
+            ok = np.isfinite(Pp[a]).all(-1) & np.isfinite(dPp[a]).all(-1)        # [B,N]: the plain row is finite
+            rows, nans = rows + int(ok.sum()), nans + int((~ok).sum())
+            use = ok[..., None] & normal
+            assert use.sum() > 0.2 * use.size
+            assert (np.abs(Ps[a] - Pp[a])[use] <= 1e-12 * Pp[a][use]).all()
+            assert (np.abs(dPs[a] - dPp[a])[use] <= 1e-12 * (Pp[a] * wmax)[use]).all()
+    assert rows > 1000 and nans > 0, "the clouds should hold both kinds of rows"
+    for mode in (GO.NONE, GO.ANALYTICAL):                                         # no quotient: nothing is shifted
+        for s, p in zip(GO.tables(tr, G, sigma, mode), GO.tables(tr, G, sigma, mode, shifted=False)):
+            assert all(np.array_equal(x, y) for x, y in zip(s, p))
+
+
+def test_oracle_is_finite_where_every_gaussian_of_a_point_underflows():
+    import test_gauss_voxels_gpu as TG
+
+    B, N, G, sigma, mode, tr, dvox = TG.case_inputs("u64")
+    assert (G, mode) == (64, GO.PER_POINT) and abs(sigma * G - 0.5) < 1e-15
+    assert np.array_equal(tr[0, :len(GO.SPECIAL)], GO.SPECIAL.astype(np.float32))
+    with np.errstate(invalid="ignore"):
+        plain = np.einsum("bnz,bny,bnx->bzyx", *GO.tables(tr, G, sigma, mode, shifted=False)[0], optimize=True)
+    assert np.isnan(plain).any(), "the case should be one the plain quotient cannot compute"
+    raw = GO.raw_separable(tr, G, sigma, mode)
+    dtr = GO.grad_separable(tr, G, sigma, mode, dvox, raw)
+    assert np.isfinite(raw).all() and np.isfinite(dtr).all()
+    assert abs(raw.sum() - B * N) <= 1e-12 * B * N                                # every point's whole mass is on the grid
+    assert (np.abs(dtr[0, list(GO.OUTSIDE)]).max(-1) > 0.1).all()                  # the outside points have a gradient
+    # where the literal form is finite it still is the separable one (G = 17: exp's argument stays above -745)
+    B, N, G, sigma, mode, tr, _ = TG.case_inputs("u17")
+    lit, _ = GO.pointcloud2voxels_literal(tr, G, sigma, mode)
+    sep = GO.raw_separable(tr, G, sigma, mode)
+    assert np.isfinite(lit).all() and np.abs(lit[..., 0] - sep.transpose(0, 2, 1, 3)).max() <= 1e-13 * sep.max()
+
+
+def test_fp32_chain_leaves_room_at_the_asserted_workload_shapes_only():
+    """How much of the parity bound an honest fp32 sum in index order uses up by itself at the workload's point count.  The
+    GPU file asserts raw only where that is at most a third (LARGE) and reports where it is more (REPORTED)."""
+    import test_gauss_voxels_gpu as TG
+
+    # a chain of few terms is the fp64 sum to fp32's precision
+    B, N, G, sigma, mode, tr, _ = TG.case_inputs("g17")
+    assert GO.fraction_of_bound(GO.raw_fp32_chain(tr, G, sigma, mode), GO.raw_separable(tr, G, sigma, mode)) < 0.05
+    got = {}
+    for tag in TG.ids(TG.LARGE + TG.REPORTED + TG.CHAIN_ONLY + TG.CLIP):
+        B, N, G, sigma, mode, tr, _ = TG.case_inputs(tag)
+        got[tag] = GO.fraction_of_bound(GO.raw_fp32_chain(tr, G, sigma, mode), GO.raw_separable(tr, G, sigma, mode))
+        print("%s: an fp32 chain in index order is at %.3f of the bound" % (tag, got[tag]))
+    for tag in TG.ids(TG.LARGE + TG.CLIP):
+        assert got[tag] <= 1.0 / 3.0, (tag, got[tag])
+    assert 0.05 < got["big32"] < 0.2 and 0.02 < got["big40"] < 0.1                # G = 32, N = 8000 and G = 40, N = 2100, sigma_rel 1
+    assert 0.6 < got["big32_wide"] < 0.9 and 0.6 < got["big32_wide_none"] < 0.9   # G = 32, N = 8000, sigma_rel 3
+
+
 def test_normalise_mode_follows_the_reference_precedence():
     from oracle import dpc_oracle as O
 
