@@ -42,6 +42,9 @@ extern "C" {
  * B <= 65535, and N <= DPC_MAX_POINTS points per cloud: a voxel's splat weights are summed in 64-bit fixed point with 44
  * fractional bits, so 2^20 - 1 points of weight 1 in ONE voxel is the most that cannot wrap. */
 #define DPC_MAX_POINTS 1048575
+/* Most points per cloud of a dpc_emd_fwd pair: the auction keeps a pair in the 160 KiB of LDS of one CU at 76 bytes per
+ * point (both clouds in fp64, prices, bids, owners), 152 KiB at this size. */
+#define DPC_EMD_MAX_POINTS 2048
 
 enum {
   DPC_OK = 0,
@@ -68,7 +71,9 @@ enum {
                                    * infinite vertex or projection (it was skipped)                                    */
   DPC_STATUS_DENSIFY_ORDER = 16,  /* dpc_densify: a new edge longer than kDnBand x the round's longest edge: the
                                    * round-ordering argument failed and the output may differ from the reference's      */
-  DPC_STATUS_NEAR = 32            /* dpc_render_meshes: a face has a vertex at depth d <= DPC_MESH_NEAR (it was skipped)   */
+  DPC_STATUS_NEAR = 32,           /* dpc_render_meshes: a face has a vertex at depth d <= DPC_MESH_NEAR (it was skipped)   */
+  DPC_STATUS_EMD_NOT_CONVERGED = 64 /* dpc_emd_fwd: a pair was still unmatched after max_rounds bidding rounds (its emd
+                                   * is NaN); DPC_STATUS_BAD_INDEX there: the device table differs from the host's    */
 };
 
 /* Geometry and camera constants of one call (dpc/resources/default_config.yaml:77-89 and the cfg fields
@@ -634,6 +639,63 @@ int dpc_nearest_batched_bwd(const void* pts, int n_pts, int is_f64, const int32_
                             int squared, void* dpts, void* workspace, void* stream);
 int dpc_chamfer_pair_means(const void* values, int is_f64, const int32_t* pair_desc, const int32_t* host_pair_desc, int pairs,
                            double* mean, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Batched Earth Mover's Distance: the cost of a one-to-one matching pi between two clouds of n points each, for P pairs
+ * in one call, with the matching and a closed-form gradient.  The reference has no EMD; the exact optimum is what
+ * scipy.optimize.linear_sum_assignment finds for the same cost matrix, one pair at a time on the host.
+ *
+ * pred [n_pred,3] and gt [n_gt,3] are packed buffers, fp32, or both fp64 when is_f64; pair p is (pred_start, pred_count,
+ * gt_start, gt_count) = pair_desc[p] (DEVICE) = host_pair_desc[p] (HOST, the same values).  The two counts of a pair are
+ * equal, n_p in [1, DPC_EMD_MAX_POINTS], and the pairs' ranges ascend without overlap in each buffer: every output is
+ * indexed like its input.  All arithmetic is fp64 (fp32 input is widened exactly first), no operation is fused:
+ *   d2   = (px-gx)*(px-gx) + (py-gy)*(py-gy) + (pz-gz)*(pz-gz)      the additions left to right
+ *   c_ij = d2 (squared != 0) or sqrt(d2)                              the same expression in the bidding and the sum
+ * The matching is a forward auction (Bertsekas) with eps-scaling, Jacobi rounds, and THE SCHEDULE IS THE CONTRACT:
+ *   span  = max c - min c over the pair;  eps_0 = max(span / 2, eps),  eps_k = max(eps_{k-1} / 5, eps); the phase that
+ *           runs with exactly eps is the last.  Prices start at 0 and carry over from phase to phase; every phase starts
+ *           with nobody assigned.
+ *   round   one snapshot of prices and owners; every unassigned i computes v_ij = -c_ij - price_j, j* = argmax_j v_ij
+ *           (ties: the lowest j), v that maximum, w = the maximum over j != j* (v itself when n = 1), and bids
+ *           b_i = price_j* + (v - w) + eps_k, the additions left to right.  Every object with bids goes to its highest bid
+ *           (ties: the lowest i), its price becomes that bid, and its previous owner becomes unassigned.
+ *   a phase ends when nobody is unassigned.  After max_rounds rounds in total a pair that still has rounds to run stops
+ *           as not converged.
+ * Outputs, for a pair that converged:
+ *   emd[p]       (sum_i c_{i,pi(i)}) / n_p, float64: 64 partial sums (terms l, l + 64, ... added in ascending order onto
+ *                0.0), then a butterfly over them at distances 32, 16, ... 1; then one IEEE divide.
+ *                sum_i c_{i,pi(i)} <= optimum + n_p * eps, so emd exceeds the optimal mean by at most eps (cost units);
+ *   assignment   [n_pred] int32: pi(i), an index into the pair's gt points, at row pred_start + i;
+ *   inverse      [n_gt] int32: the i with pi(i) = j, at row gt_start + j;
+ *   rounds[p]    the bidding rounds it ran, int32.
+ * A pair that did not converge has emd NaN, rounds = max_rounds, its unassigned entries -1 (the others are the state
+ * it stopped in), and DPC_STATUS_EMD_NOT_CONVERGED is OR-ed into *status (DEVICE int32, zeroed by the caller; NULL
+ * allowed).  A NaN coordinate ends there too.  The other pairs of the call are unaffected: a pair's results depend on
+ * its own points, eps and max_rounds only, are bit-identical from run to run and do not depend on how pairs are
+ * batched (integer LDS max / min resolve the bids; no floating-point atomics).  One workgroup per pair, every loop is
+ * bounded by max_rounds, nothing waits on another workgroup.  No host synchronisation and no host -> device copy.
+ * DPC_ERR_SHAPE, before any launch, for pairs < 0, n_pred < 0, n_gt < 0, eps <= 0 or not finite, max_rounds < 1, a
+ * negative start or count, a range outside its buffer, pred_count != gt_count, a count of 0 or above
+ * DPC_EMD_MAX_POINTS, or ranges that do not ascend.  With valid arguments and NULL device pointers the call returns
+ * DPC_ERR_NULL without touching a device.  dpc_emd_lds_bytes(n): the LDS a pair of n points takes (0 for n outside
+ * [1, DPC_EMD_MAX_POINTS]); there is no workspace, a pair's whole state is in LDS.
+ *
+ * dpc_emd_bwd: the gradient of sum_p gemd[p] * emd[p] (gemd [P] float64; NULL: zeros) given the forward's emd,
+ * assignment and inverse for the same points and table.  With a = pred point i, b = gt point pi(i), w = gemd[p] / n_p,
+ * in fp64 and unfused:  squared: c = (2 w) * (a - b);  otherwise c = ((a - b) / d) * w with d = sqrt(d2), and c is
+ * exactly zero when d == 0 (coincident points, the rule of dpc_nearest_batched_bwd).  dpred row i = c and dgt row pi(i)
+ * = -c, each rounded once to the compute type: both are gathers through the bijection, one thread per point, no atomics.
+ * A pair whose emd is NaN gets zero rows.  dpred [n_pred,3] | NULL, dgt [n_gt,3] | NULL: rows inside a pair's range are
+ * written, the others are left alone.  The same refusals as the forward.
+ * Added without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_emd_lds_bytes(int n);
+int dpc_emd_fwd(const void* pred, int n_pred, const void* gt, int n_gt, int is_f64, const int32_t* pair_desc,
+                const int32_t* host_pair_desc, int pairs, int squared, double eps, int max_rounds, double* emd,
+                int32_t* assignment, int32_t* inverse, int32_t* rounds, int32_t* status, void* stream);
+int dpc_emd_bwd(const void* pred, int n_pred, const void* gt, int n_gt, int is_f64, const int32_t* pair_desc,
+                const int32_t* host_pair_desc, int pairs, int squared, const double* emd, const int32_t* assignment,
+                const int32_t* inverse, const double* gemd, void* dpred, void* dgt, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Voxel-grid downsampling of ground-truth clouds (densify/downsample_gt.py:47-57: open3d.voxel_down_sample(pcd,

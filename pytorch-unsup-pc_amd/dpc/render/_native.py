@@ -29,6 +29,8 @@ DPC_STATUS_KEY_OVERFLOW = 4
 DPC_STATUS_NONFINITE = 8
 DPC_STATUS_DENSIFY_ORDER = 16
 DPC_STATUS_NEAR = 32
+DPC_STATUS_EMD_NOT_CONVERGED = 64
+DPC_EMD_MAX_POINTS = 2048
 DPC_GAUSS_NORM_NONE, DPC_GAUSS_NORM_ANALYTICAL, DPC_GAUSS_NORM_PER_POINT = 0, 1, 2
 DPC_GAUSS_MAX_SIDE = 64
 DPC_MESH_NEAR = 1e-3
@@ -100,6 +102,9 @@ _FUNCTIONS = (
     ("dpc_chamfer_bwd_workspace_bytes", _sz, [_i, _vp, _i]),
     ("dpc_nearest_batched_bwd", _i, [_vp, _i, _i, _vp, _vp, _i] + [_vp] * 4 + [_i] + [_vp] * 3),
     ("dpc_chamfer_pair_means", _i, [_vp, _i, _vp, _vp, _i] + [_vp] * 3),
+    ("dpc_emd_lds_bytes", _sz, [_i]),
+    ("dpc_emd_fwd", _i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _d, _i] + [_vp] * 6),
+    ("dpc_emd_bwd", _i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _i] + [_vp] * 7),
     ("dpc_downsample_workspace_bytes", _sz, [_i, _i]),
     ("dpc_voxel_downsample", _i, [_vp, _i, _i, _vp, _vp, _i, _d] + [_vp] * 6),
     ("dpc_densify_workspace_bytes", _sz, [_i, _i64, _i64, _i64, _i]),
