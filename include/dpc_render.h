@@ -45,6 +45,8 @@ extern "C" {
 /* Most points per cloud of a dpc_emd_fwd pair: the auction keeps a pair in the 160 KiB of LDS of one CU at 76 bytes per
  * point (both clouds in fp64, prices, bids, owners), 152 KiB at this size. */
 #define DPC_EMD_MAX_POINTS 2048
+/* Most points per cloud of dpc_fps: a cloud is held on chip by one workgroup of 1024 threads, 16 points per thread. */
+#define DPC_FPS_MAX_POINTS 16384
 
 enum {
   DPC_OK = 0,
@@ -68,12 +70,14 @@ enum {
                                    * dpc_densify: a non-finite vertex, edge length or midpoint (that model stops);
                                    * dpc_render_points: a non-finite coordinate, colour or radius, or a radius <= 0, in
                                    * a cloud (that image stays background); dpc_render_meshes: a face with a NaN or
-                                   * infinite vertex or projection (it was skipped)                                    */
+                                   * infinite vertex or projection (it was skipped); dpc_fps: a NaN or infinite
+                                   * coordinate in a cloud (its indices are -1, its radius2 NaN)                       */
   DPC_STATUS_DENSIFY_ORDER = 16,  /* dpc_densify: a new edge longer than kDnBand x the round's longest edge: the
                                    * round-ordering argument failed and the output may differ from the reference's      */
   DPC_STATUS_NEAR = 32,           /* dpc_render_meshes: a face has a vertex at depth d <= DPC_MESH_NEAR (it was skipped)   */
   DPC_STATUS_EMD_NOT_CONVERGED = 64 /* dpc_emd_fwd: a pair was still unmatched after max_rounds bidding rounds (its emd
-                                   * is NaN); DPC_STATUS_BAD_INDEX there: the device table differs from the host's    */
+                                   * is NaN); DPC_STATUS_BAD_INDEX there and in dpc_fps: the device table differs
+                                   * from the host's                                                                   */
 };
 
 /* Geometry and camera constants of one call (dpc/resources/default_config.yaml:77-89 and the cfg fields
@@ -696,6 +700,48 @@ int dpc_emd_fwd(const void* pred, int n_pred, const void* gt, int n_gt, int is_f
 int dpc_emd_bwd(const void* pred, int n_pred, const void* gt, int n_gt, int is_f64, const int32_t* pair_desc,
                 const int32_t* host_pair_desc, int pairs, int squared, const double* emd, const int32_t* assignment,
                 const int32_t* inverse, const double* gemd, void* dpred, void* dgt, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Batched farthest-point sampling (FPS): for each of C clouds, `samples` of its points, each the point farthest from
+ * everything taken before it.  It brings clouds of unequal size to the common size dpc_emd_fwd needs (the predictions
+ * have 8000 points, the ground-truth clouds up to 12647) deterministically and with even coverage.  The reference has
+ * no subsampling rule of its own.
+ *
+ * pts [n_pts,3] is one packed buffer, fp32, or fp64 when is_f64; cloud c is the row (start, count, first, out_start,
+ * samples) = cloud_desc[c] (DEVICE, 5 int32) = host_cloud_desc[c] (HOST, the same values): its points are rows
+ * [start, start + count) of pts, its outputs rows [out_start, out_start + samples) of indices and radius2.  Input ranges
+ * may share or skip rows; output ranges ascend without overlap; 1 <= samples <= count <= DPC_FPS_MAX_POINTS and
+ * 0 <= first < count.  All arithmetic is fp64 (fp32 input is widened exactly first), no operation is fused.  For the
+ * cloud's points p[0..count):
+ *   d2(i,j) = (xi-xj)*(xi-xj) + (yi-yj)*(yi-yj) + (zi-zj)*(zi-zj)      the additions left to right
+ *   state:    dist[i] = +inf for all i, nothing taken, cur = first
+ *   round k = 0 .. samples-1:
+ *     indices[out_start + k] = cur                     int32, an index into the cloud's own points
+ *     radius2[out_start + k] = dist[cur]               float64, as it stands BEFORE this round's update: +inf for k = 0,
+ *                                                      otherwise the squared distance from the pick to the nearest
+ *                                                      earlier pick
+ *     cur is taken
+ *     for every i not taken: dist[i] = min(dist[i], d2(i, cur))
+ *     cur = the i not taken with the largest dist[i]; TIES GO TO THE LOWEST i
+ * So the indices of a cloud are distinct, radius2 is non-increasing from k = 1 on, a cloud of coincident points yields
+ * first and then the remaining indices in ascending order, and an fp32 cloud yields the indices of the same values
+ * stored as fp64.  The arg-max is a maximum over the key (dist, lowest index), dist compared through its bit pattern
+ * (non-negative doubles order like integers), merged by compare-and-select across lanes, waves and LDS: no atomics, so
+ * results are bit-identical from run to run and do not depend on which clouds share a call.
+ * A cloud with a NaN or infinite coordinate has indices -1 and radius2 NaN, and DPC_STATUS_NONFINITE is OR-ed into
+ * *status (DEVICE int32, zeroed by the caller; NULL allowed); the other clouds are unaffected.  No entry of the device
+ * table becomes an address or a loop bound before it is checked against n_pts, the limits above and the end of the host
+ * table's last output range; a device row that fails, or whose size class the host table did not announce, sets
+ * DPC_STATUS_BAD_INDEX and is not run (its outputs are left as they were).
+ * One workgroup per cloud, every loop is bounded by samples, nothing waits on another workgroup.  No host
+ * synchronisation and no host -> device copy: the call can be captured into a hipGraph.  There is no workspace.
+ * DPC_ERR_SHAPE, before any launch, for clouds < 0, n_pts < 0, a negative start, a range outside [0, n_pts), a count of
+ * 0 or above DPC_FPS_MAX_POINTS, samples outside [1, count], first outside [0, count), a negative out_start, or output
+ * ranges that do not ascend (or end beyond 2^31 - 1).  With valid arguments and NULL device pointers the call returns
+ * DPC_ERR_NULL without touching a device.  Added without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+int dpc_fps(const void* pts, int n_pts, int is_f64, const int32_t* cloud_desc, const int32_t* host_cloud_desc, int clouds,
+            int32_t* indices, double* radius2, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Voxel-grid downsampling of ground-truth clouds (densify/downsample_gt.py:47-57: open3d.voxel_down_sample(pcd,

@@ -26,6 +26,7 @@ from .alignment import (alignment_candidates, alignment_to_ground_truth, as_rota
                         icp_point_to_point, pose_errors, quat_w_avg_markley, quaternion_from_campos, reference_rotation)
 from .chamfer import chamfer_batched, chamfer_loss, chamfer_of_split, eval_chamfer, nearest_batched  # noqa: F401
 from .emd import emd_loss, emd_match, emd_of_split  # noqa: F401
+from .sampling import farthest_point_sample  # noqa: F401
 from .downsample import downsample_split, voxel_down_sample  # noqa: F401
 from .densify import MeshError, densify_meshes, densify_split, load_obj_mesh  # noqa: F401
 from .visualise import (camera_frame, read_png_any, render_point_cloud, render_point_clouds, render_split, write_png,  # noqa: F401
@@ -46,7 +47,7 @@ __all__ = [
     "icp_point_to_point", "alignment_to_ground_truth", "alignment_candidates", "reference_rotation", "quat_w_avg_markley",
     "quaternion_from_campos", "as_rotation_matrix", "from_rotation_matrix", "pose_errors",
     "nearest_batched", "chamfer_batched", "chamfer_loss", "chamfer_of_split", "eval_chamfer", "voxel_down_sample", "downsample_split",
-    "emd_loss", "emd_match", "emd_of_split",
+    "emd_loss", "emd_match", "emd_of_split", "farthest_point_sample",
     "load_obj_mesh", "densify_meshes", "densify_split", "MeshError",
     "camera_frame", "render_point_clouds", "render_point_cloud", "render_split", "write_png",
     "write_png_rgba", "write_png_gray16", "read_png_any",

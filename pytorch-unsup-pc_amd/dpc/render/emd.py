@@ -9,7 +9,8 @@ optimum, bit-reproducible, and differentiable.
 
     emd_match     the metric with everything the matching produced: (emd [P], assignments, inverses, rounds [P])
     emd_loss      emd [P] as a differentiable loss (dpc_emd_bwd), optionally with the assignments
-    emd_of_split  the [M,V] table of a split, next to chamfer_of_split
+    emd_of_split  the [M,V] table of a split, next to chamfer_of_split; clouds are brought to a common size by a seeded
+                  random draw, or by farthest-point sampling on the device (dpc/render/sampling.py)
 
 The schedule, the tie rules and the summation order are in include/dpc_render.h (dpc_emd_fwd).
 """
@@ -19,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _batch, _native
+from . import sampling as _sampling
 from ._ops import status_word
 from .chamfer import _host_unit_quaternion, _prediction, _rotate
 
@@ -212,8 +214,20 @@ def subsample_indices(counts, num_points, seed):
     return out
 
 
+def _fps_counts(counts, num_points):
+    """The refusals of emd_of_split(sampling="fps") for counts as subsample_indices takes them: ValueError naming the
+    model for a cloud with fewer than num_points points or more than DPC_FPS_MAX_POINTS."""
+    for m, (gn, views) in enumerate(counts):
+        for what, n in [("GT cloud of model %d" % m, gn)] + [("view %d of model %d" % (v, m), vn) for v, vn in enumerate(views)]:
+            if n < num_points:
+                raise ValueError("emd_of_split: %s has %d points, fewer than num_points = %d" % (what, n, num_points))
+            if n > _sampling.MAX_POINTS:
+                raise ValueError("emd_of_split: %s has %d points, sampling=\"fps\" takes at most DPC_FPS_MAX_POINTS = %d"
+                                 % (what, n, _sampling.MAX_POINTS))
+
+
 def emd_of_split(predictions, gt_clouds, reference_rotation=None, num_points=1024, seed=0, squared=False, eps=None,
-                 max_rounds=None, models_per_call=64):
+                 max_rounds=None, models_per_call=64, sampling="random"):
     """The EMD table of a split, [M,V] float64 numpy: every view's prediction against its model's GT cloud, next to
     chamfer_of_split and with its arguments: predictions per model (points [V,N,3], num_points [V] | None) or
     load_predictions' triples, view i truncated to its first num_points[i] points; gt_clouds per model [n,3];
@@ -223,7 +237,13 @@ def emd_of_split(predictions, gt_clouds, reference_rotation=None, num_points=102
     subsampled to num_points points without replacement by subsample_indices(…, num_points, seed): one generator for
     the split; per model the GT cloud first, then its views in order.  The result does not depend on models_per_call.
     A cloud with fewer than num_points points raises ValueError naming the model; a pair that did not converge (or
-    holds a NaN coordinate) raises RuntimeError naming model and view.  squared, eps, max_rounds as emd_loss."""
+    holds a NaN coordinate) raises RuntimeError naming model and view.  squared, eps, max_rounds as emd_loss.
+
+    sampling="fps" replaces the random draw by farthest-point sampling on the device (farthest_point_sample with
+    first = 0): each model's GT cloud once, and each of its views after truncation and rotation.  The subsample is
+    deterministic and covers the cloud evenly; seed is ignored.  A cloud with more than DPC_FPS_MAX_POINTS points raises
+    ValueError naming the model, a cloud with a NaN or infinite coordinate RuntimeError naming it.  Any other value of
+    sampling raises ValueError."""
     if len(predictions) != len(gt_clouds):
         raise ValueError("emd_of_split: %d predictions and %d GT clouds" % (len(predictions), len(gt_clouds)))
     if int(models_per_call) < 1:
@@ -239,7 +259,13 @@ def emd_of_split(predictions, gt_clouds, reference_rotation=None, num_points=102
     V = views.pop() if views else 0
     counts = [(len(g), [int(p.shape[1]) if nums is None else int(nums[i]) for i in range(V)])
               for (p, nums), g in zip(preds, gts)]
-    picks = subsample_indices(counts, num_points, seed)
+    if sampling not in ("random", "fps"):
+        raise ValueError("emd_of_split: sampling must be \"random\" or \"fps\", got %r" % (sampling,))
+    fps = sampling == "fps"
+    if fps:
+        _fps_counts(counts, num_points)
+    else:
+        picks = subsample_indices(counts, num_points, seed)
     qn = None if reference_rotation is None else _host_unit_quaternion(reference_rotation)
     M = len(preds)
     out = np.zeros((M, V), dtype=np.float64)
@@ -254,13 +280,29 @@ def emd_of_split(predictions, gt_clouds, reference_rotation=None, num_points=102
         for m in group:
             pts = preds[m][0]
             pts = _rotate(pts, qn, dev) if qn is not None else pts.to(dev)
+            if fps:
+                g = gts[m].to(dev)
+                view_list.extend(pts[i][:counts[m][1][i]] for i in range(V))
+                gt_list.append(g)
+                continue
             g = gts[m].to(dev)[torch.from_numpy(picks[m][0]).to(dev)]
             for i in range(V):
                 view_list.append(pts[i][torch.from_numpy(picks[m][1][i]).to(dev)])
                 gt_list.append(g)
+        if fps:   # one call for the group's GT clouds, one for its views; the full clouds give way to their samples
+            g_idx = _sampling._sample(gt_list, num_points, 0, status)[0]
+            v_idx = _sampling._sample(view_list, num_points, 0, status)[0]
+            sampled = torch.stack([i[0] for i in g_idx + v_idx])   # -1: that cloud holds a non-finite coordinate
+            gt_list = [g[i.long()] for g, i in zip(gt_list, g_idx) for _ in range(V)]
+            view_list = [v[i.long()] for v, i in zip(view_list, v_idx)]
         with torch.no_grad():
             emd = _run(view_list, gt_list, squared, eps, max_rounds, "emd_of_split", status)[0]
         res = emd.cpu().numpy().reshape(len(group), V)
+        if fps and bool((sampled < 0).any()):
+            k = int(np.argmax(sampled.cpu().numpy() < 0))
+            G = len(group)
+            what = "GT cloud of model %d" % (a + k) if k < G else "view %d of model %d" % ((k - G) % V, a + (k - G) // V)
+            raise RuntimeError("emd_of_split: %s holds a NaN or infinite coordinate" % what)
         if np.isnan(res).any():
             j, i = np.argwhere(np.isnan(res))[0]
             raise RuntimeError("emd_of_split: model %d, view %d did not converge within max_rounds (or holds a NaN "
