@@ -47,6 +47,9 @@ extern "C" {
 #define DPC_EMD_MAX_POINTS 2048
 /* Most points per cloud of dpc_fps: a cloud is held on chip by one workgroup of 1024 threads, 16 points per thread. */
 #define DPC_FPS_MAX_POINTS 16384
+/* Longest side of a grid of the dpc_voxel* entry points: a 128^3 bit grid is 256 KiB, four LDS slabs of dpc_voxelise,
+ * and a flat voxel index stays far inside an int. */
+#define DPC_VOXEL_MAX_SIDE 128
 
 enum {
   DPC_OK = 0,
@@ -77,7 +80,9 @@ enum {
   DPC_STATUS_NEAR = 32,           /* dpc_render_meshes: a face has a vertex at depth d <= DPC_MESH_NEAR (it was skipped)   */
   DPC_STATUS_EMD_NOT_CONVERGED = 64 /* dpc_emd_fwd: a pair was still unmatched after max_rounds bidding rounds (its emd
                                    * is NaN); DPC_STATUS_BAD_INDEX there and in dpc_fps: the device table differs
-                                   * from the host's                                                                   */
+                                   * from the host's.  dpc_voxelise: DPC_STATUS_NONFINITE for a NaN or infinite
+                                   * coordinate (the point is dropped); DPC_STATUS_BAD_INDEX in the dpc_voxel* entry
+                                   * points: a device-table row failed its check (it was not run)                      */
 };
 
 /* Geometry and camera constants of one call (dpc/resources/default_config.yaml:77-89 and the cfg fields
@@ -742,6 +747,64 @@ int dpc_emd_bwd(const void* pred, int n_pred, const void* gt, int n_gt, int is_f
  * ------------------------------------------------------------------------------------------------- */
 int dpc_fps(const void* pts, int n_pts, int is_f64, const int32_t* cloud_desc, const int32_t* host_cloud_desc, int clouds,
             int32_t* indices, double* radius2, int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Voxel-grid evaluation (dpc/util/voxel.py: evaluate_voxel_prediction, voxel2pc): clouds and float grids to bit grids,
+ * the five counts of evaluate_voxel_prediction per pair of bit grids, and bit grids back to points.  Every output is
+ * integer- or bit-exact: there is one right answer and no tolerance.  The conventions:
+ *
+ * Grid layout.  A grid is [D,H,W], D = vox_size_z (vox_size when that is -1), H = W = vox_size; point column c goes to
+ *   grid axis c, as in pointcloud2voxels3d_fast (point_cloud_to.py:29-30).
+ * Voxelisation (the nearest node of the renderer's node-centred grid).  A point is valid iff -0.5 <= p_c <= 0.5 on all
+ *   three axes (the reference's outlier filter, :26).  For a valid point, in fp64 (fp32 input is widened exactly first)
+ *   and without contraction, t_c = (p_c + 0.5) * (G_c - 1) and its node is i_c = (int)floor(t_c + 0.5): the same node
+ *   for an fp32 cloud and its fp64 copy.  Invalid and non-finite points mark nothing and are counted in dropped[cloud];
+ *   a NaN or infinite coordinate also ORs DPC_STATUS_NONFINITE into *status.  An index is never formed from an invalid
+ *   point.  An empty cloud gives an all-zero grid.
+ * Bit grids.  A grid is words = ceil(D*H*W / 32) uint32; voxel f = (d*H + h)*W + w is bit f & 31 of word f >> 5.  The
+ *   entry points that write bit grids leave the padding bits of the last word zero; those that read them ignore them.
+ * Thresholding a float grid.  occupied = v > threshold, or v >= threshold when `inclusive` (voxel2pc, voxel.py:63, is
+ *   exclusive; evaluate_voxel_prediction, :5, inclusive), compared in the grid's own dtype with the threshold rounded to
+ *   that dtype (what NumPy 2 does with a Python float; it matters for 0.3 on fp32 grids).  A NaN voxel is unoccupied.
+ *   dtype: 0 fp32, 1 fp64, 2 uint8 (a bool grid: occupied = non-zero, threshold and inclusive are not read).
+ * The five counts, in evaluate_voxel_prediction's order, each an int64 popcount over a pair (p, g) of bit grids:
+ *   diff = |p ^ g|, intersection = |p & g|, union = |p | g|, num_fp = |p & ~g|, num_fn = |~p & g|.
+ * voxel2pc keeps the reference's quirk: with x = arange(G) * (1.0 / (G - 1)) + (-0.5) in fp64, nothing fused, and
+ *   x[G-1] = 0.5 (np.linspace), voxel (i,j,k) becomes the point (x[j], x[i], x[k]) -- the default 'xy' np.meshgrid swaps
+ *   the first two axes -- and points come in ascending flat index (i*G + j)*G + k.  So voxelising the points of
+ *   voxel2pc(v, t) gives (v > t) with its first two axes transposed.  Cubic grids with G >= 2 only, as the reference.
+ *
+ * Limits: 1 <= D, H, W <= DPC_VOXEL_MAX_SIDE.  dpc_voxelise keeps a workgroup's share of a grid's bits in LDS, set by
+ * LDS atomic OR and written out by plain stores; by the words of the grid it runs one of three size classes:
+ *   1 .. 1024 words (up to 32^3)       the whole grid, 4 KiB, 256 threads
+ *   1025 .. 8192 words (up to 64^3)    the whole grid, 32 KiB, 512 threads
+ *   above (up to 128^3 = 65536 words)  slabs of 16384 words (2^19 voxels: 32 z-planes at 128^3), 64 KiB, 1024 threads,
+ *                                      ceil(words / 16384) workgroups per cloud, each reading the whole cloud
+ * Tables: cloud_desc / host_cloud_desc [C,2] int32 (start, count) rows of pts (DEVICE / HOST, the same values; ranges
+ * may share rows); pair_desc [P,2] (pred grid, gt grid) indices, so the views of one model share one GT grid; out_desc
+ * [B,2] (start, count) rows of xyz per grid, count = what dpc_voxel_count reported, ranges ascending without overlap.
+ * A device-table row that fails its check against n_pts / n_pred, n_gt / n_out is not read further, sets
+ * DPC_STATUS_BAD_INDEX and leaves its outputs untouched; so does, in dpc_voxel2pc, a count that is not the grid's (no
+ * point beyond the row's range is written).  status: DEVICE int32, zeroed by the caller, NULL allowed.
+ * Every check runs before any launch (DPC_ERR_SHAPE: a negative size, a side outside the limits, an unknown dtype, a
+ * table row outside its array, G < 2 or out ranges that do not ascend in dpc_voxel2pc); valid arguments with NULL
+ * device pointers return DPC_ERR_NULL without touching a device; zero items return DPC_OK with nothing launched.  No
+ * host synchronisation, no allocation, no workspace, no floating-point atomics and no global atomics but the OR into
+ * the status word.  dpc_voxel_unpack writes one byte (0 / 1) per voxel, [B,D,H,W], to a 4-byte aligned `out` (DPC_ERR_SHAPE
+ * otherwise).  Added without a new ABI number: no
+ * existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+int dpc_voxelise(const void* pts, int n_pts, int is_f64, const int32_t* cloud_desc, const int32_t* host_cloud_desc, int clouds,
+                 int D, int H, int W, uint32_t* bits, int32_t* dropped, int32_t* status, void* stream);
+int dpc_voxel_threshold(const void* grids, int dtype, int B, int D, int H, int W, double threshold, int inclusive, uint32_t* bits,
+                        void* stream);
+int dpc_voxel_unpack(const uint32_t* bits, int B, int D, int H, int W, uint8_t* out, void* stream);
+int dpc_voxel_stats(const uint32_t* pred_bits, int n_pred, const uint32_t* gt_bits, int n_gt, int D, int H, int W,
+                    const int32_t* pair_desc, const int32_t* host_pair_desc, int pairs, int64_t* stats, int32_t* status,
+                    void* stream);
+int dpc_voxel_count(const uint32_t* bits, int B, int D, int H, int W, int32_t* counts, void* stream);
+int dpc_voxel2pc(const uint32_t* bits, int B, int G, const int32_t* out_desc, const int32_t* host_out_desc, int n_out, double* xyz,
+                 int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Voxel-grid downsampling of ground-truth clouds (densify/downsample_gt.py:47-57: open3d.voxel_down_sample(pcd,
