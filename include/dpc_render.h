@@ -50,6 +50,12 @@ extern "C" {
 /* Longest side of a grid of the dpc_voxel* entry points: a 128^3 bit grid is 256 KiB, four LDS slabs of dpc_voxelise,
  * and a flat voxel index stays far inside an int. */
 #define DPC_VOXEL_MAX_SIDE 128
+/* The fills of dpc_voxelise_meshes, and the size from which a vertex coordinate counts as not finite there (below it no
+ * product of the separating-axis tests can overflow). */
+#define DPC_MESH_FILL_NONE 0
+#define DPC_MESH_FILL_CARVE 1
+#define DPC_MESH_FILL_PARITY 2
+#define DPC_MESH_VOXEL_MAX_COORD 18446744073709551616.0 /* 2^64 */
 
 enum {
   DPC_OK = 0,
@@ -805,6 +811,62 @@ int dpc_voxel_stats(const uint32_t* pred_bits, int n_pred, const uint32_t* gt_bi
 int dpc_voxel_count(const uint32_t* bits, int B, int D, int H, int W, int32_t* counts, void* stream);
 int dpc_voxel2pc(const uint32_t* bits, int B, int G, const int32_t* out_desc, const int32_t* host_out_desc, int n_out, double* xyz,
                  int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Mesh voxelisation: triangle meshes to solid ground-truth occupancy grids (what the reference expects ready-made as
+ * <model>.mat files with a `Volume` array, dpc/run/create_tf_records.py:104-115, made off-line with binvox), for M
+ * meshes in one call, and the "carve" fill for any bit grid.  There is no counterpart program in the reference and no
+ * binvox to compare with: the rules below are this library's own, tests/mesh_voxels_oracle.py restates them in numpy
+ * with every operation written out, and where this text and the oracle could differ in a last bit the oracle is the
+ * definition.  Every output is bits; the fp64 arithmetic is elementwise, nothing is fused (csrc/dpc_mesh_voxels.hip).
+ *
+ * Conventions: those of the voxelisation above, so the grid of a mesh and the grid of a cloud of the same model line up.
+ *   Grid [D,H,W], node-centred over [-1/2, 1/2]^3, vertex column c to grid axis c; grid coordinates
+ *   u_c = (v_c + 0.5) * (G_c - 1) in fp64 (fp32 vertices widen exactly); bit grids as above; 2 <= D, H, W <=
+ *   DPC_VOXEL_MAX_SIDE.
+ * Surface.  Node n is set iff the closed cube [n - 1/2, n + 1/2]^3 meets the closed triangle: the 13-axis separating-axis
+ *   test (3 box axes, the face normal, 9 edge x axis products) on the vertices translated to the node, p = u - n, with
+ *   half-size 0.5; the edges e0 = u1 - u0, e1 = u2 - u1, e2 = u0 - u2 and the normal e0 x e1 are the face's own.  An
+ *   axis separates only on a strict inequality, so touching counts.  Candidate nodes: ceil(min_c - 0.5) ..
+ *   floor(max_c + 0.5) of the face's bounding box, clamped to the grid.  A zero-area face marks what its edges and points
+ *   touch (its normal test never separates).  Geometry outside the cube marks nothing.
+ * Fill DPC_MESH_FILL_CARVE.  A node is solid iff on each of the three grid lines through it there is a surface node at
+ *   an index <= its own and one at an index >= its own: nothing is removed that cannot be seen from one of the six
+ *   axis directions.  Robust to open and self-intersecting meshes; it fills concavities no axis direction sees, by design.
+ *   dpc_voxel_carve is the same fill for any bit grids (sides from 1), e.g. the shell of a predicted cloud.
+ * Fill DPC_MESH_FILL_PARITY.  Rays along grid axis 0 through the integer (y, x) columns, (y, x) = axes (1, 2).  A face is
+ *   projected to (y, x); its edge function of P -> Q at column c is (Q.x - P.x) * (c.y - P.y) - (Q.y - P.y) * (c.x - P.x),
+ *   evaluated from the lexicographically smaller endpoint (y first) and negated when that is Q, so two faces sharing an
+ *   edge see equal or exactly opposite values.  area = the function of 0 -> 1 at vertex 2; a face with area == 0
+ *   contributes nothing; the three values w_k (edge opposite vertex k) and the edge directions are negated when area < 0.
+ *   A column is crossed when every w_k > 0, or == 0 on a top-left edge (dy > 0, or dy == 0 and dx < 0), and
+ *   (w0 + w1) + w2 != 0.  Depth z* = ((w0 z0 + w1 z1) + w2 z2) / ((w0 + w1) + w2), z the axis-0 grid coordinates; the
+ *   crossing toggles plane k = ceil(z*) clamped to [0, D] (k = D reaches no node).  parity = prefix XOR of the toggles
+ *   along axis 0; the result is surface | parity.  A column with an odd number of crossings is "open" (it leaks to z = D).
+ * Guards.  A face with a vertex that is NaN, infinite or >= DPC_MESH_VOXEL_MAX_COORD in magnitude is skipped and sets
+ *   DPC_STATUS_NONFINITE; a face with an index outside [0, count of its mesh's vertices) is skipped and sets
+ *   DPC_STATUS_BAD_INDEX: it never becomes an address.  A device-table row that does not lie inside verts / faces sets
+ *   DPC_STATUS_BAD_INDEX and its mesh's outputs are left untouched.
+ * Arguments of dpc_voxelise_meshes:
+ *   verts [n_verts,3] fp32 (is_f64 = 0) or fp64, faces [n_faces,3] int32 with indices local to their mesh, both packed
+ *   in mesh order; mesh_desc / host_mesh_desc [M,4] int32 (first vertex, vertices, first face, faces), DEVICE / HOST, the
+ *   same values; fill one of DPC_MESH_FILL_*; bits [M, words] the grids; scratch [M, words], needed by
+ *   DPC_MESH_FILL_CARVE only (the surface, which the fill reads while it writes bits; NULL otherwise); info [M,2] int32:
+ *   (kept faces with a vertex outside the cube, open columns: 0 unless the fill is DPC_MESH_FILL_PARITY); status DEVICE
+ *   int32, zeroed by the caller, NULL allowed.  A mesh without faces gives an empty grid.
+ * Kernels: one workgroup per (mesh, slab of the grid held in LDS), as dpc_voxelise: bits are OR-ed (toggles XOR-ed) with
+ *   LDS atomics and finished words written with plain stores; the result does not depend on the order of the faces and
+ *   needs no zeroed output.  A face with many candidate nodes is handed to a whole wave or workgroup.
+ * Every check runs before any launch (DPC_ERR_SHAPE: a negative size, a side outside the limits, an unknown fill, a table
+ * row outside its array; dpc_voxel_carve: out == bits); valid arguments with NULL device pointers return DPC_ERR_NULL
+ * without touching a device; zero items return DPC_OK with nothing launched.  No host synchronisation, no allocation,
+ * no floating-point atomics and no global atomics but the OR into the status word.  Added without a new ABI number: no
+ * existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+int dpc_voxelise_meshes(const void* verts, int n_verts, int is_f64, const int32_t* faces, int n_faces, const int32_t* mesh_desc,
+                        const int32_t* host_mesh_desc, int meshes, int D, int H, int W, int fill, uint32_t* bits, uint32_t* scratch,
+                        int32_t* info, int32_t* status, void* stream);
+int dpc_voxel_carve(const uint32_t* bits, int B, int D, int H, int W, uint32_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Voxel-grid downsampling of ground-truth clouds (densify/downsample_gt.py:47-57: open3d.voxel_down_sample(pcd,

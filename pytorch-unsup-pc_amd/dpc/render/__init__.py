@@ -31,6 +31,7 @@ from .downsample import downsample_split, voxel_down_sample  # noqa: F401
 from .voxels import (evaluate_voxel_prediction, iou_of_split, render_voxels, voxel2pc, voxel_iou, voxel_stats,  # noqa: F401
                      voxelise, voxels2pc_batched)
 from .densify import MeshError, densify_meshes, densify_split, load_obj_mesh  # noqa: F401
+from .meshvoxels import carve_voxels, solid_iou_of_split, voxelise_meshes  # noqa: F401
 from .visualise import (camera_frame, read_png_any, render_point_cloud, render_point_clouds, render_split, write_png,  # noqa: F401
                         write_png_gray16, write_png_rgba)
 from .meshviews import (ShadedScene, camera_extrinsic, features_of_views, load_obj_scene, load_obj_scene_shaded,  # noqa: F401
@@ -51,7 +52,7 @@ __all__ = [
     "nearest_batched", "chamfer_batched", "chamfer_loss", "chamfer_of_split", "eval_chamfer", "voxel_down_sample", "downsample_split",
     "emd_loss", "emd_match", "emd_of_split", "farthest_point_sample",
     "voxelise", "voxel_stats", "voxel_iou", "evaluate_voxel_prediction", "voxel2pc", "voxels2pc_batched", "iou_of_split",
-    "render_voxels",
+    "render_voxels", "voxelise_meshes", "carve_voxels", "solid_iou_of_split",
     "load_obj_mesh", "densify_meshes", "densify_split", "MeshError",
     "camera_frame", "render_point_clouds", "render_point_cloud", "render_split", "write_png",
     "write_png_rgba", "write_png_gray16", "read_png_any",
