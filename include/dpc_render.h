@@ -364,6 +364,35 @@ int dpc_gauss_voxels_bwd(const DpcParams* p, const float* tr, double sigma, int 
                          float* dtr, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Ground truth prepared for the losses: cfg.pc_gauss_filter_gt / pc_gauss_filter_gt_rgb of the TF-1 original
+ * (gauss_smoothen_image, dpc/util/gauss_kernel.py:14-24; dpc/models/model_pc.py:398-404; dpc/util/losses.py:78-83, 128-129).
+ * One launch that resizes the ground truth to the projection's size and blurs it.  Added without a new ABI number.
+ *   gt   fp32, S samples of C channels (1 or 3) of Hs x Ws: [S,C,Hs,Ws] when `planar`, else [S,Hs,Ws,C];
+ *        Hs = f*H, Ws = f*W for one integer f >= 1, Hs, Ws <= 1024
+ *   out  [S,H,W,C] fp32 (overwritten)
+ * Per plane, in this order:
+ *   remap   where gt == remap_from the value is remap_to (add_proj_depth_loss's max_dataset_depth -> max_depth,
+ *           losses.py:121-124); off when remap_from == remap_to
+ *   resize  DPC_GT_RESIZE_MEAN: the f x f average, summed row-major in fp32 and divided by f*f (the bits of nn.AvgPool2d(f)
+ *           and of dpc_silhouette_loss's pooling); DPC_GT_RESIZE_SAMPLE: g[y,x] = gt[f*y, f*x] (what the depth, colour
+ *           and ray-consistency losses read)
+ *   blur    tf.nn.depthwise_conv2d twice with padding "SAME": the row pass ([1,ntaps]) first, then the column pass
+ *           ([ntaps,1]), the same ntaps taps (odd, <= DPC_MAX_TAPS) for every channel, ZEROS outside the H x W plane (so a
+ *           depth map darkens at its border: the reference's behaviour).  Each pass adds its terms in tap order
+ *           0..ntaps-1 in fp32, the first a plain product: one tap of 1.0 returns the resized input bit for bit.
+ * Taps: dev_taps != NULL -- ntaps floats in DEVICE memory, read by the kernel when it runs (a DeviceSchedule's taps_xy: a
+ * captured graph follows sigma); otherwise host_taps, ntaps floats on the host that travel as launch arguments.
+ * DPC_ERR_NULL for a missing gt, out, or both tap pointers; DPC_ERR_SHAPE for S <= 0, C not 1 or 3, a non-integer or
+ * unequal factor, a source side above 1024, an unknown resize_mode; DPC_ERR_TAPS for an even, non-positive or too long tap
+ * count -- all before any launch.  Planes are tiled (16 x 64 outputs and their halo per workgroup, at most 59 KiB of LDS at
+ * 63 taps), so no accepted plane is refused for its size: there is no DPC_ERR_LDS here.  No atomics, no host-to-device
+ * copy, no synchronisation; safe under graph capture; equal inputs give equal bits. */
+#define DPC_GT_RESIZE_MEAN 0
+#define DPC_GT_RESIZE_SAMPLE 1
+int dpc_gt_smooth(const float* gt, int S, int C, int Hs, int Ws, int planar, int H, int W, int resize_mode, float remap_from,
+                  float remap_to, const float* host_taps, const float* dev_taps, int ntaps, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Expected depth and its loss, fused (add_proj_depth_loss, dpc/util/losses.py:113-136, on drc_depth_projection,
  * dpc/util/drc.py:145-160): from grid_wh of dpc_project_fwd (the grid after the clamp and the W, H passes) in one column
  * kernel -- D pass, occupancy scale + clamp, DRC recurrence, depth, squared error -- instead of a smoothed grid, a

@@ -40,6 +40,7 @@ def chair_unsupervised(**overrides):
         # schedules, loss, optimiser
         pc_point_dropout=0.07, pc_point_dropout_scheduled=True, pc_point_dropout_exponential_schedule=False,
         pc_point_dropout_start_step=0.0, pc_point_dropout_end_step=1.0, max_number_of_steps=600000,
-        proj_weight=1.0, drc_weight=0.0, proj_depth_weight=0.0, pc_gauss_filter_gt=False, weight_decay=0.001, learning_rate=1e-4)
+        proj_weight=1.0, drc_weight=0.0, proj_depth_weight=0.0, pc_gauss_filter_gt=False,
+        pc_gauss_filter_gt_switch_off=False, weight_decay=0.001, learning_rate=1e-4)
     cfg.update(overrides)
     return cfg

@@ -32,6 +32,15 @@ Ray-consistency terms (one pose candidate per image), further nodes on the same 
     this term is the one place where the step goes beyond get_loss.
     total += drc_weight * drc + drc_rgb_weight * drc_rgb.
 
+Smoothed ground truth (cfg.pc_gauss_filter_gt; dpc/models/model_pc.py:398-404, dpc/util/losses.py:128-129): the masks are
+resized to the silhouette's size and blurred with this step's Gaussian once per step, by one node (dpc.render.smooth_gt),
+honouring cfg.pc_gauss_filter_gt_switch_off; that tensor is the ground truth of the silhouette loss (K = 1 and K candidates,
+fused or as a node on the projection), of add_drc_loss, and out["pooled_masks"].  The depth maps are prepared likewise for
+the depth loss, and under cfg.pc_gauss_filter_gt_rgb the images for the colour loss, with the same sigma
+(model_pc_to.py:400); pc_gauss_filter_gt_rgb with drc_rgb_weight != 0 is refused.  In a captured step the node reads device
+taps of the step's own (dpc.render.DeviceTaps), rewritten in front of every replay -- the identity kernel while the
+switch-off holds -- so neither sigma nor the threshold needs a recapture.
+
 cfg.pc_fast == false (compute_projection's else-branch, dpc/models/model_pc.py:249-252): the exact Gaussian renderer
 dpc.render.pointcloud_project_exact with sigma = get_smooth_sigma(step) / vox_size as a launch argument, the min-of-K
 silhouette loss on its projection and the student term; no occupancy scale (the reference passes none on this path).  The
@@ -110,6 +119,9 @@ class TrainStep:
         self._schedule = None      # dpc.render.DeviceSchedule ONLY while a graph is being captured (record() below): an eager
                                    # loss() / __call__ on this object afterwards computes its values from the step it is asked for
         self._captured_schedule = None   # the schedule the current graph's kernels read; rewritten in front of every replay
+        self._gt_taps = None       # dpc.render.DeviceTaps of the ground-truth node (cfg.pc_gauss_filter_gt), like _schedule:
+                                   # set ONLY while a graph is being captured
+        self._captured_gt_taps = None    # the taps the current graph's ground-truth node reads; rewritten like the schedule
         self.recaptures = 0
         self.global_step = 0
         self.grad_sync, self.sync_samples = None, (1, 1)
@@ -140,6 +152,11 @@ class TrainStep:
         rgb_weight = cfg.get("proj_rgb_weight", 0.0) if cfg.get("pc_rgb", False) else 0.0
         drc_weight = cfg.get("drc_weight", 0.0)
         drc_rgb_weight = cfg.get("drc_rgb_weight", 0.0) if cfg.get("pc_rgb", False) else 0.0
+        filter_gt, filter_rgb = bool(cfg.get("pc_gauss_filter_gt", False)), bool(cfg.get("pc_gauss_filter_gt_rgb", False))
+        if filter_rgb and drc_rgb_weight != 0:
+            raise NotImplementedError("pc_gauss_filter_gt_rgb: true with drc_rgb_weight != 0: the reference never smooths the "
+                                      "images of add_drc_rgb_loss (dpc/util/losses.py:93-110) and never calls that loss; the "
+                                      "two terms would read different ground truth")
         if not cfg.get("pc_fast", True):
             for key, weight in (("proj_depth_weight", depth_weight), ("proj_rgb_weight", rgb_weight), ("drc_weight", drc_weight),
                                 ("drc_rgb_weight", drc_rgb_weight)):
@@ -179,20 +196,27 @@ class TrainStep:
                 host = np.stack([np.random.choice(all_points.shape[1], n_out, replace=False) for _ in range(clouds)])
                 point_index = torch.from_numpy(host.astype(np.int32)).to(all_points.device)
         kernel = R.smoothing_kernel(cfg, R.get_smooth_sigma(cfg, step))
+        # cfg.pc_gauss_filter_gt: the masks are resized and smoothed once, with this step's sigma, and the same tensor feeds the
+        # silhouette loss and add_drc_loss (add_proj_loss stores it back into inputs['masks'], model_pc_to.py:354-366, 396-397)
+        gt_masks = self._prepared_gt(masks, "masks", step) if filter_gt else masks
+        prepared = lambda on: {"gt_prepared": True} if on else {}   # without the keys the losses are called as before
         if depth_weight != 0 or rgb_weight != 0 or drc_weight != 0 or drc_rgb_weight != 0:
             # projection, silhouette loss and depth / colour / ray-consistency losses as nodes on one projection: their gradients
             # join the silhouette's at the projection's outputs (get_loss, model_pc_to.py:391-408 with losses.py:23-136)
             proj_out = R.pointcloud_project_fast(cfg, all_points, out["poses"], None, None, kernel, scaling_factor=all_scales,
                                                  point_index=point_index, schedule=sched)
-            proj_loss, winner = R.silhouette_loss(proj_out["proj"], masks, K, valid_samples)
+            proj_loss, winner = R.silhouette_loss(proj_out["proj"], gt_masks, K, valid_samples)
             total = proj_loss.double() * cfg.proj_weight
-            out.update(projs=proj_out["proj"], min_loss=winner, proj_loss=proj_loss, pooled_masks=pooled_masks(masks, cfg.vox_size))
+            out.update(projs=proj_out["proj"], min_loss=winner, proj_loss=proj_loss,
+                       pooled_masks=gt_masks if filter_gt else pooled_masks(masks, cfg.vox_size))
             if depth_weight != 0:
-                depth_loss, projs_depth = R.proj_depth_loss(cfg, proj_out, depths, valid_samples, return_depth=True)   # one pass
+                gt_depths = self._prepared_gt(depths, "depths", step) if filter_gt else depths
+                depth_loss, projs_depth = R.proj_depth_loss(cfg, proj_out, gt_depths, valid_samples, return_depth=True,
+                                                            **prepared(filter_gt))   # one pass
                 total = total + depth_loss.double() * depth_weight
                 out.update(depth_loss=depth_loss, projs_depth=projs_depth)
             if drc_weight != 0:   # on the masks add_proj_loss pooled (model_pc_to.py:354-366), at their own size
-                drc = R.drc_loss(cfg, proj_out, out["pooled_masks"], valid_samples)
+                drc = R.drc_loss(cfg, proj_out, out["pooled_masks"], valid_samples, **prepared(filter_gt))
                 total = total + drc.double() * drc_weight
                 out.update(drc_loss=drc)
             if (rgb_weight != 0 or drc_rgb_weight != 0) and cfg.get("pc_rgb_deterministic", False):
@@ -203,9 +227,10 @@ class TrainStep:
                 all_rgb = R.replicate_rgb(out["rgb_1"], out["poses"].shape[0], point_index)   # model_pc_to.py:254-258, 323-329
                 grids = R.rgb_grids(cfg, proj_out, all_rgb, kernel)   # one colour splat and smoothing for both colour terms
                 out.update(all_rgb=all_rgb)
-            if rgb_weight != 0:
-                rgb_loss, projs_rgb = R.proj_rgb_loss(cfg, proj_out, all_rgb, images, kernel, valid_samples, return_rgb=True,
-                                                      grids=grids)
+            if rgb_weight != 0:   # get_loss hands add_proj_rgb_loss the same sigma_rel (model_pc_to.py:400)
+                gt_images = self._prepared_gt(images, "images", step) if filter_rgb else images
+                rgb_loss, projs_rgb = R.proj_rgb_loss(cfg, proj_out, all_rgb, gt_images, kernel, valid_samples, return_rgb=True,
+                                                      grids=grids, **prepared(filter_rgb))
                 total = total + rgb_loss.double() * rgb_weight
                 out.update(rgb_loss=rgb_loss, projs_rgb=projs_rgb)
             if drc_rgb_weight != 0:
@@ -214,10 +239,11 @@ class TrainStep:
                 out.update(drc_rgb_loss=drc_rgb)
             return total, out
         proj_loss, proj_out, winner = R.pointcloud_project_loss(cfg, all_points, out["poses"], None, None, kernel,
-                                                                scaling_factor=all_scales, gt=masks, num_candidates=K,
+                                                                scaling_factor=all_scales, gt=gt_masks, num_candidates=K,
                                                                 point_index=point_index, schedule=sched,
                                                                 valid_samples=valid_samples)
-        gt = pooled_masks(masks, cfg.vox_size)   # for the outputs dict only: the loss above pooled the masks itself
+        # for the outputs dict only: the loss above pooled the masks itself (or read the prepared ones)
+        gt = gt_masks if filter_gt else pooled_masks(masks, cfg.vox_size)
         total = proj_loss.double()
         if K > 1 and cfg.pose_predictor_student:
             out["student_loss"] = student_loss(out["poses"], out["pose_student"], winner, K, cfg.pose_predictor_student_loss_weight,
@@ -241,15 +267,44 @@ class TrainStep:
                 all_points, _ = R.pc_point_dropout(all_points, None, keep)
         sigma = R.get_smooth_sigma(cfg, step) / cfg.vox_size
         proj, _ = R.pointcloud_project_exact(cfg, all_points, out["poses"], sigma)
-        proj_loss, winner = R.silhouette_loss(proj, masks, K, valid_samples)
+        filter_gt = bool(cfg.get("pc_gauss_filter_gt", False))
+        gt_masks = self._prepared_gt(masks, "masks", step) if filter_gt else masks   # model_pc.py:398-404
+        proj_loss, winner = R.silhouette_loss(proj, gt_masks, K, valid_samples)
         total = proj_loss.double()
         if K > 1 and cfg.pose_predictor_student:
             out["student_loss"] = student_loss(out["poses"], out["pose_student"], winner, K, cfg.pose_predictor_student_loss_weight,
                                                valid_samples)
             total = total + out["student_loss"]
         total = total * cfg.proj_weight
-        out.update(projs=proj, min_loss=winner, proj_loss=proj_loss, pooled_masks=pooled_masks(masks, cfg.vox_size))
+        out.update(projs=proj, min_loss=winner, proj_loss=proj_loss,
+                   pooled_masks=gt_masks if filter_gt else pooled_masks(masks, cfg.vox_size))
         return total, out
+
+    # ---- smoothed ground truth (cfg.pc_gauss_filter_gt, pc_gauss_filter_gt_rgb, pc_gauss_filter_gt_switch_off) ----
+    def _prepared_gt(self, gt, kind, step):
+        """dpc.render.smooth_gt with this step's sigma_rel: ground truth at the projection's size, [S,H,W,C].  While a graph
+        is being captured the node reads the step's own device taps instead (masks only: the supervised steps are eager)."""
+        if self._gt_taps is not None:
+            return R.smooth_gt(self.cfg, gt, self.cfg.vox_size, kind, schedule=self._gt_taps)
+        return R.smooth_gt(self.cfg, gt, self.cfg.vox_size, kind, sigma_rel=R.get_smooth_sigma(self.cfg, step))
+
+    def _gt_tap_values(self, step):
+        """The taps the captured ground-truth node applies at `step`: this step's Gaussian, or under
+        cfg.pc_gauss_filter_gt_switch_off while sigma_rel < 1 the identity kernel of the same length -- multiplying finite
+        values by exactly 1 and 0 returns the resized bits, so the switch follows sigma from replay to replay without a flag
+        and without a recapture (tf.where(tf.less(sigma_rel, 1.0), gt, smoothed), model_pc.py:401-402)."""
+        cfg = self.cfg
+        sigma = R.get_smooth_sigma(cfg, step)
+        taps = R.gauss_kernel_1d(int(cfg.pc_gauss_kernel_size), sigma).numpy()
+        if cfg.get("pc_gauss_filter_gt_switch_off", False) and sigma < 1.0:
+            taps = np.zeros_like(taps)
+            taps[taps.size // 2] = 1.0
+        return taps
+
+    def _new_gt_taps(self, step):
+        if not self.cfg.get("pc_gauss_filter_gt", False):
+            return None
+        return R.DeviceTaps(self.device, self._gt_tap_values(step))
 
     def __call__(self, images, masks, valid_samples=None, depths=None):
         """zero_grad, forward, loss, backward, Adam step (train_to.py:112-131).  Returns the loss tensor (no host sync).
@@ -293,6 +348,8 @@ class TrainStep:
             self.recaptures += 1
         else:
             self._captured_schedule.update(kxy, kz, n_live)
+            if self._captured_gt_taps is not None:   # the ground-truth node takes any values: never a reason to capture again
+                self._captured_gt_taps.update(self._gt_tap_values(self.global_step))
 
     def _no_captured_depth_step(self):
         if not self.cfg.get("pc_fast", True):
@@ -337,6 +394,7 @@ class TrainStep:
 
         def record():
             self._captured_schedule = self._schedule = self._new_schedule(self.global_step)
+            self._captured_gt_taps = self._gt_taps = self._new_gt_taps(self.global_step)
             graph = torch.cuda.CUDAGraph()
             try:
                 with torch.cuda.graph(graph):
@@ -345,7 +403,7 @@ class TrainStep:
                     total, _ = self.loss(static_images, static_masks, valid_samples=static_valid)
                     total.backward()              # the hooks are disarmed: gradients simply land in the buckets
             finally:
-                self._schedule = None             # the captured kernels keep the pointers; eager calls do not see it
+                self._schedule = self._gt_taps = None   # the captured kernels keep the pointers; eager calls do not see them
             self._graph, state["graph"], state["loss"] = graph, graph, total.detach()
 
         record()
@@ -396,6 +454,7 @@ class TrainStep:
 
         def record():
             self._captured_schedule = self._schedule = self._new_schedule(self.global_step)
+            self._captured_gt_taps = self._gt_taps = self._new_gt_taps(self.global_step)
             self.optimizer.zero_grad(set_to_none=True)
             graph = torch.cuda.CUDAGraph()
             try:
@@ -404,7 +463,7 @@ class TrainStep:
                     total.backward()
                     self.optimizer.step()
             finally:
-                self._schedule = None             # the captured kernels keep the pointers; eager calls do not see it
+                self._schedule = self._gt_taps = None   # the captured kernels keep the pointers; eager calls do not see them
             self._graph, state["graph"], state["loss"] = graph, graph, total.detach()
 
         record()

@@ -17,10 +17,11 @@ import numpy as np
 import torch
 
 from . import _native
-from ._ops import (DepthLoss, DepthMap, DeviceSchedule, Drc, DrcLoss, DrcRgbLoss, GaussVoxels, Geometry, ProjectFused, ProjectLossFused, ProjectLossStep, RgbLoss, RgbMap, RgbSplat, RgbSplatFixed,
+from ._ops import (DepthLoss, DepthMap, DeviceSchedule, DeviceTaps, Drc, DrcLoss, DrcRgbLoss, GaussVoxels, Geometry, ProjectFused, ProjectLossFused, ProjectLossStep, RgbLoss, RgbMap, RgbSplat, RgbSplatFixed,
                    SilhouetteLoss, Smooth, Splat, Transform, status_word, taps_bucket)
 from ._ops import _plane as _ops_plane
 from ._ops import colour_sets as _ops_colour_sets
+from ._ops import gt_smooth as _ops_gt_smooth
 from .predictions import chamfer_of_predictions, load_predictions, save_predictions  # noqa: F401
 from .alignment import (alignment_candidates, alignment_to_ground_truth, as_rotation_matrix, from_rotation_matrix,  # noqa: F401
                         icp_point_to_point, pose_errors, quat_w_avg_markley, quaternion_from_campos, reference_rotation)
@@ -58,6 +59,7 @@ __all__ = [
     "write_png_rgba", "write_png_gray16", "read_png_any",
     "load_obj_scene", "sample_camera_positions", "view_rotation", "view_transform", "render_mesh_views", "camera_extrinsic",
     "features_of_views", "render_training_views", "load_obj_scene_shaded", "ShadedScene",
+    "smooth_gt", "gauss_smoothen_image", "DeviceTaps",
 ]
 
 
@@ -598,12 +600,15 @@ def pointcloud_project_loss(cfg, point_cloud, transform, predicted_translation, 
     unweighted), the usual output dict (`proj` from this pass, the rest lazy), and the
     winning candidate per sample.  Falls back to pointcloud_project_fast + silhouette_loss when the Gaussian is
     too long for the fused kernels.  `point_cloud` may hold shared point sets ([B/R,N,3]) and `point_index` per-cloud
-    subsets of them (see pointcloud_project_fast)."""
+    subsets of them (see pointcloud_project_fast).  Under cfg.pc_gauss_filter_gt `gt` must be the [S,H,W,1] masks
+    smooth_gt prepared: full-size masks would be pooled without the smoothing and are refused."""
     if all_rgb is not None:
         raise NotImplementedError("all_rgb: the rgb branch of the reference is dead (point_cloud_to.py:64 AttributeError); "
                                   "colour is a node of its own on the projection: dpc.render.project_rgb / proj_rgb_loss")
     if gt is None:
         raise ValueError("gt (masks [S,1,Hm,Wm], or pooled [S,H,W,1]) is required")
+    if gt.shape[0]:
+        _refuse_full_size_masks(cfg, gt, _grid(cfg)[1] * _grid(cfg)[2], "pointcloud_project_loss")
     _check_live_branches(cfg)
     _validate_point_index(point_index, point_cloud)
     geom = _geometry(cfg, kernel if smooth else None, schedule if smooth else None)
@@ -715,14 +720,26 @@ def point_dropout_indices(num_clouds, num_points, keep_prob, device, generator=N
 # ------------------------------------------------------------------------------------------------------
 # The caller's silhouette loss                       reference: dpc/models/model_pc_to.py:339-385, 410-440
 # ------------------------------------------------------------------------------------------------------
-def silhouette_loss(pred, gt, num_candidates=1, valid_samples=None):
+def _refuse_full_size_masks(cfg, gt, n_pix, where):
+    """cfg.pc_gauss_filter_gt with masks that are not at the silhouette's size yet: they have not been through smooth_gt."""
+    if _get(cfg, "pc_gauss_filter_gt", False) and gt[0].numel() != n_pix:
+        raise NotImplementedError("pc_gauss_filter_gt: true -- %s got full-size masks %s; it pools them but does not smooth "
+                                  "them. Prepare them with dpc.render.smooth_gt(cfg, masks, size, 'masks', ...) and pass the "
+                                  "[S,H,W,1] result (model_pc.py:398-404)" % (where, tuple(gt.shape)))
+
+
+def silhouette_loss(pred, gt, num_candidates=1, valid_samples=None, cfg=None):
     """Projection loss of ModelPointCloud.add_proj_loss, fused with its gradient in one kernel.
 
     pred [S*K,H,W,1] candidate silhouettes; gt the masks [S,1,f*H,f*W] (or [S,f*H,f*W,1]), average-pooled f x f inside the
     kernel like the reference's AvgPool2d (model_pc_to.py:348-369, the same bits), or [S,H,W,1] already pooled;
     valid_samples [S] | None the per-sample weights w (:432-436).  K = 1: sum w^2 (gt-pred)^2 / S.  K > 1
     (proj_loss_pose_candidates): per sample the candidate with the smallest (unweighted) sum of squared differences wins
-    and only winners contribute, w^2-weighted.  Returns (loss, winner [S] int32)."""
+    and only winners contribute, w^2-weighted.  Returns (loss, winner [S] int32).
+    cfg (optional): with cfg.pc_gauss_filter_gt, masks larger than the silhouettes are refused -- the kernel pools, it does
+    not smooth; the smoothed masks come from smooth_gt(cfg, masks, size, "masks", ...) and arrive here as [S,H,W,1]."""
+    if cfg is not None and gt.shape[0] and pred.shape[0]:
+        _refuse_full_size_masks(cfg, gt, pred[0].numel(), "silhouette_loss")
     return SilhouetteLoss.apply(pred, gt, num_candidates, valid_samples)
 
 
@@ -747,7 +764,7 @@ def project_depth(outputs):
     return DepthMap.apply(grid_wh, s, geom)
 
 
-def proj_depth_loss(cfg, outputs, depths, valid_samples=None, return_depth=False):
+def proj_depth_loss(cfg, outputs, depths, valid_samples=None, return_depth=False, gt_prepared=False):
     """add_proj_depth_loss (dpc/util/losses.py:113-136) without its weight: (1/2) sum_s w_s^2 sum_pix (g - depth)^2 / S.
     return_depth: (loss, depth [S,H,W,1] detached) -- the map the loss was formed from, written by the same launch.
 
@@ -756,11 +773,15 @@ def proj_depth_loss(cfg, outputs, depths, valid_samples=None, return_depth=False
     tf.image.resize_images(..., NEAREST_NEIGHBOR), and g = cfg.max_depth where depths == cfg.max_dataset_depth when the two
     differ; valid_samples [S] | None: per-sample weights w, squared like silhouette_loss's (None, the reference: all ones).
     The caller multiplies by cfg.proj_depth_weight.  On the fused path the whole loss is two launches forward and one backward
-    (csrc/dpc_depth.hip); outputs of the staged fallback get the same numbers from outputs["proj_depth"] with torch."""
-    if _get(cfg, "pc_gauss_filter_gt", False):
-        raise NotImplementedError("pc_gauss_filter_gt: true -- smoothing of the ground-truth depth is not implemented "
-                                  "(the reference's torch port prints 'Not implemented' there, dpc/util/losses_to.py)")
+    (csrc/dpc_depth.hip); outputs of the staged fallback get the same numbers from outputs["proj_depth"] with torch.
+    gt_prepared: depths are what smooth_gt(cfg, depths, size, "depths", ...) returned, [S,H,W,1] -- read as they are, the
+    max_dataset_depth remap already done there.  With cfg.pc_gauss_filter_gt and gt_prepared false the call is refused: the
+    loss does not smooth, smooth_gt does."""
+    if not gt_prepared:
+        _refuse_unprepared_gt(cfg, "pc_gauss_filter_gt", "depths", "proj_depth_loss")
     fused = _fused_parts(outputs)
+    if gt_prepared:
+        _prepared_plane(outputs, depths, 1, "depths")
     S = outputs["proj"].shape[0]
     H, W = outputs["proj"].shape[1], outputs["proj"].shape[2]
     plane = _ops_plane(tuple(depths.shape))
@@ -775,7 +796,7 @@ def proj_depth_loss(cfg, outputs, depths, valid_samples=None, return_depth=False
         raise ValueError("depths %dx%d are not an integer multiple of the %dx%d projections" % (Hd, Wd, H, W))
     f = Hd // H
     max_depth = float(_get(cfg, "max_depth", 10.0))
-    mdd = float(_get(cfg, "max_dataset_depth", max_depth))
+    mdd = max_depth if gt_prepared else float(_get(cfg, "max_dataset_depth", max_depth))   # equal: no remap
     if fused is not None:
         geom, grid_wh, s = fused
         loss, depth = DepthLoss.apply(grid_wh, s, depths, f, mdd, valid_samples, geom, bool(return_depth))
@@ -917,7 +938,7 @@ def _image_factor(outputs, images, what):
 
 
 def proj_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None, return_rgb=False, grids=None,
-                  point_index=None):
+                  point_index=None, gt_prepared=False):
     """add_proj_rgb_loss (dpc/util/losses.py:69-90) without its weight: (1/2) sum_s w_s^2 sum_{pix,c} (g - proj_rgb)^2 / S on
     the colour projection of project_rgb.  return_rgb: (loss, proj_rgb [S,H,W,3] detached) -- the image the loss was
     formed from, written by the same launch.
@@ -929,11 +950,14 @@ def proj_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None
     reference's value.  valid_samples [S] | None: per-sample weights w, squared like proj_depth_loss's (None, the reference:
     all ones).  The caller multiplies by cfg.proj_rgb_weight.  Splat and smoothing as in project_rgb; integral, squared
     error and their backward are one column kernel each way (csrc/dpc_rgb.hip).  grids, point_index and
-    cfg.pc_rgb_deterministic (colour sets [S/R,N,3] read in place, |c| <= 8, a bit-reproducible loss): as in project_rgb."""
-    if _get(cfg, "pc_gauss_filter_gt_rgb", False):
-        raise NotImplementedError("pc_gauss_filter_gt_rgb: true -- smoothing of the ground-truth images is not implemented "
-                                  "(gauss_smoothen_image, dpc/util/losses.py:78-83)")
+    cfg.pc_rgb_deterministic (colour sets [S/R,N,3] read in place, |c| <= 8, a bit-reproducible loss): as in project_rgb.
+    gt_prepared: images are what smooth_gt(cfg, images, size, "images", ...) returned, [S,H,W,3] -- read as they are.  With
+    cfg.pc_gauss_filter_gt_rgb and gt_prepared false the call is refused: the loss does not smooth, smooth_gt does."""
+    if not gt_prepared:
+        _refuse_unprepared_gt(cfg, "pc_gauss_filter_gt_rgb", "images", "proj_rgb_loss")
     _rgb_outputs(outputs)
+    if gt_prepared:
+        _prepared_plane(outputs, images, 3, "images")
     planar, f = _image_factor(outputs, images, "colour loss")
     _, clip_after, _, div_eps = _rgb_options(cfg)
     geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel, point_index) if grids is None else grids
@@ -952,7 +976,7 @@ def _check_drc_grid(cfg):
                                   "(dpc/util/losses.py:25, 35)" % (vz, int(cfg.vox_size), vz + 1))
 
 
-def drc_loss(cfg, outputs, masks, valid_samples=None):
+def drc_loss(cfg, outputs, masks, valid_samples=None, gt_prepared=False):
     """add_drc_loss (dpc/util/losses.py:23-29, 49-66) without its weight: sum_s w_s^2 sum_rays ((1 - g) sum_{k<D} p_k + g p_D) / S,
     the ray-consistency cost of the masks under the ray-termination probabilities p of outputs["drc_probs"] -- a ray that
     ends in a voxel pays 1 - g, one that escapes pays g.  No 1/2 and no square.
@@ -964,12 +988,16 @@ def drc_loss(cfg, outputs, masks, valid_samples=None):
     its numbers (f = 1).  valid_samples [S] | None: per-sample weights w, squared like the other losses'.  The caller
     multiplies by cfg.drc_weight.  On the fused path the loss is two launches forward and one backward on the fused node's
     grid (csrc/dpc_drc_loss.hip), a node on (grid_wh, scaling_factor); outputs of the staged fallback get the same numbers
-    from outputs["drc_probs"] with torch."""
-    if _get(cfg, "pc_gauss_filter_gt", False):
-        raise NotImplementedError("pc_gauss_filter_gt: true -- smoothing of the ground-truth masks is not implemented "
-                                  "(the reference's torch port prints 'Not implemented' there, model_pc_to.py:355-356)")
+    from outputs["drc_probs"] with torch.
+    gt_prepared: masks are what smooth_gt(cfg, masks, size, "masks", ...) returned, [S,H,W,1] -- the tensor add_proj_loss
+    stored back into inputs['masks'] -- read as they are.  With cfg.pc_gauss_filter_gt and gt_prepared false the call is
+    refused: the loss does not smooth, smooth_gt does."""
+    if not gt_prepared:
+        _refuse_unprepared_gt(cfg, "pc_gauss_filter_gt", "masks", "drc_loss")
     _check_drc_grid(cfg)
     fused = _fused_parts(outputs)
+    if gt_prepared:
+        _prepared_plane(outputs, masks, 1, "masks")
     S, H, W = outputs["proj"].shape[0], outputs["proj"].shape[1], outputs["proj"].shape[2]
     plane = _ops_plane(tuple(masks.shape))
     if plane is None:
@@ -1014,6 +1042,123 @@ def drc_rgb_loss(cfg, outputs, all_rgb, images, kernel=None, valid_samples=None,
     _, clip_after, _, div_eps = _rgb_options(cfg)
     geom, vox, C, div = _rgb_grids(cfg, outputs, all_rgb, kernel, point_index) if grids is None else grids
     return DrcRgbLoss.apply(vox, C, div, images, f, planar, valid_samples, geom, div_eps, clip_after)
+
+
+# ------------------------------------------------------------------------------------------------------
+# Smoothed ground truth (pc_gauss_filter_gt, pc_gauss_filter_gt_rgb, pc_gauss_filter_gt_switch_off)
+# reference (TF-1 originals): dpc/util/gauss_kernel.py:14-24; dpc/models/model_pc.py:398-404; dpc/util/losses.py:78-83, 128-129
+# ------------------------------------------------------------------------------------------------------
+_GT_KINDS = {"masks": (_native.DPC_GT_RESIZE_MEAN, "pc_gauss_filter_gt"), "images": (_native.DPC_GT_RESIZE_SAMPLE, "pc_gauss_filter_gt_rgb"),
+             "depths": (_native.DPC_GT_RESIZE_SAMPLE, "pc_gauss_filter_gt")}
+
+
+def _smooth_gt_planes(gt, channels, planar, source, size, mode, taps=None, dev_taps=None, ntaps=None, remap=None):
+    """[S,H,W,C] fp32 from ground truth in either layout: the device node, or on CPU tensors the same rule with torch ops."""
+    if gt.is_cuda:
+        return _ops_gt_smooth(gt, channels, planar, source, size, mode, taps, dev_taps, ntaps, remap)
+    if dev_taps is not None:
+        raise RuntimeError("dpc.render.smooth_gt: device taps with ground truth on %s" % gt.device)
+    (Hs, Ws), (H, W), C = source, size, channels
+    S = gt.shape[0]
+    g = gt.detach().to(torch.float32)
+    g = g.reshape(S, C, Hs, Ws) if planar else g.reshape(S, Hs, Ws, C).permute(0, 3, 1, 2)
+    if remap is not None and remap[0] != remap[1]:
+        g = torch.where(g == remap[0], torch.full_like(g, remap[1]), g)
+    f = Hs // H
+    if f > 1:
+        g = torch.nn.functional.avg_pool2d(g, f) if mode == _native.DPC_GT_RESIZE_MEAN else g[:, :, ::f, ::f]
+    w = torch.as_tensor(np.ascontiguousarray(taps, dtype=np.float32).reshape(-1))
+    n = w.numel()
+    if n != 1 or float(w[0]) != 1.0:   # one tap of 1.0: the resized bits as they are
+        g = torch.nn.functional.conv2d(g.contiguous(), w.reshape(1, 1, 1, n).repeat(C, 1, 1, 1), padding=(0, n // 2), groups=C)
+        g = torch.nn.functional.conv2d(g, w.reshape(1, 1, n, 1).repeat(C, 1, 1, 1), padding=(n // 2, 0), groups=C)
+    return g.permute(0, 2, 3, 1).contiguous()
+
+
+def gauss_smoothen_image(cfg, img, sigma_rel):
+    """gauss_smoothen_image of the TF-1 original (dpc/util/gauss_kernel.py:14-24): img [S,H,W,C] (C = 1 or 3) -> [S,H,W,C],
+    every channel convolved with gauss_kernel_1d(cfg.pc_gauss_kernel_size, sigma_rel) along the rows and then along the
+    columns, zero padding ("SAME").  One launch (csrc/dpc_gt_smooth.hip); fp32; no gradient."""
+    shape = tuple(img.shape)
+    if len(shape) != 4 or shape[3] not in (1, 3):
+        raise ValueError("img must be [S,H,W,1] or [S,H,W,3], got %s" % (shape,))
+    taps = gauss_kernel_1d(int(cfg.pc_gauss_kernel_size), sigma_rel).numpy()
+    return _smooth_gt_planes(img, shape[3], False, shape[1:3], shape[1:3], _native.DPC_GT_RESIZE_SAMPLE, taps)
+
+
+def smooth_gt(cfg, gt, size, kind, sigma_rel=None, kernel=None, schedule=None):
+    """The ground truth of one loss, resized to the projection's size and smoothed with the voxels' Gaussian, as ONE node:
+    what cfg.pc_gauss_filter_gt (masks, depths) and cfg.pc_gauss_filter_gt_rgb (images) ask for in the TF-1 original
+    (dpc/models/model_pc.py:398-404; dpc/util/losses.py:78-83, 128-129).  Returns [S,H,W,C] fp32, the layout the reference has
+    after its permute: hand it to silhouette_loss / pointcloud_project_loss as already pooled masks, to proj_depth_loss,
+    proj_rgb_loss and drc_loss with gt_prepared=True.
+
+    size: the projection's (H, W), or an int.  kind and the layouts it takes (those of the loss it feeds):
+      "masks"   [S,1,Hm,Wm], [S,Hm,Wm,1] or [S,Hm,Wm]; resized by the f x f mean of nn.AvgPool2d(f) (silhouette_loss)
+      "images"  [S,Hi,Wi,3] or [S,3,Hi,Wi]; g[y,x] = images[f*y, f*x] (proj_rgb_loss)
+      "depths"  [S,Hd,Wd,1], [S,1,Hd,Wd] or [S,Hd,Wd]; cfg.max_dataset_depth -> cfg.max_depth first where they differ, then
+                g[y,x] = depths[f*y, f*x] (proj_depth_loss)
+    with f = Hm / H = Wm / W an integer >= 1 and source sides <= 1024.  The blur is gauss_smoothen_image's: rows, then
+    columns, zeros outside the plane -- so depth maps darken at the border, as in the reference.
+    The taps come from exactly one of: sigma_rel (gauss_kernel_1d(cfg.pc_gauss_kernel_size, sigma_rel), on the host); kernel
+    (the x/y taps of a smoothing_kernel(...) list); schedule (a DeviceSchedule or DeviceTaps: its taps_xy are read from device
+    memory when the node runs, so a captured graph follows sigma).
+    cfg.pc_gauss_filter_gt_switch_off with sigma_rel < 1.0: the resized ground truth unchanged, for masks and images (depth has
+    no switch-off in the reference).  The switch needs sigma_rel: with kernel= or schedule= the taps are applied as they are,
+    and a caller that honours the switch puts the identity kernel there (DeviceTaps; multiplying finite values by exactly 1
+    and 0 reproduces the resized bits).  No gradient: ground truth needs none.  CPU tensors: the same rule with torch ops."""
+    if kind not in _GT_KINDS:
+        raise ValueError("kind must be 'masks', 'images' or 'depths', got %r" % (kind,))
+    if sum(v is not None for v in (sigma_rel, kernel, schedule)) != 1:
+        raise ValueError("smooth_gt takes its taps from exactly one of sigma_rel, kernel and schedule")
+    mode, _ = _GT_KINDS[kind]
+    H, W = (int(size), int(size)) if isinstance(size, (int, np.integer)) else (int(size[0]), int(size[1]))
+    shape = tuple(gt.shape)
+    if kind == "images":
+        if len(shape) != 4 or (shape[3] != 3 and shape[1] != 3):
+            raise ValueError("images must be [S,Hi,Wi,3] or [S,3,Hi,Wi], got %s" % (shape,))
+        planar, C = shape[3] != 3, 3
+        Hs, Ws = (shape[2], shape[3]) if planar else (shape[1], shape[2])
+    else:
+        plane = _ops_plane(shape)
+        if plane is None:
+            raise ValueError("%s must be [S,1,Hm,Wm], [S,Hm,Wm,1] or [S,Hm,Wm], got %s" % (kind, shape))
+        (Hs, Ws), planar, C = plane, True, 1
+    if H < 1 or W < 1 or Hs < H or Ws < W or Hs % H or Ws % W or Hs // H != Ws // W:
+        raise ValueError("%s %dx%d are not an integer multiple of the %dx%d projections" % (kind, Hs, Ws, H, W))
+    if Hs > 1024 or Ws > 1024:
+        raise ValueError("%s %dx%d: sides above 1024 are not supported" % (kind, Hs, Ws))
+    if shape[0] == 0:
+        return torch.zeros((0, H, W, C), dtype=torch.float32, device=gt.device)
+    remap = None
+    if kind == "depths":
+        max_depth = float(_get(cfg, "max_depth", 10.0))
+        remap = (float(_get(cfg, "max_dataset_depth", max_depth)), max_depth)
+    taps = dev_taps = ntaps = None
+    if schedule is not None:
+        dev_taps, ntaps = schedule.taps_xy, int(schedule.sizes[0])
+    elif kernel is not None:
+        taps = _kernel_taps(cfg, kernel)[0]
+    else:
+        taps = gauss_kernel_1d(int(cfg.pc_gauss_kernel_size), sigma_rel).numpy()
+        if kind != "depths" and _get(cfg, "pc_gauss_filter_gt_switch_off", False) and sigma_rel < 1.0:
+            taps = np.ones(1, dtype=np.float32)   # tf.where(tf.less(sigma_rel, 1.0), gt, smoothed)
+    return _smooth_gt_planes(gt, C, planar, (Hs, Ws), (H, W), mode, taps, dev_taps, ntaps, remap)
+
+
+def _refuse_unprepared_gt(cfg, key, what, where):
+    if _get(cfg, key, False):
+        raise NotImplementedError("%s: true -- %s takes the smoothed ground truth %s from dpc.render.smooth_gt, with "
+                                  "gt_prepared=True; it does not smooth inside the loss (gauss_smoothen_image, %s)"
+                                  % (key, where, what, "dpc/util/losses.py:78-83, 128-129; dpc/models/model_pc.py:398-404"))
+
+
+def _prepared_plane(outputs, gt, channels, what):
+    """Ground truth from smooth_gt against the projection: [S,H,W,C] exactly."""
+    S, H, W = outputs["proj"].shape[0], outputs["proj"].shape[1], outputs["proj"].shape[2]
+    if tuple(gt.shape) != (S, H, W, channels):
+        raise ValueError("gt_prepared: %s must be what smooth_gt returned for this projection, [%d,%d,%d,%d], got %s"
+                         % (what, S, H, W, channels, tuple(gt.shape)))
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -36,6 +36,7 @@ DPC_VOXEL_MAX_SIDE = 128
 DPC_MESH_FILL_NONE, DPC_MESH_FILL_CARVE, DPC_MESH_FILL_PARITY = 0, 1, 2
 DPC_GAUSS_NORM_NONE, DPC_GAUSS_NORM_ANALYTICAL, DPC_GAUSS_NORM_PER_POINT = 0, 1, 2
 DPC_GAUSS_MAX_SIDE = 64
+DPC_GT_RESIZE_MEAN, DPC_GT_RESIZE_SAMPLE = 0, 1
 DPC_MESH_NEAR = 1e-3
 DPC_MESH_AMBIENT, DPC_MESH_DIFFUSE = 0.25, 0.75
 
@@ -76,6 +77,7 @@ _FUNCTIONS = (
     ("dpc_silhouette_loss", _i, [_vp, _i, _vp, _vp] + [_i] * 4 + [_vp, _vp, _vp, _vp]),
     ("dpc_gauss_voxels_fwd", _i, [_pp, _vp, _d, _i, _vp, _vp, _vp]),
     ("dpc_gauss_voxels_bwd", _i, [_pp, _vp, _d, _i, _vp, _vp, _vp, _vp]),
+    ("dpc_gt_smooth", _i, [_vp] + [_i] * 8 + [ctypes.c_float] * 2 + [_vp, _vp, _i, _vp, _vp]),
     ("dpc_depth_workspace_bytes", _sz, [_pp]),
     ("dpc_depth_loss_fwd", _i, [_pp] + [_vp] * 4 + [_i, ctypes.c_float] + [_vp] * 5),
     ("dpc_depth_loss_bwd", _i, [_pp] + [_vp] * 4 + [_i, ctypes.c_float] + [_vp] * 7),

@@ -162,6 +162,56 @@ class DeviceSchedule:
         N.check(rc, "dpc_schedule_update")
 
 
+class DeviceTaps:
+    """One 1-D kernel in DEVICE memory for dpc.render.smooth_gt(schedule=...): the part of a DeviceSchedule the ground-truth
+    node reads (`taps_xy`, `sizes`), with no compiled tap window to fit -- the node takes any values of the same length.
+    A captured training step keeps one of these for the ground truth next to the projection's DeviceSchedule, so that
+    cfg.pc_gauss_filter_gt_switch_off can put the identity kernel there while sigma_rel < 1 without touching the taps the
+    projection reads.  update() is one tiny launch on the current stream; enqueue it in front of a replay."""
+
+    def __init__(self, device, kxy):
+        kxy = np.ascontiguousarray(kxy, dtype=np.float32).reshape(-1)
+        if kxy.size % 2 == 0 or kxy.size > N.DPC_MAX_TAPS:
+            raise ValueError("smoothing kernels must have odd length <= %d, got %d" % (N.DPC_MAX_TAPS, kxy.size))
+        self.device = torch.device(device)
+        self.taps_xy = torch.zeros(N.DPC_MAX_TAPS, dtype=torch.float32, device=device)
+        self.sizes = (kxy.size, 0)
+        self.update(kxy)
+
+    def update(self, kxy):
+        kxy = np.ascontiguousarray(kxy, dtype=np.float32).reshape(-1)
+        if kxy.size != self.sizes[0]:
+            raise ValueError("the tap buffer was built for a kernel of %d taps, got %d" % (self.sizes[0], kxy.size))
+        with torch.cuda.device(self.device):
+            rc = N.lib().dpc_schedule_update(kxy.ctypes.data_as(ctypes.c_void_p), kxy.size, None, 0, 0, N.ptr(self.taps_xy),
+                                             None, None, N.stream_ptr(self.device))
+        N.check(rc, "dpc_schedule_update")
+
+
+def gt_smooth(gt, channels, planar, source, size, mode, taps=None, dev_taps=None, ntaps=None, remap=None):
+    """dpc_gt_smooth (csrc/dpc_gt_smooth.hip): gt, S samples of `channels` channels of source = (Hs, Ws) = (f*H, f*W) values
+    ([S,C,Hs,Ws] when planar, else [S,Hs,Ws,C]; fp32 after conversion), size (H, W) -> [S,H,W,C] fp32: remap (remap = (from, to) | None),
+    resize by f (mode DPC_GT_RESIZE_MEAN / _SAMPLE), two-pass zero-padded blur.  Taps: a host array `taps`, or `dev_taps`
+    (a device tensor read by the kernel at run time) with its length `ntaps`.  One launch, no gradient."""
+    dev = N.require_device(gt, dev_taps)
+    (Hs, Ws), (H, W) = (int(v) for v in source), (int(v) for v in size)
+    g32 = _f32(gt)
+    S, C = g32.shape[0], int(channels)
+    if S * C * Hs * Ws != g32.numel():
+        raise ValueError("ground truth %s does not hold %d x %d planes of %dx%d" % (tuple(gt.shape), S, C, Hs, Ws))
+    host = None
+    if dev_taps is None:
+        host = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        ntaps = host.size
+    elif dev_taps.dtype is not torch.float32 or dev_taps.numel() < int(ntaps):
+        raise ValueError("dev_taps must hold %d fp32 values" % int(ntaps))
+    lo, hi = (0.0, 0.0) if remap is None else (float(remap[0]), float(remap[1]))
+    out = torch.empty((S, H, W, C), dtype=torch.float32, device=dev)
+    _call(dev, "dpc_gt_smooth", _dp(g32), S, C, Hs, Ws, int(bool(planar)), H, W, int(mode), lo, hi,
+          None if host is None else host.ctypes.data, _dp(dev_taps), int(ntaps), _dp(out))
+    return out
+
+
 def taps_bucket(k):
     """Compiled tap-window radius a 1-D kernel needs in the fused kernels (-1: beyond them)."""
     k = np.ascontiguousarray(k, dtype=np.float32).reshape(-1)
