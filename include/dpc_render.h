@@ -56,6 +56,11 @@ extern "C" {
 #define DPC_MESH_FILL_CARVE 1
 #define DPC_MESH_FILL_PARITY 2
 #define DPC_MESH_VOXEL_MAX_COORD 18446744073709551616.0 /* 2^64 */
+/* dpc_point_mesh_distance: the points of a workgroup (one lane each), the faces it stages in LDS per round, and the least
+ * number of such tiles in a chunk of faces when a row's face range is split over workgroups. */
+#define DPC_PM_BLOCK 256
+#define DPC_PM_FACE_TILE 128
+#define DPC_PM_CHUNK_TILES 8
 
 enum {
   DPC_OK = 0,
@@ -896,6 +901,56 @@ int dpc_voxelise_meshes(const void* verts, int n_verts, int is_f64, const int32_
                         const int32_t* host_mesh_desc, int meshes, int D, int H, int W, int fill, uint32_t* bits, uint32_t* scratch,
                         int32_t* info, int32_t* status, void* stream);
 int dpc_voxel_carve(const uint32_t* bits, int B, int D, int H, int W, uint32_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Exact point-to-mesh distance: for n_pairs rows (a range of points, a mesh) in one call, the squared Euclidean distance
+ * from every point to the nearest point of the union of the row's closed triangles.  The evaluation measures its
+ * distances against sampled ground truth, whose spacing is a floor under every distance; this measures against the
+ * surface itself.  There is no counterpart in the reference: the rules below are this library's own,
+ * tests/point_mesh_oracle.py restates them in numpy and in exact rational arithmetic.  All arithmetic is fp64 (fp32
+ * points and vertices widen exactly first); products and sums may be fused, so a value is right to a few units of
+ * 2^-52 S^2, S the largest coordinate magnitude of the row, not to the bit (tests/golden/f28_point_mesh.npz records the
+ * bound the tests use).
+ *
+ * Distance to one face (A, B, C), vertices rotated so that the longest edge lies opposite A:
+ *   E0 = B - A, E1 = C - A, E2 = C - B, N = E0 x E1, D = P - A;
+ *   (s, t) = the barycentric coordinates of the plane foot point, ((E1.E1) (D.E0) - (E0.E1) (D.E1)) / N.N and
+ *   ((E0.E0) (D.E1) - (E0.E1) (D.E0)) / N.N; N.N is the determinant (E0.E0)(E1.E1) - (E0.E1)^2, formed as the squared
+ *   length of the cross product; the foot point is inside when N.N > 0, s >= 0, t >= 0 and s + t <= 1, and then
+ *   d2 = (D.N)^2 / N.N; otherwise d2 = the least of the three squared distances to the segments AB, AC, BC, each
+ *   |R - clamp(R.E / E.E, 0, 1) E|^2 from its first endpoint.
+ * Zero-area faces.  A face with two or three coincident vertices, or three collinear ones, is the segment or the point
+ *   it degenerates to: the inside test is false when N.N is not > 0 (nothing is divided by it then), and a segment of
+ *   zero length takes the parameter 0 (nothing is divided by its length), i.e. it is its first endpoint.
+ * Guards.  A face with a vertex that is NaN, infinite or >= DPC_MESH_VOXEL_MAX_COORD in magnitude is skipped and sets
+ *   DPC_STATUS_NONFINITE, as in dpc_voxelise_meshes; a face with an index outside [0, vertex_count of its row) is skipped
+ *   and sets DPC_STATUS_BAD_INDEX: it never becomes an address.  A row whose faces are all skipped gives +inf for its
+ *   points.  A point with such a coordinate gets +inf and sets DPC_STATUS_NONFINITE.  A device-table row that does not
+ *   lie inside points / verts / faces sets DPC_STATUS_BAD_INDEX and nothing of it is read or written.
+ * Arguments:
+ *   points [n_points,3] fp32 (points_f64 = 0) or fp64; verts [n_verts,3] fp32 (verts_f64 = 0) or fp64, independently;
+ *   faces [n_faces,3] int32, indices local to the vertex range of their row; pair_desc / host_pair_desc [n_pairs,6]
+ *   int32 rows (point_start, point_count, vertex_start, vertex_count, face_start, face_count), DEVICE / HOST, the same
+ *   values; several rows may name the same vertex and face ranges (the views of one model share one mesh copy);
+ *   d2 [sum point_count] fp64, the rows' points in row order: a row with point_count == 0 writes nothing; workspace
+ *   dpc_point_mesh_workspace_bytes(n_pairs) bytes (two int32 prefixes; 0 for n_pairs <= 0); status DEVICE int32, zeroed
+ *   by the caller, NULL allowed.
+ * Kernels (csrc/dpc_point_mesh.hip): a lane owns a point, a workgroup of DPC_PM_BLOCK lanes stages DPC_PM_FACE_TILE
+ *   faces per round in LDS (the per-face terms above are formed once per face there) and every lane walks the tile.  A
+ *   call whose point blocks alone would not fill the device splits the face ranges into chunks of whole tiles, at least
+ *   DPC_PM_CHUNK_TILES each, over several workgroups; d2 is pre-filled with +inf and every workgroup folds its lanes'
+ *   minima in with a 64-bit unsigned atomic min (a non-negative double orders like its bit pattern).  min is exact and
+ *   order-free: the result is the same bit for bit however the rows are ordered, batched or split.
+ * Every check runs before any launch (DPC_ERR_SHAPE: a negative size, a table row outside its array, face_count == 0 for
+ * a row with points, more than 2^31 - 1 output points or work items); valid arguments with NULL device pointers return
+ * DPC_ERR_NULL without touching a device; no rows or no points return DPC_OK with nothing launched.  No host
+ * synchronisation, no allocation, no floating-point atomics.  Added without a new ABI number: no existing entry point
+ * changed.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_point_mesh_workspace_bytes(int n_pairs);
+int dpc_point_mesh_distance(const void* points, int n_points, int points_f64, const void* verts, int n_verts, int verts_f64,
+                            const int32_t* faces, int n_faces, const int32_t* pair_desc, const int32_t* host_pair_desc, int n_pairs,
+                            double* d2, void* workspace, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Voxel-grid downsampling of ground-truth clouds (densify/downsample_gt.py:47-57: open3d.voxel_down_sample(pcd,

@@ -34,6 +34,7 @@ DPC_EMD_MAX_POINTS = 2048
 DPC_FPS_MAX_POINTS = 16384
 DPC_VOXEL_MAX_SIDE = 128
 DPC_MESH_FILL_NONE, DPC_MESH_FILL_CARVE, DPC_MESH_FILL_PARITY = 0, 1, 2
+DPC_PM_BLOCK, DPC_PM_FACE_TILE, DPC_PM_CHUNK_TILES = 256, 128, 8
 DPC_GAUSS_NORM_NONE, DPC_GAUSS_NORM_ANALYTICAL, DPC_GAUSS_NORM_PER_POINT = 0, 1, 2
 DPC_GAUSS_MAX_SIDE = 64
 DPC_GT_RESIZE_MEAN, DPC_GT_RESIZE_SAMPLE = 0, 1
@@ -119,6 +120,8 @@ _FUNCTIONS = (
     ("dpc_voxel2pc", _i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     ("dpc_voxelise_meshes", _i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     ("dpc_voxel_carve", _i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    ("dpc_point_mesh_workspace_bytes", _sz, [_i]),
+    ("dpc_point_mesh_distance", _i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("dpc_downsample_workspace_bytes", _sz, [_i, _i]),
     ("dpc_voxel_downsample", _i, [_vp, _i, _i, _vp, _vp, _i, _d] + [_vp] * 6),
     ("dpc_densify_workspace_bytes", _sz, [_i, _i64, _i64, _i64, _i]),
