@@ -13,6 +13,8 @@ Differences from the reference, all deliberate (SURVEY.md section 8a "quirks"):
   * no `print` in the hot path; a point exactly on the +1/2 face contributes its in-range corners instead of
     raising IndexError.
 """
+import os as _os
+
 import numpy as np
 import torch
 
@@ -125,8 +127,6 @@ def _geometry(cfg, kernel=None, schedule=None):
 # ------------------------------------------------------------------------------------------------------
 # Bad point indices: an error, never a GPU fault         reference: fancy indexing raises IndexError
 # ------------------------------------------------------------------------------------------------------
-import os as _os
-
 _debug_checks = _os.environ.get("DPC_RENDER_DEBUG", "0") not in ("", "0")
 
 
@@ -677,12 +677,10 @@ def prefer_direct_graph_launch():
     (the four-kernel fwd+bwd step: 61.2 -> 57.2 us).  The runtime reads the setting once, when HIP initialises, so this
     must run before the first CUDA call of the process (importing torch is fine); an explicit
     DEBUG_CLR_GRAPH_PACKET_CAPTURE in the environment wins.  Returns True when the setting is in force for this process."""
-    import os
-
     if not torch.cuda.is_initialized():
-        os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
+        _os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
     # once HIP is up the runtime has read the variable: what the process started with stays
-    return os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE") == "0"
+    return _os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE") == "0"
 
 
 def point_dropout_indices(num_clouds, num_points, keep_prob, device, generator=None, n_live=None):
@@ -712,10 +710,8 @@ def point_dropout_indices(num_clouds, num_points, keep_prob, device, generator=N
     out = torch.empty((num_clouds, keep), dtype=torch.int32, device=device)
     if n_live is not None:
         out.zero_()   # slots beyond the live count are never read by the kernels; zeros keep a debug range check quiet
-    with torch.cuda.device(device):
-        rc = N.lib().dpc_point_dropout_indices_live(int(num_clouds), int(num_points), keep, N.ptr(n_live), N.ptr(seed),
-                                                    N.ptr(out), N.stream_ptr(device))
-    N.check(rc, "dpc_point_dropout_indices_live")
+    N.call(device, "dpc_point_dropout_indices_live", int(num_clouds), int(num_points), keep, N.ptr(n_live), N.ptr(seed),
+           N.ptr(out))
     return out
 
 
@@ -1207,16 +1203,13 @@ def point_cloud_distance(Vs, Vt):
         vt = Vt.to(dtype)
         _, dist, idx = nearest_batched(torch.cat([vt, Vs.to(dtype)]), [[nt, ns, 0, nt]], return_distances=True)
         return vt[idx], dist, idx
-    L = _native.lib()
     is64 = int(dtype == torch.float64)
     proj = torch.empty((ns, 3), dtype=dtype, device=dev)
     dist = torch.empty((ns,), dtype=dtype, device=dev)
     idx = torch.empty((ns,), dtype=torch.int64, device=dev)
-    ws = torch.empty((max(L.dpc_nearest_workspace_bytes(ns, nt, is64), 16),), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.dpc_point_cloud_distance(_native.ptr(vs), _native.ptr(vt), ns, nt, is64, _native.ptr(proj), _native.ptr(dist),
-                                        _native.ptr(idx), _native.ptr(ws), _native.stream_ptr(dev))
-    _native.check(rc, "dpc_point_cloud_distance")
+    ws = torch.empty((max(_native.lib().dpc_nearest_workspace_bytes(ns, nt, is64), 16),), dtype=torch.uint8, device=dev)
+    _native.call(dev, "dpc_point_cloud_distance", _native.ptr(vs), _native.ptr(vt), ns, nt, is64, _native.ptr(proj),
+                 _native.ptr(dist), _native.ptr(idx), _native.ptr(ws))
     return proj, dist, idx
 
 

@@ -1,8 +1,10 @@
-"""Ragged-batch plumbing shared by the fp64 evaluation pipelines (alignment, chamfer, downsample, densify).
+"""Ragged-batch plumbing shared by the evaluation pipelines (alignment, chamfer, downsample, densify, emd, sampling, voxels,
+meshvoxels, pointmesh, visualise, meshviews).
 
-Each packs its items (clouds, pairs of clouds, meshes) into one buffer, describes them in a host int32 table, asks the
-library's own argument checks before anything touches a device (a dry run with NULL device pointers), allocates the
-workspace the library asks for, and turns the status bits of a job into exceptions.
+Each packs its items (clouds, pairs of clouds, meshes) into one buffer in the widest dtype among them, describes them in a
+host int32 table that also goes to the device, asks the library's own argument checks before anything touches a device (a
+dry run with NULL device pointers), allocates the workspace the library asks for, and turns the status bits of a job into
+exceptions.
 """
 import numpy as np
 import torch
@@ -36,6 +38,20 @@ def cloud(x, what, cast=torch.float32):
     return t.detach()
 
 
+def refuse_cpu(*groups):
+    """Arrays are copied to the device; a CPU tensor is refused, as everywhere in the package.  groups: clouds arguments
+    as the caller gave them, each a tensor or a list of tensors and arrays (one device per group)."""
+    for group in groups:
+        _native.require_device(*[c for c in ([group] if isinstance(group, torch.Tensor) else group)
+                                 if isinstance(c, torch.Tensor)])
+
+
+def widest(tensors):
+    """float64 when one of the tensors is, else float32: the kernels compute in fp64 and fp32 widens exactly, so one fp64
+    item makes the whole call fp64 without changing a result."""
+    return torch.float64 if any(t.dtype == torch.float64 for t in tensors) else torch.float32
+
+
 def pack(clouds, dev, dtype):
     """The clouds ([n_i,3] float32 / float64 tensors, at least one float64 when dtype is) in one contiguous
     [sum n_i, 3] tensor of dtype on dev, and the start of each.  Host clouds are joined by numpy (torch.cat of large host
@@ -54,6 +70,11 @@ def table(rows, width, message):
     if desc.size and (desc.min() < np.iinfo(np.int32).min or desc.max() > INT32_MAX):
         raise ValueError(message)
     return np.ascontiguousarray(desc, dtype=np.int32)
+
+
+def on_device(desc, dev):
+    """The device copy of a host table; the entry points take both (the host one as desc.ctypes.data)."""
+    return torch.from_numpy(desc).to(dev)
 
 
 def dry_run(rc, message, exc=ValueError):

@@ -183,20 +183,52 @@ def check(code, where):
 
 
 def ptr(t):
-    """Device pointer of a tensor (None -> NULL)."""
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+    """Address of a tensor as a plain int (None -> NULL): the argtypes of the bindings turn it into a void*."""
+    return None if t is None else t.data_ptr()
 
 
-def host_floats(arr):
-    """float32 host array -> (ctypes pointer, keep-alive)."""
-    import numpy as np
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
-    a = np.ascontiguousarray(arr, dtype=np.float32)
-    return a.ctypes.data_as(ctypes.c_void_p), a
+
+def stream(dev):
+    """torch's current HIP stream of `dev` as an address (the raw getter skips building a Stream object per call)."""
+    if _raw_stream is not None:
+        return _raw_stream(dev.index if dev.index is not None else torch.cuda.current_device())
+    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def stream_ptr(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    """stream() for a device given as a torch.device or a string."""
+    return stream(torch.device(device))
+
+
+class on:
+    """`with torch.cuda.device(dev)` only when `dev` is not the current device already (the guard costs ~10 us of host time
+    per call; a training process sits on its one device)."""
+
+    __slots__ = ("guard",)
+
+    def __init__(self, dev):
+        self.guard = None if (dev.index is None or dev.index == torch.cuda.current_device()) else torch.cuda.device(dev)
+
+    def __enter__(self):
+        if self.guard is not None:
+            self.guard.__enter__()
+
+    def __exit__(self, *exc):
+        if self.guard is not None:
+            return self.guard.__exit__(*exc)
+        return False
+
+
+def call(dev, entry, *args):
+    """One entry point of the library on `dev` and its current stream (every entry's last argument); raises DpcError on a
+    return code.  The only way the package invokes an entry that takes a stream: the work goes to the current stream of
+    the tensors' device and no return code is dropped."""
+    with on(dev):
+        rc = getattr(lib(), entry)(*args, stream(dev))
+    if rc != 0:
+        raise DpcError(rc, entry)
 
 
 def require_device(*tensors):

@@ -155,11 +155,8 @@ class DeviceSchedule:
             raise ValueError("schedule values do not fit what the schedule was built for: tap windows %s (needed %s), capacity %s "
                              "(n_live %s) -- build a new DeviceSchedule (and capture again)"
                              % (self.buckets, (taps_bucket(kxy), taps_bucket(kz)), self.capacity, n_live))
-        with torch.cuda.device(self.device):
-            rc = N.lib().dpc_schedule_update(kxy.ctypes.data_as(ctypes.c_void_p), kxy.size, kz.ctypes.data_as(ctypes.c_void_p),
-                                             kz.size, 0 if n_live is None else int(n_live), N.ptr(self.taps_xy),
-                                             N.ptr(self.taps_z), N.ptr(self.n_live), N.stream_ptr(self.device))
-        N.check(rc, "dpc_schedule_update")
+        N.call(self.device, "dpc_schedule_update", kxy.ctypes.data, kxy.size, kz.ctypes.data, kz.size,
+               0 if n_live is None else int(n_live), N.ptr(self.taps_xy), N.ptr(self.taps_z), N.ptr(self.n_live))
 
 
 class DeviceTaps:
@@ -182,10 +179,7 @@ class DeviceTaps:
         kxy = np.ascontiguousarray(kxy, dtype=np.float32).reshape(-1)
         if kxy.size != self.sizes[0]:
             raise ValueError("the tap buffer was built for a kernel of %d taps, got %d" % (self.sizes[0], kxy.size))
-        with torch.cuda.device(self.device):
-            rc = N.lib().dpc_schedule_update(kxy.ctypes.data_as(ctypes.c_void_p), kxy.size, None, 0, 0, N.ptr(self.taps_xy),
-                                             None, None, N.stream_ptr(self.device))
-        N.check(rc, "dpc_schedule_update")
+        N.call(self.device, "dpc_schedule_update", kxy.ctypes.data, kxy.size, None, 0, 0, N.ptr(self.taps_xy), None, None)
 
 
 def gt_smooth(gt, channels, planar, source, size, mode, taps=None, dev_taps=None, ntaps=None, remap=None):
@@ -207,15 +201,15 @@ def gt_smooth(gt, channels, planar, source, size, mode, taps=None, dev_taps=None
         raise ValueError("dev_taps must hold %d fp32 values" % int(ntaps))
     lo, hi = (0.0, 0.0) if remap is None else (float(remap[0]), float(remap[1]))
     out = torch.empty((S, H, W, C), dtype=torch.float32, device=dev)
-    _call(dev, "dpc_gt_smooth", _dp(g32), S, C, Hs, Ws, int(bool(planar)), H, W, int(mode), lo, hi,
-          None if host is None else host.ctypes.data, _dp(dev_taps), int(ntaps), _dp(out))
+    N.call(dev, "dpc_gt_smooth", N.ptr(g32), S, C, Hs, Ws, int(bool(planar)), H, W, int(mode), lo, hi,
+          None if host is None else host.ctypes.data, N.ptr(dev_taps), int(ntaps), N.ptr(out))
     return out
 
 
 def taps_bucket(k):
     """Compiled tap-window radius a 1-D kernel needs in the fused kernels (-1: beyond them)."""
     k = np.ascontiguousarray(k, dtype=np.float32).reshape(-1)
-    return N.lib().dpc_taps_bucket(k.ctypes.data_as(ctypes.c_void_p), k.size)
+    return N.lib().dpc_taps_bucket(k.ctypes.data, k.size)
 
 
 def _f32(t):
@@ -224,40 +218,6 @@ def _f32(t):
     if t.dtype is torch.float32 and t.is_contiguous():
         return t.detach()
     return t.detach().to(torch.float32).contiguous()
-
-
-def _dp(t):
-    """Device address of a tensor as a plain int (None -> NULL): the bindings' argtypes turn it into a void*."""
-    return None if t is None else t.data_ptr()
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream(dev):
-    """torch's current HIP stream of `dev` as an address (the raw getter skips building a Stream object per call)."""
-    if _raw_stream is not None:
-        return _raw_stream(dev.index if dev.index is not None else torch.cuda.current_device())
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-class _on:
-    """`with torch.cuda.device(dev)` only when `dev` is not the current device already (the guard costs ~10 us of host time
-    per call; a training process sits on its one device)."""
-
-    __slots__ = ("guard",)
-
-    def __init__(self, dev):
-        self.guard = None if (dev.index is None or dev.index == torch.cuda.current_device()) else torch.cuda.device(dev)
-
-    def __enter__(self):
-        if self.guard is not None:
-            self.guard.__enter__()
-
-    def __exit__(self, *exc):
-        if self.guard is not None:
-            return self.guard.__exit__(*exc)
-        return False
 
 
 def _replicas(pc, q):
@@ -354,6 +314,15 @@ def _zero_grads(metas, dev):
     return tuple(None if m is None else torch.zeros(m[1], dtype=m[0], device=dev) for m in metas)
 
 
+def _pose_grads(metas, has, dpc, dsmall, B, nones):
+    """What the backward of a node with inputs (pc, q, t, f[, s], ...) returns: d pc and the blocks of the small-gradient
+    buffer, each like its input (`metas`); `has`: which of t, f[, s] were given; then `nones` Nones for the other arguments."""
+    grads = [_like_input(dpc, metas[0]), _like_input(_small(dsmall, N.COL_DQ, 4, B), metas[1])]
+    for meta, present, (col, width) in zip(metas[2:], has, ((N.COL_DT, 3), (N.COL_DF, 1), (N.COL_DS, 1))):
+        grads.append(_like_input(_small(dsmall, col, width, B), meta) if present else None)
+    return tuple(grads) + (None,) * nones
+
+
 def _new_cells(P, dev):
     return torch.empty((max(N.lib().dpc_cells_bytes(ctypes.byref(P)), 1),), dtype=torch.uint8, device=dev)
 
@@ -393,10 +362,7 @@ def locate_points(pc, q, t, f, geom):
     P = geom.params(B, Npts)
     tr = torch.empty_like(pc32)
     cells = _new_cells(P, dev)
-    with torch.cuda.device(dev):
-        rc = N.lib().dpc_locate(ctypes.byref(P), N.ptr(pc32), N.ptr(q32), N.ptr(t32), N.ptr(f32), N.ptr(tr), N.ptr(cells),
-                                N.stream_ptr(dev))
-    N.check(rc, "dpc_locate")
+    N.call(dev, "dpc_locate", ctypes.byref(P), N.ptr(pc32), N.ptr(q32), N.ptr(t32), N.ptr(f32), N.ptr(tr), N.ptr(cells))
     return tr, cells
 
 
@@ -416,7 +382,6 @@ class ProjectFused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pc, q, t, f, s, geom, point_index=None, want_grad=False):
         dev = N.require_device(pc, q, t, f, s)
-        L = N.lib()
         pc32, q32, t32, f32, s32 = _f32(pc), _f32(q), _f32(t), _f32(f), _f32(s)
         idx = _index32(point_index, pc32, q32)
         B, reps = q32.shape[0], _replicas(pc32, q32)
@@ -431,11 +396,8 @@ class ProjectFused(torch.autograd.Function):
         proj = torch.empty((B, geom.H, geom.W, 1), dtype=torch.float32, device=dev)
         trans = torch.empty((B, geom.H, geom.W), dtype=torch.float32, device=dev)
         kxy, kz = geom.kern_ptrs()
-        with _on(dev):
-            rc = L.dpc_project_fwd(Z.ref, _dp(pc32), _dp(q32), _dp(t32), _dp(f32), _dp(s32), kxy, kz,
-                                   None, _dp(cells), None, _dp(grid_wh), None, _dp(mask), _dp(proj), _dp(trans), _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_project_fwd")
+        N.call(dev, "dpc_project_fwd", Z.ref, N.ptr(pc32), N.ptr(q32), N.ptr(t32), N.ptr(f32), N.ptr(s32), kxy, kz,
+               None, N.ptr(cells), None, N.ptr(grid_wh), None, N.ptr(mask), N.ptr(proj), N.ptr(trans))
         ctx.geom = geom
         ctx.inputs = tuple(_meta(x) for x in (pc, q, t, f, s))
         empty = pc32.new_empty(0)
@@ -457,7 +419,6 @@ class ProjectFused(torch.autograd.Function):
         s32 = s32 if has_s else None
         geom = ctx.geom
         dev = pc32.device
-        L = N.lib()
         B, reps = q32.shape[0], _replicas(pc32, q32)
         Z = geom.sized(B, ctx.npts, reps, cells if ctx.indexed else None, pc32.shape[1])  # the backward reads the source
         # index out of the binned records; any non-NULL pointer says "dpc is per stored set, accumulate"
@@ -467,17 +428,10 @@ class ProjectFused(torch.autograd.Function):
         dsmall = torch.empty((N.DPC_SMALL_COLS * B,), dtype=torch.float32, device=dev)
         ws = torch.empty((Z.ws_bytes,), dtype=torch.uint8, device=dev)
         kxy, kz = geom.kern_ptrs()
-        with _on(dev):
-            rc = L.dpc_project_bwd(Z.ref, _dp(pc32), _dp(q32), _dp(t32), _dp(f32), _dp(s32), kxy, kz,
-                                   _dp(cells), _dp(grid_wh), _dp(mask), _dp(trans), _dp(dproj32), _dp(dgrid32),
-                                   _dp(dpc), _dp(dsmall), _dp(ws), _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_project_bwd")
-        pc, q, t, f, s = ctx.inputs
-        return (_like_input(dpc, pc), _like_input(_small(dsmall, N.COL_DQ, 4, B), q),
-                _like_input(_small(dsmall, N.COL_DT, 3, B), t) if has_t else None,
-                _like_input(_small(dsmall, N.COL_DF, 1, B), f) if has_f else None,
-                _like_input(_small(dsmall, N.COL_DS, 1, B), s) if has_s else None, None, None, None)
+        N.call(dev, "dpc_project_bwd", Z.ref, N.ptr(pc32), N.ptr(q32), N.ptr(t32), N.ptr(f32), N.ptr(s32), kxy, kz,
+               N.ptr(cells), N.ptr(grid_wh), N.ptr(mask), N.ptr(trans), N.ptr(dproj32), N.ptr(dgrid32),
+               N.ptr(dpc), N.ptr(dsmall), N.ptr(ws))
+        return _pose_grads(ctx.inputs, ctx.has, dpc, dsmall, B, 3)
 
 
 class ProjectLossFused(torch.autograd.Function):
@@ -506,7 +460,6 @@ class ProjectLossFused(torch.autograd.Function):
         if weights is not None and tuple(weights.shape) != (S,):
             raise ValueError("valid_samples must be [%d] (one weight per sample), got %s" % (S, tuple(weights.shape)))
         dev = N.require_device(pc, q, t, f, s, gt, weights)
-        L = N.lib()
         pc32, q32, t32, f32, s32, gt32 = _f32(pc), _f32(q), _f32(t), _f32(f), _f32(s), _f32(gt)
         w32 = _weights32(weights, S)
         idx = _index32(point_index, pc32, q32)
@@ -540,13 +493,10 @@ class ProjectLossFused(torch.autograd.Function):
             dsmall = f32e(N.DPC_SMALL_COLS * B)
         fused = ctypes.c_int(0)
         kxy, kz = geom.kern_ptrs()
-        with _on(dev):
-            rc = L.dpc_project_loss_fwd(Z.ref, _dp(pc32), _dp(q32), _dp(t32), _dp(f32), _dp(s32), kxy, kz,
-                                        _dp(gt32), gf, _dp(w32), K, None, _dp(cells), _dp(grid_wh), _dp(mask), _dp(proj),
-                                        _dp(trans), _dp(sse), _dp(sse_tiles), _dp(loss), _dp(winner), _dp(ws), _dp(dsmall),
-                                        ctypes.byref(fused), _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_project_loss_fwd")
+        N.call(dev, "dpc_project_loss_fwd", Z.ref, N.ptr(pc32), N.ptr(q32), N.ptr(t32), N.ptr(f32), N.ptr(s32), kxy, kz,
+               N.ptr(gt32), gf, N.ptr(w32), K, None, N.ptr(cells), N.ptr(grid_wh), N.ptr(mask), N.ptr(proj),
+               N.ptr(trans), N.ptr(sse), N.ptr(sse_tiles), N.ptr(loss), N.ptr(winner), N.ptr(ws), N.ptr(dsmall),
+               ctypes.byref(fused))
         ctx.geom, ctx.K, ctx.fused, ctx.gf, ctx.weighted = geom, K, bool(fused.value), gf, w32 is not None
         ctx.inputs = tuple(_meta(x) for x in (pc, q, t, f, s))
         empty = pc32.new_empty(0)
@@ -569,7 +519,7 @@ class ProjectLossFused(torch.autograd.Function):
         w32 = w32 if ctx.weighted else None
         has_t, has_f, has_s = ctx.has
         t32, f32, s32 = (t32 if has_t else None), (f32 if has_f else None), (s32 if has_s else None)
-        geom, dev, L = ctx.geom, pc32.device, N.lib()
+        geom, dev = ctx.geom, pc32.device
         B, reps = q32.shape[0], _replicas(pc32, q32)
         Z = geom.sized(B, ctx.npts, reps, cells if ctx.indexed else None, pc32.shape[1])  # see ProjectFused.backward
         dl = dloss.detach().to(torch.float32).reshape(())
@@ -580,18 +530,10 @@ class ProjectLossFused(torch.autograd.Function):
         if not ctx.fused:
             ws = torch.empty((Z.ws_bytes,), dtype=torch.uint8, device=dev)
         kxy, kz = geom.kern_ptrs()
-        with _on(dev):
-            rc = L.dpc_project_loss_bwd(Z.ref, _dp(pc32), _dp(q32), _dp(t32), _dp(f32), _dp(s32), kxy, kz,
-                                        _dp(cells), _dp(grid_wh), _dp(mask), _dp(proj), _dp(trans), _dp(gt32),
-                                        ctx.gf, _dp(w32), ctx.K, _dp(winner), _dp(dl), int(ctx.fused), _dp(dpc), _dp(out_small),
-                                        _dp(ws), _stream(dev))
-        if rc != 0:
-            N.check(rc, "dpc_project_loss_bwd")
-        pc, q, t, f, s = ctx.inputs
-        return (_like_input(dpc, pc), _like_input(_small(out_small, N.COL_DQ, 4, B), q),
-                _like_input(_small(out_small, N.COL_DT, 3, B), t) if has_t else None,
-                _like_input(_small(out_small, N.COL_DF, 1, B), f) if has_f else None,
-                _like_input(_small(out_small, N.COL_DS, 1, B), s) if has_s else None, None, None, None, None, None, None)
+        N.call(dev, "dpc_project_loss_bwd", Z.ref, N.ptr(pc32), N.ptr(q32), N.ptr(t32), N.ptr(f32), N.ptr(s32), kxy, kz,
+               N.ptr(cells), N.ptr(grid_wh), N.ptr(mask), N.ptr(proj), N.ptr(trans), N.ptr(gt32),
+               ctx.gf, N.ptr(w32), ctx.K, N.ptr(winner), N.ptr(dl), int(ctx.fused), N.ptr(dpc), N.ptr(out_small), N.ptr(ws))
+        return _pose_grads(ctx.inputs, ctx.has, dpc, out_small, B, 6)
 
 
 class ProjectLossStep:
@@ -634,9 +576,10 @@ class ProjectLossStep:
         self.dq, self.ds = _small(self.dsmall, N.COL_DQ, 4, self.B), _small(self.dsmall, N.COL_DS, 1, self.B)
         self.dt, self.df = _small(self.dsmall, N.COL_DT, 3, self.B), _small(self.dsmall, N.COL_DF, 1, self.B)
         self._kxy, self._kz = geom.kern_ptrs()
-        self._fixed = (N.ptr(self.cells), N.ptr(self.grid_wh), N.ptr(self.mask), N.ptr(self.proj), N.ptr(self.trans), N.ptr(self.sse),
-                       N.ptr(self.sse_tiles), N.ptr(self.loss), N.ptr(self.winner), N.ptr(self.ws), N.ptr(self.fwd_dsmall))
-        self._tail = (N.ptr(self.dpc), N.ptr(self.dsmall))
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())
+        self._fixed = (vp(self.cells), vp(self.grid_wh), vp(self.mask), vp(self.proj), vp(self.trans), vp(self.sse),
+                       vp(self.sse_tiles), vp(self.loss), vp(self.winner), vp(self.ws), vp(self.fwd_dsmall))
+        self._tail = (vp(self.dpc), vp(self.dsmall))
         self._fn = L.dpc_project_loss_step
         self._pref = ctypes.byref(self.P)
 
@@ -692,10 +635,7 @@ class Transform(torch.autograd.Function):
         pc32, q32, t32, f32 = _f32(pc), _f32(q), _f32(t), _f32(f)
         P = geom.params(pc32.shape[0], pc32.shape[1])
         out = torch.empty_like(pc32)
-        with torch.cuda.device(dev):
-            rc = N.lib().dpc_transform_fwd(ctypes.byref(P), N.ptr(pc32), N.ptr(q32), N.ptr(t32), N.ptr(f32), N.ptr(out),
-                                           N.stream_ptr(dev))
-        N.check(rc, "dpc_transform_fwd")
+        N.call(dev, "dpc_transform_fwd", ctypes.byref(P), N.ptr(pc32), N.ptr(q32), N.ptr(t32), N.ptr(f32), N.ptr(out))
         ctx.geom, ctx.inputs, ctx.saved = geom, tuple(_meta(x) for x in (pc, q, t, f)), (pc32, q32, t32, f32)
         return out
 
@@ -707,14 +647,9 @@ class Transform(torch.autograd.Function):
         dout32 = dout.detach().to(torch.float32).contiguous()
         dpc = torch.empty_like(pc32)
         dsmall = torch.empty((N.DPC_SMALL_COLS * pc32.shape[0],), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = N.lib().dpc_transform_bwd(ctypes.byref(P), N.ptr(pc32), N.ptr(q32), N.ptr(t32), N.ptr(f32),
-                                           N.ptr(dout32), N.ptr(dpc), N.ptr(dsmall), N.stream_ptr(dev))
-        N.check(rc, "dpc_transform_bwd")
-        B = pc32.shape[0]
-        pc, q, t, f = ctx.inputs
-        return (_like_input(dpc, pc), _like_input(_small(dsmall, N.COL_DQ, 4, B), q),
-                _like_input(_small(dsmall, N.COL_DT, 3, B), t), _like_input(_small(dsmall, N.COL_DF, 1, B), f), None)
+        N.call(dev, "dpc_transform_bwd", ctypes.byref(P), N.ptr(pc32), N.ptr(q32), N.ptr(t32), N.ptr(f32),
+               N.ptr(dout32), N.ptr(dpc), N.ptr(dsmall))
+        return _pose_grads(ctx.inputs, (True, True), dpc, dsmall, pc32.shape[0], 1)
 
 
 class Splat(torch.autograd.Function):
@@ -728,9 +663,7 @@ class Splat(torch.autograd.Function):
         P = geom.params(trc.shape[0], trc.shape[1])
         vox = torch.empty((trc.shape[0], geom.D, geom.H, geom.W), dtype=torch.float32, device=dev)
         cells = _new_cells(P, dev)
-        with torch.cuda.device(dev):
-            rc = N.lib().dpc_splat_fwd(ctypes.byref(P), N.ptr(trc), int(is64), N.ptr(cells), N.ptr(vox), N.stream_ptr(dev))
-        N.check(rc, "dpc_splat_fwd")
+        N.call(dev, "dpc_splat_fwd", ctypes.byref(P), N.ptr(trc), int(is64), N.ptr(cells), N.ptr(vox))
         ctx.geom, ctx.tr, ctx.trc, ctx.is64 = geom, _meta(tr), trc, is64
         return vox
 
@@ -741,10 +674,7 @@ class Splat(torch.autograd.Function):
         P = ctx.geom.params(trc.shape[0], trc.shape[1])
         dvox32 = dvox.detach().to(torch.float32).contiguous()
         dtr = torch.empty(trc.shape, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = N.lib().dpc_splat_bwd(ctypes.byref(P), N.ptr(trc), int(ctx.is64), N.ptr(dvox32), N.ptr(dtr),
-                                       N.stream_ptr(dev))
-        N.check(rc, "dpc_splat_bwd")
+        N.call(dev, "dpc_splat_bwd", ctypes.byref(P), N.ptr(trc), int(ctx.is64), N.ptr(dvox32), N.ptr(dtr))
         return _like_input(dtr, ctx.tr), None
 
 
@@ -755,10 +685,7 @@ def _smooth_call(x32, geom, transpose):
     P = geom.params(B, 0)
     out, tmp = torch.empty_like(x32), torch.empty_like(x32)
     kxy, kz = geom.kern_ptrs()
-    with torch.cuda.device(dev):
-        rc = N.lib().dpc_smooth(ctypes.byref(P), kxy, kz, int(transpose), N.ptr(x32), N.ptr(out), N.ptr(tmp),
-                                N.stream_ptr(dev))
-    N.check(rc, "dpc_smooth")
+    N.call(dev, "dpc_smooth", ctypes.byref(P), kxy, kz, int(transpose), N.ptr(x32), N.ptr(out), N.ptr(tmp))
     return out
 
 
@@ -791,10 +718,7 @@ class Drc(torch.autograd.Function):
         proj = torch.empty((B, geom.H, geom.W), dtype=torch.float32, device=dev)
         probs = torch.empty((geom.D + 1, B, geom.H, geom.W), dtype=torch.float32, device=dev)
         depth = torch.empty((B, geom.H, geom.W), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = N.lib().dpc_drc_fwd(ctypes.byref(P), N.ptr(vox32), N.ptr(proj), N.ptr(probs), N.ptr(depth),
-                                     N.stream_ptr(dev))
-        N.check(rc, "dpc_drc_fwd")
+        N.call(dev, "dpc_drc_fwd", ctypes.byref(P), N.ptr(vox32), N.ptr(proj), N.ptr(probs), N.ptr(depth))
         ctx.geom, ctx.vox, ctx.vox32 = geom, _meta(vox), vox32
         ctx.set_materialize_grads(False)  # unused outputs arrive as None, not as zero-filled [D+1,B,H,W] tensors
         return proj, probs, depth
@@ -807,10 +731,7 @@ class Drc(torch.autograd.Function):
         c = lambda g: None if g is None else g.detach().to(torch.float32).contiguous()
         dproj, dprobs, ddepth = c(dproj), c(dprobs), c(ddepth)
         dvox = torch.empty_like(vox32)
-        with torch.cuda.device(dev):
-            rc = N.lib().dpc_drc_bwd(ctypes.byref(P), N.ptr(vox32), N.ptr(dproj), N.ptr(dprobs), N.ptr(ddepth),
-                                     N.ptr(dvox), N.stream_ptr(dev))
-        N.check(rc, "dpc_drc_bwd")
+        N.call(dev, "dpc_drc_bwd", ctypes.byref(P), N.ptr(vox32), N.ptr(dproj), N.ptr(dprobs), N.ptr(ddepth), N.ptr(dvox))
         return _like_input(dvox, ctx.vox), None
 
 
@@ -830,10 +751,7 @@ class GaussVoxels(torch.autograd.Function):
         P = geom.params(B, Npts)
         vox = torch.empty((B, G, G, G), dtype=torch.float32, device=dev)
         raw = torch.empty_like(vox) if ctx.needs_input_grad[0] else None
-        with _on(dev):
-            rc = N.lib().dpc_gauss_voxels_fwd(ctypes.byref(P), _dp(tr32), float(sigma), int(normalise), _dp(raw), _dp(vox),
-                                              _stream(dev))
-        N.check(rc, "dpc_gauss_voxels_fwd")
+        N.call(dev, "dpc_gauss_voxels_fwd", ctypes.byref(P), N.ptr(tr32), float(sigma), int(normalise), N.ptr(raw), N.ptr(vox))
         ctx.geom, ctx.tr, ctx.tr32, ctx.raw, ctx.sigma, ctx.normalise = geom, _meta(tr), tr32, raw, float(sigma), int(normalise)
         return vox
 
@@ -844,10 +762,8 @@ class GaussVoxels(torch.autograd.Function):
         P = ctx.geom.params(tr32.shape[0], tr32.shape[1])
         dvox32 = dvox.detach().to(torch.float32).contiguous()
         dtr = torch.empty(tr32.shape, dtype=torch.float32, device=dev)
-        with _on(dev):
-            rc = N.lib().dpc_gauss_voxels_bwd(ctypes.byref(P), _dp(tr32), ctx.sigma, ctx.normalise, _dp(ctx.raw), _dp(dvox32),
-                                              _dp(dtr), _stream(dev))
-        N.check(rc, "dpc_gauss_voxels_bwd")
+        N.call(dev, "dpc_gauss_voxels_bwd", ctypes.byref(P), N.ptr(tr32), ctx.sigma, ctx.normalise, N.ptr(ctx.raw), N.ptr(dvox32),
+               N.ptr(dtr))
         return _like_input(dtr, ctx.tr), None, None, None
 
 
@@ -878,10 +794,8 @@ class SilhouetteLoss(torch.autograd.Function):
         part = torch.empty((S,), dtype=torch.float32, device=dev)
         winner = torch.empty((S,), dtype=torch.int32, device=dev)
         dpred = torch.empty_like(p32)
-        with torch.cuda.device(dev):
-            rc = N.lib().dpc_silhouette_loss(N.ptr(g32), gf, N.ptr(w32), N.ptr(p32), S, K, H, W, N.ptr(part), N.ptr(winner),
-                                             N.ptr(dpred), N.stream_ptr(dev))
-        N.check(rc, "dpc_silhouette_loss")
+        N.call(dev, "dpc_silhouette_loss", N.ptr(g32), gf, N.ptr(w32), N.ptr(p32), S, K, H, W, N.ptr(part), N.ptr(winner),
+               N.ptr(dpred))
         ctx.dpred, ctx.meta = dpred, _meta(pred)
         ctx.mark_non_differentiable(winner)
         return part.sum(), winner
@@ -904,21 +818,13 @@ def _depth_workspace(dev, nbytes):
     is not kept: it comes from the graph's pool and its zero fill is part of the graph."""
     if torch.cuda.is_current_stream_capturing():
         return torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), _stream(dev), nbytes)
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), N.stream(dev), nbytes)
     ws = _depth_ws.get(key)
     if ws is None:
         if len(_depth_ws) >= 16:
             _depth_ws.clear()
         ws = _depth_ws[key] = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
     return ws
-
-
-def _call(dev, entry, *args):
-    """One entry point of the library on `dev` and its current stream (every entry's last argument); raises on a return code."""
-    with _on(dev):
-        rc = getattr(N.lib(), entry)(*args, _stream(dev))
-    if rc != 0:
-        N.check(rc, entry)
 
 
 def _loss_targets(x32, gt, weights, f, geom, what, rgb=False):
@@ -946,10 +852,10 @@ def _column_backward(ctx, entry, ws_entry, extra, *grads):
     Z = geom.sized(B, 0)
     dgrid = torch.empty_like(grid_wh)
     ds = None if s32 is None else torch.empty((B,), dtype=torch.float32, device=dev)
-    with _on(dev):
+    with N.on(dev):
         ws = _depth_workspace(dev, max(getattr(N.lib(), ws_entry)(Z.ref), 16))
-    _call(dev, entry, Z.ref, _dp(grid_wh), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), ctx.gt_factor, *extra, _dp(w32),
-          *[_dp(_f32(g)) for g in grads], _dp(dgrid), _dp(ds), _dp(ws))
+    N.call(dev, entry, Z.ref, N.ptr(grid_wh), N.ptr(s32), geom.kern_ptrs()[1], N.ptr(gt32), ctx.gt_factor, *extra, N.ptr(w32),
+          *[N.ptr(_f32(g)) for g in grads], N.ptr(dgrid), N.ptr(ds), N.ptr(ws))
     return _like_input(dgrid, ctx.metas[0]), _like_input(ds, ctx.metas[1])
 
 
@@ -976,8 +882,8 @@ class DepthMap(torch.autograd.Function):
         dev, g32, s32 = _depth_inputs(grid_wh, s, geom)
         B = g32.shape[0]
         depth = torch.empty((B, geom.H, geom.W, 1), dtype=torch.float32, device=dev)
-        _call(dev, "dpc_depth_loss_fwd", geom.sized(B, 0).ref, _dp(g32), _dp(s32), geom.kern_ptrs()[1], None, 1, 0.0, None,
-              _dp(depth), None, None)
+        N.call(dev, "dpc_depth_loss_fwd", geom.sized(B, 0).ref, N.ptr(g32), N.ptr(s32), geom.kern_ptrs()[1], None, 1, 0.0, None,
+              N.ptr(depth), None, None)
         ctx.geom, ctx.saved, ctx.metas = geom, (g32, s32, None, None), (_meta(grid_wh), _meta(s))
         ctx.gt_factor, ctx.max_dataset_depth = 1, 0.0
         return depth
@@ -1001,8 +907,8 @@ class DepthLoss(torch.autograd.Function):
         gt32, w32 = _loss_targets(g32, gt, weights, f, geom, "depths")
         tiles, loss = _loss_buffers(B, geom, dev)
         depth = torch.empty((B, geom.H, geom.W, 1), dtype=torch.float32, device=dev) if want_depth else None
-        _call(dev, "dpc_depth_loss_fwd", geom.sized(B, 0).ref, _dp(g32), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), f,
-              float(max_dataset_depth), _dp(w32), _dp(depth), _dp(tiles), _dp(loss))
+        N.call(dev, "dpc_depth_loss_fwd", geom.sized(B, 0).ref, N.ptr(g32), N.ptr(s32), geom.kern_ptrs()[1], N.ptr(gt32), f,
+              float(max_dataset_depth), N.ptr(w32), N.ptr(depth), N.ptr(tiles), N.ptr(loss))
         ctx.geom, ctx.saved, ctx.metas = geom, (g32, s32, gt32, w32), (_meta(grid_wh), _meta(s))
         ctx.gt_factor, ctx.max_dataset_depth = f, float(max_dataset_depth)
         if depth is not None:
@@ -1022,7 +928,7 @@ def _splat_forward(ctx, entry, tr, rgb, Z, geom, stop, n_set=(), ws=()):
     """Forward of a colour splat, the grid [B,3,D,H,W]; n_set / ws: the fixed-point entry's own arguments, as tuples."""
     tr32, rgb32 = _f32(tr), _f32(rgb)
     out = torch.empty((tr32.shape[0], 3, geom.D, geom.H, geom.W), dtype=torch.float32, device=tr32.device)
-    _call(tr32.device, entry, Z.ref, _dp(tr32), _dp(rgb32), *n_set, _dp(out), *ws)
+    N.call(tr32.device, entry, Z.ref, N.ptr(tr32), N.ptr(rgb32), *n_set, N.ptr(out), *ws)
     ctx.Z, ctx.saved, ctx.metas, ctx.stop = Z, (tr32, rgb32), (_meta(tr), _meta(rgb)), bool(stop)
     return out
 
@@ -1033,7 +939,7 @@ def _splat_backward(ctx, entry, dC, n_set=(), ws=()):
     dC32 = _f32(dC)
     drgb = torch.empty_like(rgb32)
     dtr = torch.empty_like(tr32) if (ctx.needs_input_grad[0] and not ctx.stop) else None
-    _call(tr32.device, entry, ctx.Z.ref, _dp(tr32), _dp(rgb32), *n_set, _dp(dC32), _dp(drgb), _dp(dtr), *ws)
+    N.call(tr32.device, entry, ctx.Z.ref, N.ptr(tr32), N.ptr(rgb32), *n_set, N.ptr(dC32), N.ptr(drgb), N.ptr(dtr), *ws)
     return _like_input(dtr, ctx.metas[0]), _like_input(drgb, ctx.metas[1])
 
 
@@ -1095,7 +1001,7 @@ class RgbSplatFixed(torch.autograd.Function):
         ctx.shared, n_set = reps > 1 or idx is not None, rgb.shape[1]
         Z = geom.sized(tr.shape[0], tr.shape[1], reps, idx, n_set if idx is not None else 0)
         ws = torch.empty((max(N.lib().dpc_rgb_splat_fixed_workspace_bytes(Z.ref, n_set), 16),), dtype=torch.uint8, device=dev)
-        return _splat_forward(ctx, "dpc_rgb_splat_fixed_fwd", tr, rgb, Z, geom, stop_points_gradient, (n_set,), (_dp(ws),))
+        return _splat_forward(ctx, "dpc_rgb_splat_fixed_fwd", tr, rgb, Z, geom, stop_points_gradient, (n_set,), (N.ptr(ws),))
 
     @staticmethod
     def backward(ctx, dC):
@@ -1103,7 +1009,7 @@ class RgbSplatFixed(torch.autograd.Function):
         ws = None
         if ctx.shared:   # the sets' 64-bit sums and poison words (include/dpc_render.h)
             ws = torch.empty(((24 * sets * n_set + 4 * sets + 255) // 256 * 256 + 16,), dtype=torch.uint8, device=dC.device)
-        return _splat_backward(ctx, "dpc_rgb_splat_fixed_bwd", dC, (n_set,), (_dp(ws),)) + (None,) * 3
+        return _splat_backward(ctx, "dpc_rgb_splat_fixed_bwd", dC, (n_set,), (N.ptr(ws),)) + (None,) * 3
 
 
 def _rgb_inputs(vox, C, div, geom):
@@ -1140,8 +1046,8 @@ def _rgb_loss_forward(ctx, entry, with_proj, vox, C, div, gt, gt_factor, gt_plan
     ctx.empty = False
     tiles, loss = _loss_buffers(B, geom, dev)
     proj = torch.empty((B, geom.H, geom.W, 3), dtype=torch.float32, device=dev) if with_proj else None
-    _call(dev, entry, geom.sized(B, 0).ref, _dp(v32), _dp(c32), _dp(d32), eps, clip, _dp(gt32), ctx.gt_factor, ctx.gt_planar,
-          _dp(w32), *([_dp(proj)] if with_proj else []), _dp(tiles), _dp(loss))
+    N.call(dev, entry, geom.sized(B, 0).ref, N.ptr(v32), N.ptr(c32), N.ptr(d32), eps, clip, N.ptr(gt32), ctx.gt_factor, ctx.gt_planar,
+          N.ptr(w32), *([N.ptr(proj)] if with_proj else []), N.ptr(tiles), N.ptr(loss))
     ctx.geom, ctx.saved, ctx.metas = geom, (v32, c32, d32, gt32, w32, proj), (_meta(vox), _meta(C))
     return loss, proj
 
@@ -1154,8 +1060,8 @@ def _rgb_backward(ctx, entry, *grads):
     v32, c32, d32, gt32, w32, _ = ctx.saved
     geom, dev = ctx.geom, v32.device
     dvox, dC = torch.empty_like(v32), torch.empty_like(c32)
-    _call(dev, entry, geom.sized(v32.shape[0], 0).ref, _dp(v32), _dp(c32), _dp(d32), ctx.div_eps, ctx.clip_after, _dp(gt32),
-          ctx.gt_factor, ctx.gt_planar, _dp(w32), *[_dp(_f32(g)) for g in grads], _dp(dvox), _dp(dC))
+    N.call(dev, entry, geom.sized(v32.shape[0], 0).ref, N.ptr(v32), N.ptr(c32), N.ptr(d32), ctx.div_eps, ctx.clip_after, N.ptr(gt32),
+          ctx.gt_factor, ctx.gt_planar, N.ptr(w32), *[N.ptr(_f32(g)) for g in grads], N.ptr(dvox), N.ptr(dC))
     return _like_input(dvox, ctx.metas[0]), _like_input(dC, ctx.metas[1])
 
 
@@ -1170,7 +1076,7 @@ class RgbMap(torch.autograd.Function):
         B = v32.shape[0]
         eps, clip = _rgb_options(ctx, div_eps, clip_after, 1, 0)
         proj = torch.empty((B, geom.H, geom.W, 3), dtype=torch.float32, device=dev)
-        _call(dev, "dpc_rgb_loss_fwd", geom.sized(B, 0).ref, _dp(v32), _dp(c32), _dp(d32), eps, clip, None, 1, 0, None, _dp(proj),
+        N.call(dev, "dpc_rgb_loss_fwd", geom.sized(B, 0).ref, N.ptr(v32), N.ptr(c32), N.ptr(d32), eps, clip, None, 1, 0, None, N.ptr(proj),
               None, None)
         ctx.geom, ctx.saved, ctx.metas = geom, (v32, c32, d32, None, None, None), (_meta(vox), _meta(C))
         return proj
@@ -1213,8 +1119,8 @@ class DrcLoss(torch.autograd.Function):
         B, f = g32.shape[0], int(gt_factor)
         gt32, w32 = _loss_targets(g32, gt, weights, f, geom, "masks")
         tiles, loss = _loss_buffers(B, geom, dev)
-        _call(dev, "dpc_drc_loss_fwd", geom.sized(B, 0).ref, _dp(g32), _dp(s32), geom.kern_ptrs()[1], _dp(gt32), f, _dp(w32),
-              _dp(tiles), _dp(loss))
+        N.call(dev, "dpc_drc_loss_fwd", geom.sized(B, 0).ref, N.ptr(g32), N.ptr(s32), geom.kern_ptrs()[1], N.ptr(gt32), f, N.ptr(w32),
+              N.ptr(tiles), N.ptr(loss))
         ctx.geom, ctx.saved, ctx.metas, ctx.gt_factor = geom, (g32, s32, gt32, w32), (_meta(grid_wh), _meta(s)), f
         return loss
 

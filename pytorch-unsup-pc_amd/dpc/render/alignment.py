@@ -10,7 +10,6 @@ The ICP runs on the GPU (csrc/dpc_icp.hip, all pairs in one call) with the seman
 registration_icp; the rest is host code in fp64 numpy that restates the reference's functions op for op.  Reading and
 writing .mat files stays with the caller: everything here takes and returns arrays.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -71,7 +70,7 @@ def icp_point_to_point(sources, targets, max_correspondence_distance, init=None,
         raise ValueError("icp_point_to_point: more than 2^31 - 1 points")
     desc = _batch.table([(src_start[i], len(srcs[i]), tgt_start[k], len(tgts[k])) for i, k in enumerate(target_of)], 4,
                         "icp_point_to_point: more than 2^31 - 1 points")
-    host_desc = desc.ctypes.data_as(ctypes.c_void_p)
+    host_desc = desc.ctypes.data
     _batch.dry_run(L.dpc_icp_point_to_point(None, n_src, None, n_tgt, None, host_desc, P, None,
                                             float(max_correspondence_distance), int(max_iteration),
                                             float(relative_fitness), float(relative_rmse), None, None, None, None, None,
@@ -89,18 +88,14 @@ def icp_point_to_point(sources, targets, max_correspondence_distance, init=None,
         return out_t, out_f, out_r, out_i
     src = torch.from_numpy(np.concatenate(srcs) if n_src else np.zeros((1, 3))).to(dev)
     tgt = torch.from_numpy(np.concatenate(tgts) if n_tgt else np.zeros((1, 3))).to(dev)
-    desc_d = torch.from_numpy(desc).to(dev)
+    desc_d = _batch.on_device(desc, dev)
     init_d = torch.from_numpy(init_np).to(dev)
     counts = np.ascontiguousarray(desc[:, 1]), np.ascontiguousarray(desc[:, 3])
-    ws = _batch.workspace(L.dpc_icp_workspace_bytes(P, counts[0].ctypes.data_as(ctypes.c_void_p),
-                                                    counts[1].ctypes.data_as(ctypes.c_void_p)), dev)
-    with torch.cuda.device(dev):
-        rc = L.dpc_icp_point_to_point(_native.ptr(src), n_src, _native.ptr(tgt), n_tgt, _native.ptr(desc_d), host_desc, P,
-                                      _native.ptr(init_d),
-                                      float(max_correspondence_distance), int(max_iteration), float(relative_fitness),
-                                      float(relative_rmse), _native.ptr(out_t), _native.ptr(out_f), _native.ptr(out_r),
-                                      _native.ptr(out_i), _native.ptr(ws), _native.stream_ptr(dev))
-    _native.check(rc, "dpc_icp_point_to_point")
+    ws = _batch.workspace(L.dpc_icp_workspace_bytes(P, counts[0].ctypes.data, counts[1].ctypes.data), dev)
+    _native.call(dev, "dpc_icp_point_to_point", _native.ptr(src), n_src, _native.ptr(tgt), n_tgt, _native.ptr(desc_d), host_desc, P,
+                 _native.ptr(init_d), float(max_correspondence_distance), int(max_iteration), float(relative_fitness),
+                 float(relative_rmse), _native.ptr(out_t), _native.ptr(out_f), _native.ptr(out_r), _native.ptr(out_i),
+                 _native.ptr(ws))
     return out_t, out_f, out_r, out_i
 
 

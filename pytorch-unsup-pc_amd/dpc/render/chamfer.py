@@ -14,7 +14,6 @@ in numpy's float64 order, so every number equals the reference's own compute_dis
 
 Reading .mat files stays with the caller (load_gt), as everywhere in this package.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -41,24 +40,21 @@ def _forward(pts, desc, dev, dtype, want_points, squared):
     L = _native.lib()
     P, n_pts = desc.shape[0], int(pts.shape[0])
     is64 = int(dtype == torch.float64)
-    host_desc = desc.ctypes.data_as(ctypes.c_void_p)
+    host_desc = desc.ctypes.data
     total = int(desc[:, 1].astype(np.int64).sum()) if P else 0
     mean = torch.empty((P,), dtype=torch.float64, device=dev)
     dist = torch.empty((total,), dtype=dtype, device=dev) if want_points else None
     idx = torch.empty((total,), dtype=torch.int64, device=dev) if want_points else None
     val, desc_d = dist, None
     if P:
-        desc_d = torch.from_numpy(desc).to(dev)
+        desc_d = _batch.on_device(desc, dev)
         ws = _batch.workspace(L.dpc_chamfer_workspace_bytes(P, host_desc, is64), dev)
-        with torch.cuda.device(dev):
-            rc = L.dpc_nearest_batched(_native.ptr(pts), n_pts, is64, _native.ptr(desc_d), host_desc, P, _native.ptr(mean),
-                                       _native.ptr(dist), _native.ptr(idx), _native.ptr(ws), _native.stream_ptr(dev))
-            _native.check(rc, "dpc_nearest_batched")
-            if squared:
-                val = dist * dist
-                rc = L.dpc_chamfer_pair_means(_native.ptr(val), is64, _native.ptr(desc_d), host_desc, P, _native.ptr(mean),
-                                              _native.ptr(ws), _native.stream_ptr(dev))
-                _native.check(rc, "dpc_chamfer_pair_means")
+        _native.call(dev, "dpc_nearest_batched", _native.ptr(pts), n_pts, is64, _native.ptr(desc_d), host_desc, P,
+                     _native.ptr(mean), _native.ptr(dist), _native.ptr(idx), _native.ptr(ws))
+        if squared:
+            val = dist * dist
+            _native.call(dev, "dpc_chamfer_pair_means", _native.ptr(val), is64, _native.ptr(desc_d), host_desc, P,
+                         _native.ptr(mean), _native.ptr(ws))
     elif squared:
         val = dist * dist
     return mean, val, dist, idx, desc_d
@@ -88,16 +84,14 @@ class _NearestBatched(torch.autograd.Function):
             dpts = torch.zeros_like(pts)
         else:
             L = _native.lib()
-            host_desc = desc.ctypes.data_as(ctypes.c_void_p)
+            host_desc = desc.ctypes.data
             gmean = None if gmean is None else gmean.to(device=dev, dtype=torch.float64).contiguous()
             gval = None if gval is None else gval.to(device=dev, dtype=dtype).contiguous()
             dpts = torch.empty_like(pts)
             ws = _batch.workspace(L.dpc_chamfer_bwd_workspace_bytes(P, host_desc, is64), dev)
-            with torch.cuda.device(dev):
-                rc = L.dpc_nearest_batched_bwd(_native.ptr(pts), n_pts, is64, _native.ptr(ctx.desc_d), host_desc, P,
-                                               _native.ptr(dist), _native.ptr(idx), _native.ptr(gmean), _native.ptr(gval),
-                                               int(ctx.squared), _native.ptr(dpts), _native.ptr(ws), _native.stream_ptr(dev))
-            _native.check(rc, "dpc_nearest_batched_bwd")
+            _native.call(dev, "dpc_nearest_batched_bwd", _native.ptr(pts), n_pts, is64, _native.ptr(ctx.desc_d), host_desc, P,
+                         _native.ptr(dist), _native.ptr(idx), _native.ptr(gmean), _native.ptr(gval), int(ctx.squared),
+                         _native.ptr(dpts), _native.ptr(ws))
         return dpts.to(device=ctx.like[0], dtype=ctx.like[1]), None, None, None, None
 
 
@@ -122,7 +116,7 @@ def nearest_batched(points, pairs, return_distances=False, squared=False):
     n_pts = int(pts.shape[0])
     if n_pts > _batch.INT32_MAX:
         raise ValueError("nearest_batched: more than 2^31 - 1 points")
-    host_desc = desc.ctypes.data_as(ctypes.c_void_p)
+    host_desc = desc.ctypes.data
     _batch.dry_run(L.dpc_nearest_batched(None, n_pts, 0, None, host_desc, P, None, None, None, None, None),
                    "nearest_batched: invalid pair table (a negative start or count, a range outside the %d points, "
                    "an empty target for a non-empty source, or more than 2^31 - 1 output points)" % n_pts)

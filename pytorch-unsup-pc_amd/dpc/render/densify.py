@@ -12,7 +12,6 @@ point equals the reference's, in the reference's order, bit for bit.
 
 Reading .obj files and writing .mat files stays with the caller (load_mesh, save), as everywhere in this package.
 """
-import ctypes
 import numbers
 
 import numpy as np
@@ -141,7 +140,7 @@ def _densify_packed(meshes, n, rounds_per_sync=ROUNDS_PER_SYNC):
                         "densify: more than 2^31 - 1 vertices, edges or faces, or num_points %d, in one job" % n)
     most = max(mm[4] for mm in meshes)
     L = _native.lib()
-    host_desc = desc.ctypes.data_as(ctypes.c_void_p)
+    host_desc = desc.ctypes.data
     _batch.dry_run(L.dpc_densify(None, vo, None, eo, None, None, fo, None, host_desc, C, most, 1, 0, None, None, None,
                                  None, None),
                    "densify: refused by dpc_densify (%d models, num_points %d: an id would pass 2^31 - 1)" % (C, n),
@@ -152,22 +151,20 @@ def _densify_packed(meshes, n, rounds_per_sync=ROUNDS_PER_SYNC):
     rows = [len(mm[0]) + n for mm in meshes]
     out = torch.empty((max(sum(rows), 1), 3), dtype=torch.float64, device=dev)
     info = torch.zeros((2,), dtype=torch.int32, device=dev)  # status, models with splits left
-    desc_d = torch.from_numpy(desc).to(dev)
+    desc_d = _batch.on_device(desc, dev)
     ws = _batch.workspace(L.dpc_densify_workspace_bytes(C, eo, fo, C * n, most), dev)
     rounds, begin = 0, 1
-    with torch.cuda.device(dev):
-        while True:
-            rc = L.dpc_densify(_native.ptr(verts), vo, _native.ptr(edges), eo, _native.ptr(faces), _native.ptr(face_edges),
-                               fo, _native.ptr(desc_d), host_desc, C, most, begin, rounds_per_sync, _native.ptr(out),
-                               _native.ptr(info[:1]), _native.ptr(info[1:]), _native.ptr(ws), _native.stream_ptr(dev))
-            _native.check(rc, "dpc_densify")
-            rounds += rounds_per_sync
-            begin = 0
-            status, left = (int(x) for x in info.cpu().tolist())  # one synchronisation per rounds_per_sync rounds
-            if status or left == 0:
-                break
-            if rounds > n + rounds_per_sync:  # every round splits at least one edge of every model with splits left
-                raise RuntimeError("dpc_densify: %d rounds and %d models still unfinished" % (rounds, left))
+    while True:
+        _native.call(dev, "dpc_densify", _native.ptr(verts), vo, _native.ptr(edges), eo, _native.ptr(faces),
+                     _native.ptr(face_edges), fo, _native.ptr(desc_d), host_desc, C, most, begin, rounds_per_sync,
+                     _native.ptr(out), _native.ptr(info[:1]), _native.ptr(info[1:]), _native.ptr(ws))
+        rounds += rounds_per_sync
+        begin = 0
+        status, left = (int(x) for x in info.cpu().tolist())  # one synchronisation per rounds_per_sync rounds
+        if status or left == 0:
+            break
+        if rounds > n + rounds_per_sync:  # every round splits at least one edge of every model with splits left
+            raise RuntimeError("dpc_densify: %d rounds and %d models still unfinished" % (rounds, left))
     _batch.raise_status(status, [
         (_native.DPC_STATUS_NONFINITE, "densify: a vertex, edge length or midpoint is not finite"),
         (_native.DPC_STATUS_BAD_INDEX, "densify: dpc_densify found an inconsistent mesh"),

@@ -10,7 +10,6 @@ rather than open3d's hash-map order (include/dpc_render.h states the semantics).
 
 Reading and writing .mat files stays with the caller (load_dense, save), as everywhere in this package.
 """
-import ctypes
 import math
 import numbers
 
@@ -45,21 +44,19 @@ def _downsample_packed(clouds, vs):
     desc = _batch.table(np.stack([np.cumsum(counts) - counts, counts], axis=1), 2,
                         "voxel_down_sample: more than 2^31 - 2 points in one call")
     L = _native.lib()
-    host_desc = desc.ctypes.data_as(ctypes.c_void_p)
+    host_desc = desc.ctypes.data
     _batch.dry_run(L.dpc_voxel_downsample(None, M, 0, None, host_desc, C, vs, None, None, None, None, None, None),
                    "voxel_down_sample: refused by dpc_voxel_downsample (voxel_size %r, %d points)" % (vs, M))
     dev = _batch.device("dpc.render voxel downsampling", clouds)
-    dtype = torch.float64 if any(c.dtype == torch.float64 for c in clouds) else torch.float32  # widening is exact
+    dtype = _batch.widest(clouds)
     pts, _ = _batch.pack(clouds, dev, dtype)
     out = torch.empty((max(M, 1), 3), dtype=torch.float64, device=dev)
     info = torch.zeros((1 + 2 * C,), dtype=torch.int32, device=dev)  # status, out_count [C], out_offset [C]
-    desc_d = torch.from_numpy(desc).to(dev)
+    desc_d = _batch.on_device(desc, dev)
     ws = _batch.workspace(L.dpc_downsample_workspace_bytes(C, M), dev)
-    with torch.cuda.device(dev):
-        rc = L.dpc_voxel_downsample(_native.ptr(pts), M, int(dtype == torch.float64), _native.ptr(desc_d), host_desc, C, vs,
-                                    _native.ptr(out), _native.ptr(info[1:1 + C]), _native.ptr(info[1 + C:]),
-                                    _native.ptr(info[:1]), _native.ptr(ws), _native.stream_ptr(dev))
-    _native.check(rc, "dpc_voxel_downsample")
+    _native.call(dev, "dpc_voxel_downsample", _native.ptr(pts), M, int(dtype == torch.float64), _native.ptr(desc_d), host_desc,
+                 C, vs, _native.ptr(out), _native.ptr(info[1:1 + C]), _native.ptr(info[1 + C:]), _native.ptr(info[:1]),
+                 _native.ptr(ws))
     info = info.cpu().numpy().astype(np.int64)  # the call's one synchronisation
     _batch.raise_status(int(info[0]), [
         (_native.DPC_STATUS_NONFINITE, lambda: "voxel_down_sample: cloud %d holds a NaN or inf coordinate"

@@ -14,8 +14,6 @@ optimum, bit-reproducible, and differentiable.
 
 The schedule, the tie rules and the summation order are in include/dpc_render.h (dpc_emd_fwd).
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -80,7 +78,7 @@ def _check(preds, gts, eps, max_rounds, fn):
     desc = _batch.table([(start[i], counts[i], start[i], counts[i]) for i in range(len(counts))], 4,
                         "%s: pair table entries must fit int32" % fn)
     total = int(start[-1])
-    rc = _native.lib().dpc_emd_fwd(None, total, None, total, 0, None, desc.ctypes.data_as(ctypes.c_void_p), len(counts), 0,
+    rc = _native.lib().dpc_emd_fwd(None, total, None, total, 0, None, desc.ctypes.data, len(counts), 0,
                                    eps, int(max_rounds), None, None, None, None, None, None)
     _batch.dry_run(rc, "%s: dpc_emd_fwd refused the pair table" % fn)
     return P_list, G_list, desc, eps, int(max_rounds)
@@ -96,13 +94,10 @@ def _forward(pred, gt, desc, squared, eps, max_rounds, status):
     rounds = torch.empty((P,), dtype=torch.int32, device=dev)
     desc_d = None
     if P:
-        desc_d = torch.from_numpy(desc).to(dev)
-        with torch.cuda.device(dev):
-            rc = _native.lib().dpc_emd_fwd(_native.ptr(pred), total, _native.ptr(gt), total, int(pred.dtype == torch.float64),
-                                           _native.ptr(desc_d), desc.ctypes.data_as(ctypes.c_void_p), P, int(squared), eps,
-                                           max_rounds, _native.ptr(emd), _native.ptr(assignment), _native.ptr(inverse),
-                                           _native.ptr(rounds), _native.ptr(status), _native.stream_ptr(dev))
-        _native.check(rc, "dpc_emd_fwd")
+        desc_d = _batch.on_device(desc, dev)
+        _native.call(dev, "dpc_emd_fwd", _native.ptr(pred), total, _native.ptr(gt), total, int(pred.dtype == torch.float64),
+                     _native.ptr(desc_d), desc.ctypes.data, P, int(squared), eps, max_rounds, _native.ptr(emd),
+                     _native.ptr(assignment), _native.ptr(inverse), _native.ptr(rounds), _native.ptr(status))
     return emd, assignment, inverse, rounds, desc_d
 
 
@@ -131,27 +126,21 @@ class _Emd(torch.autograd.Function):
         gemd = gemd.to(device=dev, dtype=torch.float64).contiguous()
         dpred = torch.empty_like(p) if want_p else None
         dgt = torch.empty_like(g) if want_g else None
-        with torch.cuda.device(dev):
-            rc = _native.lib().dpc_emd_bwd(_native.ptr(p), total, _native.ptr(g), total, int(p.dtype == torch.float64),
-                                           _native.ptr(ctx.desc_d), desc.ctypes.data_as(ctypes.c_void_p), P, int(ctx.squared),
-                                           _native.ptr(emd), _native.ptr(assignment), _native.ptr(inverse), _native.ptr(gemd),
-                                           _native.ptr(dpred), _native.ptr(dgt), _native.stream_ptr(dev))
-        _native.check(rc, "dpc_emd_bwd")
+        _native.call(dev, "dpc_emd_bwd", _native.ptr(p), total, _native.ptr(g), total, int(p.dtype == torch.float64),
+                     _native.ptr(ctx.desc_d), desc.ctypes.data, P, int(ctx.squared), _native.ptr(emd), _native.ptr(assignment),
+                     _native.ptr(inverse), _native.ptr(gemd), _native.ptr(dpred), _native.ptr(dgt))
         return (dpred, dgt) + (None,) * 5
 
 
 def _run(preds, gts, squared, eps, max_rounds, fn, status=None):
     P_list, G_list, desc, eps, max_rounds = _check(preds, gts, eps, max_rounds, fn)
-    for group in (preds, gts):   # arrays are copied to the device; a CPU tensor is refused, as everywhere in the package
-        _native.require_device(*[c for c in ([group] if isinstance(group, torch.Tensor) else group)
-                                 if isinstance(c, torch.Tensor)])
+    _batch.refuse_cpu(preds, gts)
     dev = _batch.device(_WHAT, P_list, G_list)
     counts = [len(p) for p in P_list]
     if not counts:
         empty = torch.empty((0,), dtype=torch.float64, device=dev)
         return empty, [], [], torch.empty((0,), dtype=torch.int32, device=dev)
-    # all arithmetic is fp64 and fp32 widens exactly, so one fp64 pair makes the whole call fp64 without changing a bit
-    dtype = torch.float64 if any(c.dtype == torch.float64 for c in P_list + G_list) else torch.float32
+    dtype = _batch.widest(P_list + G_list)    # one fp64 pair makes the whole call fp64 without changing a bit
     pred = torch.cat([c.to(device=dev, dtype=dtype) for c in P_list])
     gt = torch.cat([c.to(device=dev, dtype=dtype) for c in G_list])
     status = status_word(dev) if status is None else status

@@ -20,7 +20,6 @@ normals (load_obj_scene_shaded) go through dpc_render_meshes_shaded, which diffe
 Reading .obj files stays on the host; writing PNG / .mat / pickle files stays with the caller (tools/render_train_data.py).
 """
 import collections
-import ctypes
 import os
 
 import numpy as np
@@ -412,8 +411,7 @@ def _tables(items, view_scene, attrs=None):
 
 def _workspace_bytes(meshes, views):
     L = _native.lib()
-    return L.dpc_render_meshes_workspace_bytes(meshes.ctypes.data_as(ctypes.c_void_p), len(meshes),
-                                               views.ctypes.data_as(ctypes.c_void_p), len(views))
+    return L.dpc_render_meshes_workspace_bytes(meshes.ctypes.data, len(meshes), views.ctypes.data, len(views))
 
 
 def _status_message(items, view_scene, cams, S, bits, attrs=None, textures=True, smooth_normals=True):
@@ -515,10 +513,10 @@ def _render(items, attrs, cam_pos, cfg, image_size, supersample, return_face_id,
     L = _native.lib()
     if attrs is not None:
         meshes, views, (nv, nf, nk, nu, nn, nt), tex, texel_bytes = _tables(items, view_scene, attrs)
-        ht = tex.ctypes.data_as(ctypes.c_void_p)
+        ht = tex.ctypes.data
     else:
         meshes, views, (nv, nf, nk) = _tables(items, view_scene)
-    hm, hv = meshes.ctypes.data_as(ctypes.c_void_p), views.ctypes.data_as(ctypes.c_void_p)
+    hm, hv = meshes.ctypes.data, views.ctypes.data
     if attrs is not None:
         rc = L.dpc_render_meshes_shaded(None, nv, None, None, nf, None, nk, None, nu, None, None, nn, None, None, None,
                                         texel_bytes, None, ht, nt, None, hm, len(meshes), None, hv, None, W, S, ss, None,
@@ -539,14 +537,14 @@ def _render(items, attrs, cam_pos, cfg, image_size, supersample, return_face_id,
             cat(3, np.float64, (-1, 3))
         meshes_d, views_d, cams_d = (torch.from_numpy(a).to(dev) for a in (meshes, views, cams))
         status = torch.zeros((1,), dtype=torch.int32, device=dev)
-        P = _native.ptr
+        N = _native
+        geometry = (N.ptr(verts) if nv else None, nv, N.ptr(faces) if nf else None, N.ptr(mats) if nf else None, nf,
+                    N.ptr(kd) if nk else None, nk)
+        tail = (N.ptr(meshes_d), hm, len(meshes), N.ptr(views_d), hv, N.ptr(cams_d), W, S, ss, N.ptr(rgba), N.ptr(depth),
+                N.ptr(face_id), N.ptr(status))
         if attrs is None:
             ws = _batch.workspace(_workspace_bytes(meshes, views), dev)
-            with torch.cuda.device(dev):
-                rc = L.dpc_render_meshes(P(verts) if nv else None, nv, P(faces) if nf else None, P(mats) if nf else None, nf,
-                                         P(kd) if nk else None, nk, P(meshes_d), hm, len(meshes), P(views_d), hv, P(cams_d),
-                                         W, S, ss, P(rgba), P(depth), P(face_id), P(status), P(ws), _native.stream_ptr(dev))
-            _native.check(rc, "dpc_render_meshes")
+            N.call(dev, "dpc_render_meshes", *geometry, *tail, N.ptr(ws))
         else:
             # a switched-off group travels as NULL pointers: the library then reads none of it
             up = lambda arrays, dt, shape: torch.from_numpy(np.concatenate(arrays).astype(dt, copy=False).reshape(shape)).to(dev)
@@ -558,15 +556,10 @@ def _render(items, attrs, cam_pos, cfg, image_size, supersample, return_face_id,
                 texels_d = up([img.reshape(-1) for a in attrs for img in a[5]] + [np.zeros(0, dtype=np.uint8)], np.uint8, (-1,))
             if smooth_normals:
                 vn_d, fvn_d = up([a[2] for a in attrs], np.float64, (-1, 3)), up([a[3] for a in attrs], np.int32, (-1, 3))
-            some = lambda t: P(t) if t is not None and t.numel() else None
+            some = lambda t: N.ptr(t) if t is not None and t.numel() else None
             ws = _batch.workspace(L.dpc_render_meshes_shaded_workspace_bytes(hm, len(meshes), hv, len(views)), dev)
-            with torch.cuda.device(dev):
-                rc = L.dpc_render_meshes_shaded(
-                    P(verts) if nv else None, nv, P(faces) if nf else None, P(mats) if nf else None, nf, P(kd) if nk else None,
-                    nk, some(uv_d), nu, some(fuv_d), some(vn_d), nn, some(fvn_d), some(mt_d), some(texels_d), texel_bytes,
-                    some(tex_d), ht, nt, P(meshes_d), hm, len(meshes), P(views_d), hv, P(cams_d), W, S, ss, P(rgba), P(depth),
-                    P(face_id), P(status), P(ws), _native.stream_ptr(dev))
-            _native.check(rc, "dpc_render_meshes_shaded")
+            N.call(dev, "dpc_render_meshes_shaded", *geometry, some(uv_d), nu, some(fuv_d), some(vn_d), nn, some(fvn_d),
+                   some(mt_d), some(texels_d), texel_bytes, some(tex_d), ht, nt, *tail, N.ptr(ws))
         bits = int(status.item())
         if bits:
             raise MeshError(_status_message(items, view_scene, cams, S, bits, attrs, textures, smooth_normals))

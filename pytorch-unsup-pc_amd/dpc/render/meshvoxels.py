@@ -10,16 +10,13 @@ The rules (the surface test, the two fills, the counts) are this library's own; 
 include/dpc_render.h (dpc_voxelise_meshes) and defined by tests/mesh_voxels_oracle.py.  Grid, axis order and bit layout
 are those of voxelise, so the grid of a mesh and the grid of a cloud of the same model line up.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _batch, _native
 from ._ops import status_word
 from .densify import MeshError
-from .voxels import (MAX_SIDE, _bits_of_clouds, _bits_of_grids, _call, _grid_tensor, _iou, _pair_stats, _shape_of, _unpack,
-                     _words)
+from .voxels import MAX_SIDE, _bits_of_clouds, _bits_of_grids, _grid_tensor, _iou, _pair_stats, _shape_of, _unpack, _words
 
 _WHAT = "dpc.render mesh voxelisation"
 FILLS = {"none": _native.DPC_MESH_FILL_NONE, "carve": _native.DPC_MESH_FILL_CARVE, "parity": _native.DPC_MESH_FILL_PARITY}
@@ -66,7 +63,7 @@ def _checked_meshes(meshes, shape, fill, fn):
         raise ValueError("%s: more than 2^31 - 1 vertices or faces in one call" % fn)
     desc = _batch.table(np.stack([vs[:-1], nv, fs[:-1], nf], axis=1) if items else np.zeros((0, 4)), 4,
                         "%s: mesh table entries must fit int32" % fn)
-    rc = _native.lib().dpc_voxelise_meshes(None, int(vs[-1]), 0, None, int(fs[-1]), None, desc.ctypes.data_as(ctypes.c_void_p),
+    rc = _native.lib().dpc_voxelise_meshes(None, int(vs[-1]), 0, None, int(fs[-1]), None, desc.ctypes.data,
                                            len(items), shape[0], shape[1], shape[2], fill, None, None, None, None, None)
     _batch.dry_run(rc, "%s: dpc_voxelise_meshes refused the mesh table or the grid %s" % (fn, (shape,)))
     return items, desc
@@ -78,17 +75,16 @@ def _bits_of_meshes(items, desc, shape, fill, dev, status=None):
     bits = torch.empty((M, _words(shape)), dtype=torch.int32, device=dev)
     info = torch.zeros((M, 2), dtype=torch.int32, device=dev)
     if M:
-        dtype = torch.float64 if any(V.dtype == torch.float64 for V, _ in items) else torch.float32   # fp32 widens exactly
+        dtype = _batch.widest(V for V, _ in items)
         verts, _ = _batch.pack([V for V, _ in items], dev, dtype)
         faces = torch.from_numpy(np.concatenate([F for _, F in items]).reshape(-1, 3)).to(dev)
         scratch = torch.empty_like(bits) if fill == _native.DPC_MESH_FILL_CARVE else None
-        desc_d = torch.from_numpy(desc).to(dev)
+        desc_d = _batch.on_device(desc, dev)
         status = status_word(dev) if status is None else status
-        with torch.cuda.device(dev):
-            _call("dpc_voxelise_meshes", _native.ptr(verts) if len(verts) else None, int(verts.shape[0]), int(dtype == torch.float64),
-                  _native.ptr(faces) if len(faces) else None, int(faces.shape[0]), _native.ptr(desc_d),
-                  desc.ctypes.data_as(ctypes.c_void_p), M, shape[0], shape[1], shape[2], fill, _native.ptr(bits), _native.ptr(scratch),
-                  _native.ptr(info), _native.ptr(status), _native.stream_ptr(dev))
+        _native.call(dev, "dpc_voxelise_meshes", _native.ptr(verts) if len(verts) else None, int(verts.shape[0]),
+                     int(dtype == torch.float64), _native.ptr(faces) if len(faces) else None, int(faces.shape[0]), _native.ptr(desc_d),
+                     desc.ctypes.data, M, shape[0], shape[1], shape[2], fill, _native.ptr(bits), _native.ptr(scratch),
+                     _native.ptr(info), _native.ptr(status))
     return bits, info
 
 
@@ -96,9 +92,8 @@ def _carved(bits, shape):
     """The "carve" fill of bit grids [B, words]: a new tensor."""
     out = torch.empty_like(bits)
     if bits.shape[0]:
-        with torch.cuda.device(bits.device):
-            _call("dpc_voxel_carve", _native.ptr(bits), int(bits.shape[0]), shape[0], shape[1], shape[2], _native.ptr(out),
-                  _native.stream_ptr(bits.device))
+        _native.call(bits.device, "dpc_voxel_carve", _native.ptr(bits), int(bits.shape[0]), shape[0], shape[1], shape[2],
+                     _native.ptr(out))
     return out
 
 

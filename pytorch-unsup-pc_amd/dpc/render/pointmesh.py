@@ -12,8 +12,6 @@ themselves (csrc/dpc_point_mesh.hip), and fscore can take its precision half fro
 The rules of the distance (zero-area faces, non-finite vertices) are stated in include/dpc_render.h
 (dpc_point_mesh_distance) and defined by tests/point_mesh_oracle.py.
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -64,7 +62,7 @@ class _Plan:
                                  "%s: table entries must fit int32" % fn)
         self.sizes = (int(ps[-1]), int(vs[-1]), int(fs[-1]))
         rc = _native.lib().dpc_point_mesh_distance(None, self.sizes[0], 0, None, self.sizes[1], 0, None, self.sizes[2], None,
-                                                   self.desc.ctypes.data_as(ctypes.c_void_p), len(rows), None, None, None, None)
+                                                   self.desc.ctypes.data, len(rows), None, None, None, None)
         _batch.dry_run(rc, "%s: dpc_point_mesh_distance refused the table (too many points or work items in one call)" % fn)
 
     def tensors(self):
@@ -76,8 +74,7 @@ class _Plan:
         d2 = torch.empty((n_pts,), dtype=torch.float64, device=dev)
         if n_pts == 0:
             return d2
-        pdt = torch.float64 if any(c.dtype == torch.float64 for c in self.clouds) else torch.float32   # fp32 widens exactly
-        vdt = torch.float64 if any(V.dtype == torch.float64 for V, _ in self.items) else torch.float32
+        pdt, vdt = _batch.widest(self.clouds), _batch.widest(V for V, _ in self.items)
         pts, _ = _batch.pack(self.clouds, dev, pdt)
         if not bool(torch.isfinite(pts).all()):
             for i, c in enumerate(self.clouds):
@@ -85,15 +82,11 @@ class _Plan:
                     raise ValueError("%s: %s[%d] holds a NaN or inf coordinate" % (self.fn, self.cloud_name, i))
         verts, _ = _batch.pack([V for V, _ in self.items], dev, vdt)
         faces = torch.from_numpy(np.concatenate([F for _, F in self.items]).reshape(-1, 3)).to(dev)
-        desc_d = torch.from_numpy(self.desc).to(dev)
-        L = _native.lib()
-        ws = _batch.workspace(L.dpc_point_mesh_workspace_bytes(len(self.desc)), dev)
-        with torch.cuda.device(dev):
-            rc = L.dpc_point_mesh_distance(_native.ptr(pts), n_pts, int(pdt == torch.float64), _native.ptr(verts), n_verts,
-                                           int(vdt == torch.float64), _native.ptr(faces), n_faces, _native.ptr(desc_d),
-                                           self.desc.ctypes.data_as(ctypes.c_void_p), len(self.desc), _native.ptr(d2),
-                                           _native.ptr(ws), _native.ptr(status_word(dev)), _native.stream_ptr(dev))
-        _native.check(rc, "dpc_point_mesh_distance")
+        desc_d = _batch.on_device(self.desc, dev)
+        ws = _batch.workspace(_native.lib().dpc_point_mesh_workspace_bytes(len(self.desc)), dev)
+        _native.call(dev, "dpc_point_mesh_distance", _native.ptr(pts), n_pts, int(pdt == torch.float64), _native.ptr(verts),
+                     n_verts, int(vdt == torch.float64), _native.ptr(faces), n_faces, _native.ptr(desc_d), self.desc.ctypes.data,
+                     len(self.desc), _native.ptr(d2), _native.ptr(ws), _native.ptr(status_word(dev)))
         return d2
 
 

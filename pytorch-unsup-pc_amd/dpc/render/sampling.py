@@ -10,8 +10,6 @@ rounds).
 
 The distance expression, the tie rule and the outputs are in include/dpc_render.h (dpc_fps).
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -69,7 +67,7 @@ def _check(clouds, num_samples, first):
         raise ValueError("%s: more than 2^31 - 1 points in one call" % _FN)
     desc = _batch.table([(start[i], counts[i], firsts[i], out[i], samples[i]) for i in range(C)], 5,
                         "%s: cloud table entries must fit int32" % _FN)
-    rc = _native.lib().dpc_fps(None, int(start[-1]), 0, None, desc.ctypes.data_as(ctypes.c_void_p), C, None, None, None, None)
+    rc = _native.lib().dpc_fps(None, int(start[-1]), 0, None, desc.ctypes.data, C, None, None, None, None)
     _batch.dry_run(rc, "%s: dpc_fps refused the cloud table" % _FN)
     return C_list, samples, desc, as_tensor and len(set(samples)) <= 1
 
@@ -77,24 +75,18 @@ def _check(clouds, num_samples, first):
 def _sample(clouds, num_samples, first, status=None):
     """farthest_point_sample with the status word to report into (None: the package's): (indices, radius2, one tensor?)."""
     C_list, samples, desc, stacked = _check(clouds, num_samples, first)
-    # arrays are copied to the device; a CPU tensor is refused, as everywhere in the package
-    group = [clouds] if isinstance(clouds, torch.Tensor) else clouds
-    _native.require_device(*[c for c in group if isinstance(c, torch.Tensor)])
+    _batch.refuse_cpu(clouds)
     dev = _batch.device(_WHAT, C_list)
     total_out = int(sum(samples))
     indices = torch.empty((total_out,), dtype=torch.int32, device=dev)
     radius2 = torch.empty((total_out,), dtype=torch.float64, device=dev)
     if C_list:
-        # all arithmetic is fp64 and fp32 widens exactly, so one fp64 cloud makes the whole call fp64 without changing an index
-        dtype = torch.float64 if any(c.dtype == torch.float64 for c in C_list) else torch.float32
+        dtype = _batch.widest(C_list)    # one fp64 cloud makes the whole call fp64 without changing an index
         pts, _ = _batch.pack(C_list, dev, dtype)
-        desc_d = torch.from_numpy(desc).to(dev)
+        desc_d = _batch.on_device(desc, dev)
         status = status_word(dev) if status is None else status
-        with torch.cuda.device(dev):
-            rc = _native.lib().dpc_fps(_native.ptr(pts), int(pts.shape[0]), int(dtype == torch.float64), _native.ptr(desc_d),
-                                       desc.ctypes.data_as(ctypes.c_void_p), len(C_list), _native.ptr(indices),
-                                       _native.ptr(radius2), _native.ptr(status), _native.stream_ptr(dev))
-        _native.check(rc, "dpc_fps")
+        _native.call(dev, "dpc_fps", _native.ptr(pts), int(pts.shape[0]), int(dtype == torch.float64), _native.ptr(desc_d),
+                     desc.ctypes.data, len(C_list), _native.ptr(indices), _native.ptr(radius2), _native.ptr(status))
     if stacked:
         m = samples[0] if samples else 0
         return indices.view(len(C_list), m), radius2.view(len(C_list), m)

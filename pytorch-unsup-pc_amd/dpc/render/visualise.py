@@ -13,7 +13,6 @@ of our own; include/dpc_render.h states the semantics and the deliberate deviati
     write_png            8-bit RGB PNG with zlib and struct only
     write_png_rgba, write_png_gray16, read_png_any   the training views' render_N.png (RGBA8) and depth_N.png (16-bit grey)
 """
-import ctypes
 import numbers
 import struct
 import zlib
@@ -126,7 +125,7 @@ def render_point_clouds(clouds, azimuth=140.0, elevation=15.0, dist=2.0, image_s
                          "render_point_clouds: more than 2^31 - 1 points in one call")
     n = int(sum(counts))
     L = _native.lib()
-    host_table = table.ctypes.data_as(ctypes.c_void_p)
+    host_table = table.ctypes.data
     _batch.dry_run(L.dpc_render_points(None, None, None, n, None, host_table, P, None, S, ss, F, float(point_size), None,
                                        None, None, None),
                    "render_point_clouds: refused by dpc_render_points (%d clouds of %d points, image_size %d, supersample "
@@ -143,13 +142,11 @@ def render_point_clouds(clouds, azimuth=140.0, elevation=15.0, dist=2.0, image_s
     ids = torch.empty((P, S * ss, S * ss), dtype=torch.int32, device=dev) if return_ids else None
     status = torch.zeros((1,), dtype=torch.int32, device=dev)
     if P:
-        table_d = torch.from_numpy(table).to(dev)
+        table_d = _batch.on_device(table, dev)
         frames_d = torch.from_numpy(frames).to(dev)
-        with torch.cuda.device(dev):
-            rc = L.dpc_render_points(_native.ptr(scene), _native.ptr(col_t), _native.ptr(rad_t), n, _native.ptr(table_d),
-                                     host_table, P, _native.ptr(frames_d), S, ss, F, float(point_size), _native.ptr(image),
-                                     _native.ptr(ids), _native.ptr(status), _native.stream_ptr(dev))
-        _native.check(rc, "dpc_render_points")
+        _native.call(dev, "dpc_render_points", _native.ptr(scene), _native.ptr(col_t), _native.ptr(rad_t), n, _native.ptr(table_d),
+                     host_table, P, _native.ptr(frames_d), S, ss, F, float(point_size), _native.ptr(image), _native.ptr(ids),
+                     _native.ptr(status))
         _batch.raise_status(int(status.item()), [(_native.DPC_STATUS_NONFINITE, lambda: _nonfinite_message(cl, cols, rads))])
     out = image if dtype == torch.float32 else to_uint8(image)
     return (out, ids) if return_ids else out

@@ -12,8 +12,6 @@ Clouds and float grids become bit grids (csrc/dpc_voxels.hip); everything downst
 output has one right answer.  The conventions -- grid layout, the voxelisation rule, the bit layout, which threshold is
 inclusive, voxel2pc's axis order -- are in include/dpc_render.h (dpc_voxelise).
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -83,10 +81,6 @@ def _grid_tensor(x, name, fn, kinds):
     return t.detach()
 
 
-def _call(fn_name, *args):
-    _native.check(getattr(_native.lib(), fn_name)(*args), fn_name)
-
-
 def _bits_of_clouds(clouds, shape, dev, fn, status=None):
     """(bit grids int32 [C, words], dropped int32 [C]) of a list of [n,3] tensors: one dpc_voxelise call."""
     C = len(clouds)
@@ -102,14 +96,13 @@ def _bits_of_clouds(clouds, shape, dev, fn, status=None):
         if stacked is not None:
             pts, dtype = stacked.view(-1, 3), stacked.dtype
         else:
-            dtype = torch.float64 if any(c.dtype == torch.float64 for c in clouds) else torch.float32   # fp32 widens exactly
+            dtype = _batch.widest(clouds)
             pts, _ = _batch.pack(clouds, dev, dtype)
-        desc_d = torch.from_numpy(desc).to(dev)
+        desc_d = _batch.on_device(desc, dev)
         status = status_word(dev) if status is None else status
-        with torch.cuda.device(dev):
-            _call("dpc_voxelise", _native.ptr(pts) if len(pts) else None, int(pts.shape[0]), int(dtype == torch.float64),
-                  _native.ptr(desc_d), desc.ctypes.data_as(ctypes.c_void_p), C, shape[0], shape[1], shape[2], _native.ptr(bits),
-                  _native.ptr(dropped), _native.ptr(status), _native.stream_ptr(dev))
+        _native.call(dev, "dpc_voxelise", _native.ptr(pts) if len(pts) else None, int(pts.shape[0]), int(dtype == torch.float64),
+                     _native.ptr(desc_d), desc.ctypes.data, C, shape[0], shape[1], shape[2], _native.ptr(bits),
+                     _native.ptr(dropped), _native.ptr(status))
     return bits, dropped
 
 
@@ -119,9 +112,8 @@ def _bits_of_grids(grids, threshold, inclusive, dev):
     B, shape = g.shape[0], tuple(g.shape[1:])
     bits = torch.empty((B, _words(shape)), dtype=torch.int32, device=dev)
     if B:
-        with torch.cuda.device(dev):
-            _call("dpc_voxel_threshold", _native.ptr(g), _GRID_DTYPES[g.dtype], B, shape[0], shape[1], shape[2], float(threshold),
-                  int(bool(inclusive)), _native.ptr(bits), _native.stream_ptr(dev))
+        _native.call(dev, "dpc_voxel_threshold", _native.ptr(g), _GRID_DTYPES[g.dtype], B, shape[0], shape[1], shape[2],
+                     float(threshold), int(bool(inclusive)), _native.ptr(bits))
     return bits
 
 
@@ -130,8 +122,7 @@ def _unpack(bits, shape):
     B = bits.shape[0]
     out = torch.empty((B,) + tuple(shape), dtype=torch.bool, device=bits.device)
     if B:
-        with torch.cuda.device(bits.device):
-            _call("dpc_voxel_unpack", _native.ptr(bits), B, shape[0], shape[1], shape[2], _native.ptr(out), _native.stream_ptr(bits.device))
+        _native.call(bits.device, "dpc_voxel_unpack", _native.ptr(bits), B, shape[0], shape[1], shape[2], _native.ptr(out))
     return out
 
 
@@ -141,12 +132,11 @@ def _pair_stats(pred_bits, gt_bits, pairs, shape, status=None):
     P = len(pairs)
     stats = torch.zeros((P, 5), dtype=torch.int64, device=dev)
     if P:
-        pairs_d = torch.from_numpy(pairs).to(dev)
+        pairs_d = _batch.on_device(pairs, dev)
         status = status_word(dev) if status is None else status
-        with torch.cuda.device(dev):
-            _call("dpc_voxel_stats", _native.ptr(pred_bits), int(pred_bits.shape[0]), _native.ptr(gt_bits), int(gt_bits.shape[0]),
-                  shape[0], shape[1], shape[2], _native.ptr(pairs_d), pairs.ctypes.data_as(ctypes.c_void_p), P, _native.ptr(stats),
-                  _native.ptr(status), _native.stream_ptr(dev))
+        _native.call(dev, "dpc_voxel_stats", _native.ptr(pred_bits), int(pred_bits.shape[0]), _native.ptr(gt_bits),
+                     int(gt_bits.shape[0]), shape[0], shape[1], shape[2], _native.ptr(pairs_d), pairs.ctypes.data, P,
+                     _native.ptr(stats), _native.ptr(status))
     return stats
 
 
@@ -162,7 +152,7 @@ def voxelise(clouds, vox_size, vox_size_z=-1, return_dropped=False):
     fn = "voxelise"
     shape = _shape_of(vox_size, vox_size_z, fn)
     cl = _clouds(clouds, "clouds", fn)
-    _native.require_device(*[c for c in (clouds if isinstance(clouds, (list, tuple)) else [clouds]) if isinstance(c, torch.Tensor)])
+    _batch.refuse_cpu(clouds)
     dev = _batch.device(_WHAT, cl)
     bits, dropped = _bits_of_clouds(cl, shape, dev, fn)
     grids = _unpack(bits, shape)
@@ -202,8 +192,7 @@ def _sources(preds, gts, gt_of, vox_size, vox_size_z, fn):
         raise ValueError("%s: gt_of must map each of the %d predictions to one of %d ground truths" % (fn, P, Q))
     pairs = _batch.table(np.stack([np.arange(P), np.asarray(gt_of, dtype=np.int64)], axis=1) if P else np.zeros((0, 2)), 2,
                          "%s: pair table entries must fit int32" % fn)
-    rc = _native.lib().dpc_voxel_stats(None, P, None, Q, shape[0], shape[1], shape[2], None, pairs.ctypes.data_as(ctypes.c_void_p), P,
-                                       None, None, None)
+    rc = _native.lib().dpc_voxel_stats(None, P, None, Q, shape[0], shape[1], shape[2], None, pairs.ctypes.data, P, None, None, None)
     _batch.dry_run(rc, "%s: dpc_voxel_stats refused the pair table" % fn)
     return pred, gt, pairs, shape
 
@@ -299,8 +288,7 @@ def _points_of_bits(bits, G, dev):
     B = bits.shape[0]
     counts_d = torch.empty((B,), dtype=torch.int32, device=dev)
     if B:
-        with torch.cuda.device(dev):
-            _call("dpc_voxel_count", _native.ptr(bits), B, G, G, G, _native.ptr(counts_d), _native.stream_ptr(dev))
+        _native.call(dev, "dpc_voxel_count", _native.ptr(bits), B, G, G, G, _native.ptr(counts_d))
     counts = counts_d.cpu().numpy().astype(np.int64)      # the one host synchronisation: the output is sized by it
     start = np.cumsum(np.concatenate([[0], counts]))
     total = int(start[-1])
@@ -309,10 +297,9 @@ def _points_of_bits(bits, G, dev):
     xyz = torch.empty((total, 3), dtype=torch.float64, device=dev)
     if B:
         desc = _batch.table(np.stack([start[:-1], counts], axis=1), 2, "voxel2pc: table entries must fit int32")
-        desc_d = torch.from_numpy(desc).to(dev)
-        with torch.cuda.device(dev):
-            _call("dpc_voxel2pc", _native.ptr(bits), B, G, _native.ptr(desc_d), desc.ctypes.data_as(ctypes.c_void_p), total,
-                  _native.ptr(xyz) if total else None, _native.ptr(status_word(dev)), _native.stream_ptr(dev))
+        desc_d = _batch.on_device(desc, dev)
+        _native.call(dev, "dpc_voxel2pc", _native.ptr(bits), B, G, _native.ptr(desc_d), desc.ctypes.data, total,
+                     _native.ptr(xyz) if total else None, _native.ptr(status_word(dev)))
     return xyz, [int(c) for c in counts]
 
 

@@ -306,3 +306,30 @@ def test_kernel_lists_carry_their_taps_and_geometry():
     # DpcParams blocks and buffer sizes are cached per call shape (needs the library, not a GPU)
     z1, z2 = g1.sized(4, 1000), g1.sized(4, 1000)
     assert z1 is z2 and z1.cells_bytes > 0 and z1.ws_bytes >= 4 * 32 ** 3 * 4 and g1.sized(5, 1000) is not z1
+
+
+def test_the_library_is_called_through_one_helper():
+    """dpc/render reaches libdpc_render.so in one dialect: _native.call (device guard, torch's current raw stream, DpcError on a
+    return code) with plain-int addresses (_native.ptr, array.ctypes.data).  Read from the source files: outside _native.py, and
+    outside ProjectLossStep (the pre-bound plan bench.py times, which keeps its own hand-tuned call), no module spells the guard,
+    the stream getters, a c_void_p conversion or the return-code check itself."""
+    pkg = os.path.join(ROOT, "pytorch-unsup-pc_amd", "dpc", "render")
+    banned = ("torch.cuda.device(", "current_stream(", "_cuda_getCurrentRawStream", "c_void_p(", "data_as(")
+    found = []
+    files = sorted(f for f in os.listdir(pkg) if f.endswith(".py"))
+    assert "_native.py" in files and "_ops.py" in files and len(files) >= 15
+    for name in files:
+        if name == "_native.py":
+            continue
+        text = open(os.path.join(pkg, name)).read()
+        if name == "_ops.py":   # cut the class ProjectLossStep out: from its header to the next top-level statement
+            m = re.search(r"^class ProjectLossStep\b.*?(?=^\S)", text, flags=re.S | re.M)
+            assert m and "def run(" in m.group(0) and "dpc_project_loss_step" in m.group(0)
+            text = text[:m.start()] + text[m.end():]
+        for no, line in enumerate(text.splitlines(), 1):
+            hits = [b for b in banned if b in line] + (["check("] if re.search(r"(?<![\w])check\(", line) else [])
+            found += ["%s: %s: %s" % (name, hits, line.strip())] if hits else []
+    assert not found, "call sites outside _native.call:\n" + "\n".join(found)
+    from dpc.render import _native, _ops
+
+    assert not any(hasattr(_ops, n) for n in ("_dp", "_call", "_on", "_stream")) and not hasattr(_native, "host_floats")

@@ -1277,6 +1277,36 @@ def test_point_dropout_indices_in_a_replayed_graph(R):
     assert all(not np.array_equal(seen[0], s) for s in seen[1:]) and not np.array_equal(seen[1], seen[2])
 
 
+def test_evaluation_calls_follow_the_current_stream(R):
+    """The evaluation modules enqueue on torch's current stream like the autograd path: voxelise and farthest_point_sample
+    called under torch.cuda.stream(side) give, once `side` alone has been synchronised, what they give on the default stream."""
+    d = torch.device("cuda")
+    g = torch.Generator().manual_seed(5)
+    clouds = [(torch.rand(n, 3, generator=g) - 0.5).to(d) for n in (3, 5)]
+    cloud8 = (torch.rand(8, 3, generator=g, dtype=torch.float64) - 0.5).to(d)
+    want_grids, want_idx = R.voxelise(clouds, 4), R.farthest_point_sample([cloud8], 3)
+    torch.cuda.synchronize()
+    assert want_grids.shape == (2, 4, 4, 4) and want_grids.any() and want_idx[0].shape == (3,)
+    side = torch.cuda.Stream(d)
+    with torch.cuda.stream(side):
+        grids, idx = R.voxelise(clouds, 4), R.farthest_point_sample([cloud8], 3)
+    side.synchronize()
+    assert torch.equal(grids, want_grids)
+    assert torch.equal(idx[0], want_idx[0]) and idx[0][0] == 0 and len(set(idx[0].tolist())) == 3
+
+
+def test_call_raises_an_error_naming_the_entry_and_the_code():
+    """_native.call turns a return code into DpcError with the entry's name and the library's code and message.  The refusal
+    used launches nothing: dpc_point_dropout_indices returns DPC_ERR_SHAPE for n > N on its first line (csrc/dpc_stages.hip),
+    and the NULL pointers here could not reach a kernel anyway."""
+    from dpc.render import _native as Nat
+
+    with pytest.raises(Nat.DpcError) as e:
+        Nat.call(torch.device("cuda"), "dpc_point_dropout_indices", 1, 10, 11, None, None)
+    assert e.value.code == Nat.DPC_ERR_SHAPE
+    assert str(e.value) == "dpc_point_dropout_indices failed: %s (code %d)" % (Nat.strerror(Nat.DPC_ERR_SHAPE), Nat.DPC_ERR_SHAPE)
+
+
 def test_graphed_project_loss(R, O):
     """The graph-captured step for eager loops: same loss and gradients as the eager call, on the sample data and on new
     data of the same shapes, called repeatedly."""
