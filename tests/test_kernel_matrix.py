@@ -215,15 +215,15 @@ def _family(i):
 
 
 # ------------------------------------------------------------------------------------------------------ CPU: the gate
-def built_instantiations():
-    """{demangled template id} of the kernels in the fused-path device objects, from their mangled symbols
+def built_instantiations(objects=FUSED_OBJECTS):
+    """{demangled template id} of the kernels in the device objects `objects` (the fused path's), from their mangled symbols
     (_ZN4dpck12_GLOBAL__N_111k_gather_hwILi64ELi8ELi3EEEv... -> k_gather_hw<64, 8, 3>).  Only the dpck kernels count:
     k_zero_words (the memset kernel every object carries, dpc_common.h), the stage kernels (dpc_stages.o) and the nearest-point
     kernels (dpc_nearest.o) are not the fused path and are out of this gate's scope."""
     import re
 
     out = set()
-    for obj in FUSED_OBJECTS:
+    for obj in objects:
         for line in device_object_output(obj, ["llvm-readelf", "-sW"]).splitlines():
             f = line.split()
             if len(f) < 8 or f[3] != "FUNC":
