@@ -903,6 +903,75 @@ int dpc_voxelise_meshes(const void* verts, int n_verts, int is_f64, const int32_
 int dpc_voxel_carve(const uint32_t* bits, int B, int D, int H, int W, uint32_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Iso-surface extraction (dpc/util/voxel.py: extract_surface): occupancy grids to triangle meshes, for a ragged batch of
+ * grids in one call.  The reference calls skimage's Lewiner marching cubes; this is a surface extractor with a stated
+ * rule of its own: the same cube-edge vertices, this library's order, no Lewiner interior vertices.  Everything below is
+ * exact: there is one right answer and no tolerance.  tests/surface_oracle.py restates the rule in numpy.
+ *
+ * Grid.  A grid is [D,H,W], fp32 or fp64, sides 1 .. DPC_VOXEL_MAX_SIDE; node (d,h,w) has the flat index
+ *   f = (d*H + h)*W + w.  Output column c is grid axis c, as in dpc_voxelise.  Coordinates are in index units (node i is
+ *   at i), as skimage with spacing 1.
+ * Inside.  A node is inside iff (double)v > iso, strictly, as in voxel2pc; a NaN node is outside.  iso is one double per
+ *   grid.
+ * Vertices.  The edge from node n to n + e_a (a = 0, 1, 2 for D, H, W) is owned by n and carries a vertex iff exactly one
+ *   of its ends is inside.  With va, vb the two values widened to fp64, t = (iso - va) / (vb - va), and the vertex is n
+ *   with (double)n_a + t in column a; nothing is fused (csrc/dpc_surface.hip is built with -ffp-contract=off).  A grid's
+ *   vertices come in ascending key 3*f(n) + a; a vertex exists once, however many cells use it.
+ * Cells.  A cell has corner 0 at node (d,h,w), d < D-1, h < H-1, w < W-1; corner k = 4*dd + 2*dh + dw;
+ *   case = sum inside(k) << k.  Cell edge e = 4*a + j runs along axis a; j = u_b + 2*u_c for its offsets on the two other
+ *   axes b < c.
+ * Triangulation of a case.  On each of the six faces 0, 2 or 4 edges are crossed.  Two crossed edges are joined by a
+ *   segment.  Four (the ambiguous face) are joined so that each inside corner of the face is cut off alone: its two
+ *   adjacent face edges are joined.  The pairing depends on the face's own four corners only, so two cells sharing a face
+ *   agree: the surface is closed.  Each segment is directed so that (v1-v0) x (v2-v0) of the resulting triangles, in
+ *   output columns 0, 1, 2, points toward lower values (skimage's default gradient_direction='descent'): a blob above the
+ *   level has positive signed volume sum v0 . (v1 x v2) / 6.  The directed segments form disjoint loops; a loop starts at
+ *   its lowest edge id, loops are emitted in ascending order of that id, and a loop e0, e1, ... is fanned as
+ *   (e0, e_i, e_i+1).  The table is the generated csrc/dpc_surface_table.h (tools/gen_surface_table.py): 256 rows, at most
+ *   5 triangles a case, 820 in all.
+ * Faces.  A grid's faces come in ascending flat index of the cell's corner 0, then table order; they are int32 indices
+ *   into that grid's own vertices, 0-based.  Degenerate triangles (a node exactly at iso is outside and gives t = 0 on
+ *   its edges) are kept.
+ * Borders and small grids.  Surfaces are open at the grid border.  A grid with a side of 1 has no cell and no face; it
+ *   still has the vertices of its crossed edges (the vertex rule does not know about cells).
+ * Non-finite values.  A crossed edge with a NaN or infinite end writes its vertex as it comes out (NaN; t = 0 when only
+ *   vb is infinite) and ORs DPC_STATUS_NONFINITE into *status (dpc_surface_extract only).  Counts and faces are not
+ *   affected.
+ *
+ * Calling shape, as dpc_voxel_count + dpc_voxel2pc: dpc_surface_count writes counts [B,2] int32 (vertices, faces) per grid;
+ * the caller reads them, sizes the outputs and calls dpc_surface_extract with out_desc.
+ *   values      the grids' nodes packed one grid after another, n_values of them, fp32 (is_f64 = 0) or fp64
+ *   grid_desc / host_grid_desc   [B,4] int32 (first node, D, H, W), DEVICE / HOST, the same values; the grids ascend
+ *               in values without overlap (a node has one entry of the workspace's map)
+ *   iso         DEVICE double [B]
+ *   out_desc / host_out_desc     [B,4] int32 (first vertex row, vertices, first face row, faces), DEVICE / HOST; the counts
+ *               are what dpc_surface_count reported, the ranges ascend without overlap
+ *   verts       DEVICE double [n_verts,3];  faces  DEVICE int32 [n_faces,3]
+ *   workspace   dpc_surface_workspace_bytes(host_grid_desc, B, n_values) bytes (0 for a table the entry points refuse):
+ *               8 bytes per tile of 1024 nodes (every grid rounded up to the largest grid's tiles), 4 per grid, 4 per
+ *               node; the two passes do not share its contents
+ *   status      DEVICE int32, zeroed by the caller, NULL allowed
+ * Launches.  dpc_surface_count: k_surface_tiles (per tile of 1024 consecutive nodes the vertices and faces it will emit),
+ *   k_surface_scan (one workgroup per grid: the ordered scan over its tiles).  dpc_surface_extract: the same two, then
+ *   k_surface_verts (the vertices, and per node an int32 map entry: first vertex id, inside bit, crossing bits) and
+ *   k_surface_faces (the faces through the map).  The output order does not depend on scheduling.
+ * A device-table row that fails its check against n_values / n_verts / n_faces, or whose out_desc counts are not the
+ * grid's, sets DPC_STATUS_BAD_INDEX and nothing of that grid is written; the other grids are unaffected.
+ * Every check runs before any launch (DPC_ERR_SHAPE: a negative size, a side outside the limits, a grid outside values or
+ * overlapping its predecessor, out ranges that do not ascend, overrun their buffers or exceed 3 vertices a node / 5 faces
+ * a cell; the totals are int arguments, so a call's totals fit int32 by construction); valid arguments with NULL device
+ * pointers return DPC_ERR_NULL without touching a device; zero grids return DPC_OK with nothing launched.  No host
+ * synchronisation inside a call, no allocation, no floating-point atomics and no global atomics but the OR into the
+ * status word.  Added without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_surface_workspace_bytes(const int32_t* host_grid_desc, int B, int n_values);
+int dpc_surface_count(const void* values, int n_values, int is_f64, const int32_t* grid_desc, const int32_t* host_grid_desc, int B,
+                      const double* iso, int32_t* counts, void* workspace, int32_t* status, void* stream);
+int dpc_surface_extract(const void* values, int n_values, int is_f64, const int32_t* grid_desc, const int32_t* host_grid_desc,
+                        int B, const double* iso, const int32_t* out_desc, const int32_t* host_out_desc, int n_verts, int n_faces,
+                        double* verts, int32_t* faces, void* workspace, int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Exact point-to-mesh distance: for n_pairs rows (a range of points, a mesh) in one call, the squared Euclidean distance
  * from every point to the nearest point of the union of the row's closed triangles.  The evaluation measures its
  * distances against sampled ground truth, whose spacing is a floor under every distance; this measures against the

@@ -120,6 +120,9 @@ _FUNCTIONS = (
     ("dpc_voxel2pc", _i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     ("dpc_voxelise_meshes", _i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     ("dpc_voxel_carve", _i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    ("dpc_surface_workspace_bytes", _sz, [_vp, _i, _i]),
+    ("dpc_surface_count", _i, [_vp, _i, _i, _vp, _vp, _i] + [_vp] * 5),
+    ("dpc_surface_extract", _i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i] + [_vp] * 5),
     ("dpc_point_mesh_workspace_bytes", _sz, [_i]),
     ("dpc_point_mesh_distance", _i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     ("dpc_downsample_workspace_bytes", _sz, [_i, _i]),

@@ -327,11 +327,17 @@ def _cfg_get(cfg, key, default):
     return getattr(cfg, key, default)
 
 
+_PLAIN_KD = np.array([[0.8, 0.8, 0.8]])   # the diffuse colour of a scene given as a bare (V, F) pair
+
+
 def _scene(scene, i):
-    """(V, F, material, Kd[, names]) -> host arrays (float64 [n,3], int32 [f,3], int32 [f], float64 [k,3])."""
+    """(V, F, material, Kd[, names]) -> host arrays (float64 [n,3], int32 [f,3], int32 [f], float64 [k,3]).  A bare
+    (V, F) pair, as extract_surfaces returns it, is one material of _PLAIN_KD; device tensors are copied to the host."""
+    if len(scene) == 2:
+        scene = (scene[0], scene[1], np.zeros(len(scene[1]), dtype=np.int32), _PLAIN_KD)
     if len(scene) < 4:
         raise ValueError("render_mesh_views: scene %d must be (V, F, material, Kd[, names])" % i)
-    V, F, mat, Kd = (np.asarray(x) for x in scene[:4])
+    V, F, mat, Kd = (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x) for x in scene[:4])
     V = np.ascontiguousarray(V.reshape(-1, 3) if V.size == 0 else V, dtype=np.float64)
     F = F.reshape(-1, 3) if F.size == 0 else F
     Kd = np.ascontiguousarray(Kd.reshape(-1, 3) if Kd.size == 0 else Kd, dtype=np.float64)
