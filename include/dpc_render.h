@@ -61,6 +61,12 @@ extern "C" {
 #define DPC_PM_BLOCK 256
 #define DPC_PM_FACE_TILE 128
 #define DPC_PM_CHUNK_TILES 8
+/* dpc_knn_batched / dpc_pca_normals: the most neighbours per query, and the references a workgroup stages in LDS per
+ * round.  A workgroup holds DPC_KNN_BLOCK(k) queries, one lane each: 256 for k <= 16, 128 for k <= 32, 64 above, so that
+ * the lanes' sorted lists (k slots of a d2 and an int32 each) fit next to the tile. */
+#define DPC_KNN_MAX_K 64
+#define DPC_KNN_TILE 512
+#define DPC_KNN_BLOCK(k) ((k) <= 16 ? 256 : (k) <= 32 ? 128 : 64)
 
 enum {
   DPC_OK = 0,
@@ -1020,6 +1026,65 @@ size_t dpc_point_mesh_workspace_bytes(int n_pairs);
 int dpc_point_mesh_distance(const void* points, int n_points, int points_f64, const void* verts, int n_verts, int verts_f64,
                             const int32_t* faces, int n_faces, const int32_t* pair_desc, const int32_t* host_pair_desc, int n_pairs,
                             double* d2, void* workspace, int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Batched k-nearest-neighbour search, and surface normals from the neighbours' covariance (PCA): the building blocks of
+ * the normal-consistency metric (dpc/render/normals.py).  There is no counterpart in the reference: the rules below are
+ * this library's own, tests/normals_oracle.py restates them in numpy.
+ *
+ * dpc_knn_batched.  Row r = (q_start, q_count, r_start, r_count) names a range of queries and a range of references of
+ * the one packed buffer pts [n_pts,3]; a cloud against itself is one row with both ranges the same, and several rows may
+ * name one reference range (the views of one model share one GT copy).  T = fp64 when is_f64, else fp32.
+ *   distance     for query i and reference j, in T, nothing fused and no square root taken:
+ *                d = ref_j - q_i;  d2 = (d0*d0 + d1*d1) + d2*d2   (the expression of dpc_nearest_batched);
+ *   neighbours   the k references smallest by the pair (d2, j), in ascending order of that pair: ties in d2 go to the
+ *                lower index, inside the list and at its k-th place.  A query is not excluded from its own neighbours
+ *                (when queries and references coincide it is normally slot 0, d2 = 0).  A d2 that overflows to +inf is
+ *                ordered like any other value;
+ *   NaN          a candidate whose d2 is NaN (a NaN coordinate, or inf - inf) never enters a list and ORs
+ *                DPC_STATUS_NONFINITE into *status; the other candidates are ranked as without it;
+ *   outputs      idx [sum q_count, k] int32, relative to r_start, and d2 [sum q_count, k] in T (NULL: not wanted), the
+ *                rows' queries packed in row order; slots beyond r_count, or beyond the candidates that are not NaN, hold
+ *                -1 and +inf.  A row with q_count == 0 writes nothing.
+ *   The result is the same bit for bit from run to run and however the rows are ordered or batched: a lane owns a
+ *   query and walks the row's references in index order; nothing is summed across lanes.
+ * dpc_pca_normals.  The same table, and the idx that dpc_knn_batched wrote for it with the same k.  For each query with
+ * c valid slots (0 <= idx < r_count), everything in fp64 after exact widening, x_j the neighbours:
+ *   mu = (1/c) sum x_j;   C = (1/c) sum (x_j - mu)(x_j - mu)^T, from the deviations (two passes), never from raw moments;
+ *   eigenvalues  l0 <= l1 <= l2 of C (c == 0: C counts as the zero matrix), ascending in eigenvalues [sum q_count,3]
+ *                (NULL: not wanted), never below zero;
+ *   normal       a unit eigenvector of l0, normals [sum q_count,3] fp64; (0, 0, 0) when c < 3 (the eigenvalues are still
+ *                those of C).  Where l0 == l1 any unit vector of their eigenspace may be returned;
+ *   sign         with viewpoints ([rows,3] fp64, DEVICE): flipped so that n . (viewpoint_r - q_i) >= 0, open3d's
+ *                orient_normals_towards_camera_location; without (NULL): the component of largest magnitude is
+ *                positive, the lowest axis deciding between equal magnitudes;
+ *   guards       an idx value outside [-1, r_count) never becomes an address: it ORs DPC_STATUS_BAD_INDEX into *status
+ *                and counts as an invalid slot.
+ *   accuracy     is the contract, not the algorithm (a cyclic Jacobi iteration on C / trace C; products and sums may be
+ *                fused).  With unit = 2^-52 trace(C) / (l1 - l0): the sine of the angle between the normal and the exact
+ *                eigenvector of the exact C is a small multiple of unit, | |n| - 1 | <= 4 2^-52, and every eigenvalue is
+ *                within a small multiple of 2^-52 trace(C).  tests/golden/f30_normals.npz records the multiple that
+ *                numpy's eigh reaches on the fixtures; the tests allow 8 times it.
+ * Both.  row_desc / host_row_desc [rows,4] int32, DEVICE / HOST, the same values; status DEVICE int32, zeroed by the
+ * caller, NULL allowed.  A device-table row that does not lie inside pts, or whose outputs do not lie inside what the
+ * host table counted, sets DPC_STATUS_BAD_INDEX and nothing of it is read or written.
+ * Kernels (csrc/dpc_knn.hip): a lane owns a query; a workgroup of DPC_KNN_BLOCK(k) lanes stages DPC_KNN_TILE references
+ * per round in LDS and every lane walks the tile.  Each lane's sorted list lives in LDS as [slot][lane] and its k-th
+ * best d2 in a register, so a candidate is rejected with one compare.  LDS per workgroup:
+ * DPC_KNN_BLOCK(k) k (sizeof(T) + 4) + 3 DPC_KNN_TILE sizeof(T) bytes, at most 60 KiB: two workgroups per CU in fp64
+ * and four in fp32 at every k.  The launch grid is (query blocks of the longest row) x rows; a block sums the q_count of
+ * the rows before its own from the device table, so no workspace is needed.
+ * Every check runs before any launch (DPC_ERR_SHAPE: k outside [1, DPC_KNN_MAX_K], a negative size, start or count, a
+ * range outside [0, n_pts), more than 2^31 - 1 output slots sum q_count x k); valid arguments with NULL device pointers
+ * (pts, row_desc, idx; normals too in dpc_pca_normals) return DPC_ERR_NULL without touching a device; no rows or no
+ * queries return DPC_OK with nothing launched.  No host synchronisation, no allocation, no workspace, no atomics but
+ * the status word.  Added without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+int dpc_knn_batched(const void* pts, int n_pts, int is_f64, const int32_t* row_desc, const int32_t* host_row_desc, int rows, int k,
+                    int32_t* idx, void* d2, int32_t* status, void* stream);
+int dpc_pca_normals(const void* pts, int n_pts, int is_f64, const int32_t* row_desc, const int32_t* host_row_desc, int rows, int k,
+                    const int32_t* idx, const double* viewpoints, double* normals, double* eigenvalues, int32_t* status,
+                    void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Voxel-grid downsampling of ground-truth clouds (densify/downsample_gt.py:47-57: open3d.voxel_down_sample(pcd,

@@ -35,11 +35,17 @@ DPC_FPS_MAX_POINTS = 16384
 DPC_VOXEL_MAX_SIDE = 128
 DPC_MESH_FILL_NONE, DPC_MESH_FILL_CARVE, DPC_MESH_FILL_PARITY = 0, 1, 2
 DPC_PM_BLOCK, DPC_PM_FACE_TILE, DPC_PM_CHUNK_TILES = 256, 128, 8
+DPC_KNN_MAX_K, DPC_KNN_TILE = 64, 512
 DPC_GAUSS_NORM_NONE, DPC_GAUSS_NORM_ANALYTICAL, DPC_GAUSS_NORM_PER_POINT = 0, 1, 2
 DPC_GAUSS_MAX_SIDE = 64
 DPC_GT_RESIZE_MEAN, DPC_GT_RESIZE_SAMPLE = 0, 1
 DPC_MESH_NEAR = 1e-3
 DPC_MESH_AMBIENT, DPC_MESH_DIFFUSE = 0.25, 0.75
+
+
+def knn_block(k):
+    """DPC_KNN_BLOCK(k) of the header: the queries a workgroup of dpc_knn_batched holds."""
+    return 256 if k <= 16 else 128 if k <= 32 else 64
 
 
 class DpcParams(ctypes.Structure):
@@ -125,6 +131,8 @@ _FUNCTIONS = (
     ("dpc_surface_extract", _i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i] + [_vp] * 5),
     ("dpc_point_mesh_workspace_bytes", _sz, [_i]),
     ("dpc_point_mesh_distance", _i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("dpc_knn_batched", _i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    ("dpc_pca_normals", _i, [_vp, _i, _i, _vp, _vp, _i, _i] + [_vp] * 6),
     ("dpc_downsample_workspace_bytes", _sz, [_i, _i]),
     ("dpc_voxel_downsample", _i, [_vp, _i, _i, _vp, _vp, _i, _d] + [_vp] * 6),
     ("dpc_densify_workspace_bytes", _sz, [_i, _i64, _i64, _i64, _i]),
