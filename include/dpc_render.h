@@ -1028,6 +1028,53 @@ int dpc_point_mesh_distance(const void* points, int n_points, int points_f64, co
                             double* d2, void* workspace, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Closest points on meshes: dpc_point_mesh_distance with its argmin.  For every point, besides the squared distance, the
+ * nearest face of the row's mesh, the closest point Q of that face, Q's weights on the face's vertices and the face's
+ * unit normal.  The gradient of the squared point-to-surface distance with respect to the point is 2 (P - Q), so Q is
+ * what a surface loss needs (dpc/render/closest.py: point_surface_loss); the normal is what a mesh-based normal
+ * consistency needs.  tests/closest_oracle.py restates the rules in numpy and in exact rational arithmetic.
+ *
+ * The same points, verts, faces, pair_desc / host_pair_desc [n_pairs,6] and guards as dpc_point_mesh_distance.  Per
+ * output point (the rows' points in row order, sum point_count of them):
+ *   d2       fp64: the squared distance.  The distance to one face is dpc_point_mesh_distance's arithmetic (both kernels
+ *            inline the same functions of csrc/dpc_point_mesh.h), so d2 equals that entry point's d2.
+ *   face     int32: the index of the nearest face within the row's face range, as the caller numbered it; -1 when the
+ *            row has no usable face.  Among faces whose computed d2 are bit-equal the lowest index wins; a skipped face
+ *            (its d2 is NaN) never wins.
+ *   closest  fp64 [.,3]: Q.  Inside region (the plane foot point lies in the face): Q = P - (D.N / N.N) N.  Otherwise the
+ *            point of the nearest of the three segments (the first of equals in the order AB, AC, BC of the staged
+ *            rotation -- equal segments meet in the same point): the segment's first endpoint plus t E.  Where a weight
+ *            is exactly 1 (t = 0 or t = 1 on any of the segments), Q is that vertex itself, bit for bit.  A zero-area face is the segment or point it degenerates to, so Q lies on that.
+ *   weights  fp64 [.,3]: non-negative weights on the three vertices of faces[face] IN THE CALLER'S VERTEX ORDER (not the
+ *            staged rotation), summing to 1 up to two roundings, with Q = sum w_k V_k: (1 - s - t, s, t) mapped back
+ *            through the rotation in the inside region, (1 - t, t, 0) on the edge's two vertices otherwise.
+ *   normal   fp64 [.,3], NULL to skip: (V1 - V0) x (V2 - V0) over its length for the caller's winding of faces[face], every
+ *            operation rounded on its own (nothing fused), as numpy's elementwise arithmetic gives it; zeros when that
+ *            cross product has no length (a zero-area face).
+ * No usable face (every face of the row skipped), or a point with a NaN, infinite or >= DPC_MESH_VOXEL_MAX_COORD
+ * coordinate: d2 = +inf, face = -1, closest and weights NaN, normal zero.  The status bits are the ones
+ * dpc_point_mesh_distance sets.
+ * Kernels (csrc/dpc_closest.hip): dpc_point_mesh_distance's decomposition -- (row, DPC_PM_BLOCK points, chunk of faces)
+ *   per workgroup, DPC_PM_FACE_TILE faces staged per round -- with every lane keeping (best, arg) under a strict < while
+ *   it walks the faces in ascending order.  There is no atomic: a work item writes its lanes' pairs to its own workspace
+ *   slots [chunk][point]; a per-point epilogue reduces the chunks in ascending order with a strict <, stages the winning
+ *   face alone and writes the outputs.  The result is the same bit for bit however the faces are cut into tiles and
+ *   chunks, however the rows are ordered or batched, and whichever workgroup finishes first.
+ * workspace: dpc_point_mesh_closest_workspace_bytes(host_pair_desc, n_pairs) bytes, sized from the host table (three int32
+ *   prefixes and 12 bytes per slot; a row has point_count slots per chunk of its faces, one chunk unless the call's point
+ *   blocks would not fill the device); 0 for n_pairs <= 0, a NULL table or a table the call would refuse.
+ * Every check runs before any launch and returns what dpc_point_mesh_distance returns for the same table (DPC_ERR_SHAPE
+ * also for more than 2^31 - 1 slots); valid arguments with NULL device pointers (normal apart) return DPC_ERR_NULL without
+ * touching a device; no rows or no points return DPC_OK with nothing launched.  No host synchronisation, no allocation,
+ * no atomics but the status word's.  Added without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_point_mesh_closest_workspace_bytes(const int32_t* host_pair_desc, int n_pairs);
+int dpc_point_mesh_closest(const void* points, int n_points, int points_f64, const void* verts, int n_verts, int verts_f64,
+                           const int32_t* faces, int n_faces, const int32_t* pair_desc, const int32_t* host_pair_desc, int n_pairs,
+                           double* d2, int32_t* face, double* closest, double* weights, double* normal, void* workspace,
+                           int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Batched k-nearest-neighbour search, and surface normals from the neighbours' covariance (PCA): the building blocks of
  * the normal-consistency metric (dpc/render/normals.py).  There is no counterpart in the reference: the rules below are
  * this library's own, tests/normals_oracle.py restates them in numpy.

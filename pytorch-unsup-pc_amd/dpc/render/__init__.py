@@ -37,6 +37,7 @@ from .densify import MeshError, densify_meshes, densify_split, load_obj_mesh  # 
 from .meshvoxels import carve_voxels, solid_iou_of_split, voxelise_meshes  # noqa: F401
 from .pointmesh import fscore, fscore_of_split, point_mesh_distance  # noqa: F401
 from .normals import estimate_normals, knn_batched, normal_consistency, normal_consistency_of_split  # noqa: F401
+from .closest import closest_points_on_meshes, face_normals_at, point_surface_loss  # noqa: F401
 from .surface import augment_mesh, extract_surface, extract_surfaces, save_obj  # noqa: F401
 from .visualise import (camera_frame, read_png_any, render_point_cloud, render_point_clouds, render_split, write_png,  # noqa: F401
                         write_png_gray16, write_png_rgba)
@@ -61,6 +62,7 @@ __all__ = [
     "render_voxels", "voxelise_meshes", "carve_voxels", "solid_iou_of_split",
     "point_mesh_distance", "fscore", "fscore_of_split",
     "knn_batched", "estimate_normals", "normal_consistency", "normal_consistency_of_split",
+    "closest_points_on_meshes", "point_surface_loss", "face_normals_at",
     "extract_surfaces", "extract_surface", "augment_mesh", "save_obj",
     "load_obj_mesh", "densify_meshes", "densify_split", "MeshError",
     "camera_frame", "render_point_clouds", "render_point_cloud", "render_split", "write_png",

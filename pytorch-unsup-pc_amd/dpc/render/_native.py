@@ -131,6 +131,8 @@ _FUNCTIONS = (
     ("dpc_surface_extract", _i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i] + [_vp] * 5),
     ("dpc_point_mesh_workspace_bytes", _sz, [_i]),
     ("dpc_point_mesh_distance", _i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("dpc_point_mesh_closest_workspace_bytes", _sz, [_vp, _i]),
+    ("dpc_point_mesh_closest", _i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i] + [_vp] * 8),
     ("dpc_knn_batched", _i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     ("dpc_pca_normals", _i, [_vp, _i, _i, _vp, _vp, _i, _i] + [_vp] * 6),
     ("dpc_downsample_workspace_bytes", _sz, [_i, _i]),

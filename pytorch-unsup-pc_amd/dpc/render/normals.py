@@ -17,6 +17,7 @@ import torch
 from . import _batch, _native
 from ._ops import status_word
 from .chamfer import _host_unit_quaternion, _prediction, _rotate, nearest_batched
+from .closest import _ClosestPlan
 from .pointmesh import _index_map
 
 _WHAT = "dpc.render normal estimation"
@@ -200,6 +201,14 @@ def _given_normals(normals, clouds, fn, name, cloud_name):
     return out
 
 
+def _check_gt_meshes(gt_meshes, gt_normals, gts, fn):
+    """gt_meshes stands in for gt_normals, one mesh per GT cloud."""
+    if gt_normals is not None:
+        raise ValueError("%s: give gt_normals or gt_meshes, not both" % fn)
+    if len(gt_meshes) != len(gts):
+        raise ValueError("%s: %d GT clouds and %d GT meshes" % (fn, len(gts), len(gt_meshes)))
+
+
 def _dot_abs(a, b):
     """|a . b| per row, elementwise in fp64 in a fixed order: the value of a point does not depend on its neighbours in
     the batch."""
@@ -209,7 +218,7 @@ def _dot_abs(a, b):
 class _ConsistencyPlan:
     """Every host check of a normal_consistency call."""
 
-    def __init__(self, preds, gts, gt_of, k, pred_normals, gt_normals, fn):
+    def __init__(self, preds, gts, gt_of, k, pred_normals, gt_normals, fn, gt_meshes=None):
         self.fn, self.k = fn, _check_k(k, fn)
         self.preds = [_batch.cloud(p, "%s: preds[%d]" % (fn, i)) for i, p in enumerate(preds)]
         self.gts = [_batch.cloud(g, "%s: gts[%d]" % (fn, i)) for i, g in enumerate(gts)]
@@ -220,18 +229,23 @@ class _ConsistencyPlan:
         self.pred_normals = _given_normals(pred_normals, self.preds, fn, "pred_normals", "preds")
         self.gt_normals = _given_normals(gt_normals, self.gts, fn, "gt_normals", "gts")
         self.used = sorted(set(self.gt_of))
-        self.pred_plan = self.gt_plan = None
+        self.pred_plan = self.gt_plan = self.mesh_plan = None
+        self.meshes = gt_meshes
+        if gt_meshes is not None:
+            _check_gt_meshes(gt_meshes, gt_normals, self.gts, fn)
+            self.mesh_plan = _ClosestPlan(self.gts, gt_meshes, None, fn, "gts")   # face_normals_at(gts, gt_meshes), checked
         if self.pred_normals is None:
             self.pred_plan = _NormalsPlan(self.preds, self.k, None, fn, "preds")
         else:
             _refuse_nonfinite(self.preds, ["preds[%d]" % i for i in range(len(self.preds))], fn, True)
-        if self.gt_normals is None:   # once per GT cloud that a prediction names, not once per view
+        if self.gt_normals is None and self.mesh_plan is None:   # once per GT cloud that a prediction names, not once per view
             self.gt_plan = _NormalsPlan([self.gts[j] for j in self.used], self.k, None, fn, "gts", self.used)
         else:
             _refuse_nonfinite(self.gts, ["gts[%d]" % i for i in range(len(self.gts))], fn, True)
 
     def tensors(self):
-        return [self.preds, self.gts, self.pred_normals or [], self.gt_normals or []]
+        return [self.preds, self.gts, self.pred_normals or [], self.gt_normals or [],
+                [] if self.meshes is None else [x for m in self.meshes for x in m[:2]]]
 
     def run(self, dev):
         P = len(self.preds)
@@ -239,7 +253,9 @@ class _ConsistencyPlan:
         if P == 0:
             return out
         n_pred = self.pred_normals if self.pred_plan is None else self.pred_plan.run(dev, False)[0]
-        if self.gt_plan is None:
+        if self.mesh_plan is not None:   # face_normals_at(gts, gt_meshes): the normal of the face each GT sample lies on
+            n_gt = dict(enumerate(self.mesh_plan.split(self.mesh_plan.closest(dev, True)[4])))
+        elif self.gt_plan is None:
             n_gt = {j: self.gt_normals[j] for j in self.used}
         else:
             n_gt = dict(zip(self.used, self.gt_plan.run(dev, False)[0]))
@@ -288,7 +304,7 @@ class _ConsistencyPlan:
         return torch.cat([ab, ((ab[:, 0] + ab[:, 1]) / 2.0)[:, None]], dim=1)
 
 
-def normal_consistency(preds, gts, gt_of=None, k=16, pred_normals=None, gt_normals=None):
+def normal_consistency(preds, gts, gt_of=None, k=16, pred_normals=None, gt_normals=None, gt_meshes=None):
     """The normal consistency of every prediction against its ground truth: [P,3] float64 on the device, (a, b, (a + b) / 2)
     per prediction, each in [0, 1], 1 where the surfaces face the same way up to sign.
 
@@ -296,20 +312,26 @@ def normal_consistency(preds, gts, gt_of=None, k=16, pred_normals=None, gt_norma
     points of |Ng[l] . Np[nearest predicted point of G_l]|.  preds, gts: lists of [n,3] tensors or arrays; gt_of: the GT
     index of each prediction (default i -> i), as in chamfer_batched, whose precision rule applies to the nearest-neighbour
     searches (nearest_batched's).  pred_normals / gt_normals: one [n,3] array of normals per prediction / per GT cloud;
-    those not supplied are estimated with estimate_normals(k) -- the GT's once per GT cloud, not once per view.  The means
+    those not supplied are estimated with estimate_normals(k) -- the GT's once per GT cloud, not once per view.
+    gt_meshes: one (V, F, ...) per GT cloud, as point_mesh_distance takes them -- the GT normals are then
+    face_normals_at(gts, gt_meshes), the unit normal of the mesh face nearest to each GT point (for a cloud sampled from
+    its mesh, the face it lies on), as published single-view reconstruction numbers take them, instead of the PCA
+    estimate; giving both gt_normals and gt_meshes is a ValueError.  The means
     are dpc_chamfer_pair_means over the packed |dot| values, so they are bit-reproducible and do not depend on how the
     predictions are grouped.  A zero normal contributes 0; an empty prediction gives NaN.  Every argument is checked
     before a device is looked for; ValueError for a NaN or inf coordinate, naming the cloud."""
-    plan = _ConsistencyPlan(preds, gts, gt_of, k, pred_normals, gt_normals, "normal_consistency")
+    plan = _ConsistencyPlan(preds, gts, gt_of, k, pred_normals, gt_normals, "normal_consistency", gt_meshes)
     return plan.run(_batch.device(_WHAT, *plan.tensors()))
 
 
-def normal_consistency_of_split(predictions, gt_clouds, gt_normals=None, k=16, reference_rotation=None, models_per_call=256):
+def normal_consistency_of_split(predictions, gt_clouds, gt_normals=None, k=16, reference_rotation=None, models_per_call=256,
+                                gt_meshes=None):
     """normal_consistency for every view of M models: [M,V,3] float64 numpy.
 
     predictions, gt_clouds, reference_rotation and models_per_call as in fscore_of_split (view i is truncated to its first
     num_points[i] points, the rotation is applied to every view first); gt_normals: one [n,3] array per model, estimated
-    with k when not given, once per model.  The predictions' normals are always estimated with k.  The result does not
+    with k when not given, once per model; gt_meshes: one mesh per model instead, as in normal_consistency (the GT normals
+    are the mesh faces').  The predictions' normals are always estimated with k.  The result does not
     depend on the grouping.  Every argument is checked before anything is launched."""
     fn = "normal_consistency_of_split"
     if len(predictions) != len(gt_clouds):
@@ -333,10 +355,16 @@ def normal_consistency_of_split(predictions, gt_clouds, gt_normals=None, k=16, r
     _refuse_nonfinite(gts, ["gt_clouds[%d]" % m for m in range(len(gts))], fn, True)
     qn = None if reference_rotation is None else _host_unit_quaternion(reference_rotation)
     M = len(preds)
+    if gt_meshes is not None:
+        # The meshes' own checks and the dry run of every group's table.  normal_consistency builds the same plan again
+        # for each group; building them here first is what makes every refusal come before the first group is launched.
+        _check_gt_meshes(gt_meshes, gt_normals, gts, fn)
+        for a in range(0, M, step):
+            _ClosestPlan(gts[a:a + step], gt_meshes[a:a + step], None, fn, "gt_clouds")
     out = np.zeros((M, V, 3), dtype=np.float64)
     if M == 0 or V == 0:
         return out
-    dev = _batch.device(_WHAT, [p for p, _ in preds], gts)
+    dev = _batch.device(_WHAT, [p for p, _ in preds], gts, [] if gt_meshes is None else [x for m in gt_meshes for x in m[:2]])
     for a in range(0, M, step):
         group = range(a, min(M, a + step))
         views_list, gt_of = [], []
@@ -348,6 +376,7 @@ def normal_consistency_of_split(predictions, gt_clouds, gt_normals=None, k=16, r
                 views_list.append(pts[i] if nums is None else pts[i, :int(nums[i])])
                 gt_of.append(j)
         res = normal_consistency(views_list, [gts[m] for m in group], gt_of, k, None,
-                                 None if given is None else [given[m] for m in group])
+                                 None if given is None else [given[m] for m in group],
+                                 None if gt_meshes is None else [gt_meshes[m] for m in group])
         out[a:a + len(group)] = res.cpu().numpy().reshape(len(group), V, 3)
     return out

@@ -68,12 +68,10 @@ class _Plan:
     def tensors(self):
         return self.clouds, [V for V, _ in self.items]
 
-    def run(self, dev):
-        """The packed squared distances [sum n_i] float64 on dev, in cloud order: one native call."""
+    def packed(self, dev):
+        """The leading arguments both point-to-mesh entry points take, points to n_pairs, on dev (the tuple keeps the
+        packed tensors alive), after the one finiteness check of the points.  Needs at least one point."""
         n_pts, n_verts, n_faces = self.sizes
-        d2 = torch.empty((n_pts,), dtype=torch.float64, device=dev)
-        if n_pts == 0:
-            return d2
         pdt, vdt = _batch.widest(self.clouds), _batch.widest(V for V, _ in self.items)
         pts, _ = _batch.pack(self.clouds, dev, pdt)
         if not bool(torch.isfinite(pts).all()):
@@ -83,10 +81,18 @@ class _Plan:
         verts, _ = _batch.pack([V for V, _ in self.items], dev, vdt)
         faces = torch.from_numpy(np.concatenate([F for _, F in self.items]).reshape(-1, 3)).to(dev)
         desc_d = _batch.on_device(self.desc, dev)
+        keep = (pts, verts, faces, desc_d)
+        return keep, (_native.ptr(pts), n_pts, int(pdt == torch.float64), _native.ptr(verts), n_verts, int(vdt == torch.float64),
+                      _native.ptr(faces), n_faces, _native.ptr(desc_d), self.desc.ctypes.data, len(self.desc))
+
+    def run(self, dev):
+        """The packed squared distances [sum n_i] float64 on dev, in cloud order: one native call."""
+        d2 = torch.empty((self.sizes[0],), dtype=torch.float64, device=dev)
+        if self.sizes[0] == 0:
+            return d2
+        keep, args = self.packed(dev)
         ws = _batch.workspace(_native.lib().dpc_point_mesh_workspace_bytes(len(self.desc)), dev)
-        _native.call(dev, "dpc_point_mesh_distance", _native.ptr(pts), n_pts, int(pdt == torch.float64), _native.ptr(verts),
-                     n_verts, int(vdt == torch.float64), _native.ptr(faces), n_faces, _native.ptr(desc_d), self.desc.ctypes.data,
-                     len(self.desc), _native.ptr(d2), _native.ptr(ws), _native.ptr(status_word(dev)))
+        _native.call(dev, "dpc_point_mesh_distance", *args, _native.ptr(d2), _native.ptr(ws), _native.ptr(status_word(dev)))
         return d2
 
 
