@@ -61,6 +61,8 @@ extern "C" {
 #define DPC_PM_BLOCK 256
 #define DPC_PM_FACE_TILE 128
 #define DPC_PM_CHUNK_TILES 8
+/* dpc_mesh_winding: the fractional bits of a face's quantised term, and so of the int64 sums (the unit is 2^-40). */
+#define DPC_WINDING_FRAC_BITS 40
 /* dpc_knn_batched / dpc_pca_normals: the most neighbours per query, and the references a workgroup stages in LDS per
  * round.  A workgroup holds DPC_KNN_BLOCK(k) queries, one lane each: 256 for k <= 16, 128 for k <= 32, 64 above, so that
  * the lanes' sorted lists (k slots of a d2 and an int32 each) fit next to the tile. */
@@ -1073,6 +1075,63 @@ int dpc_point_mesh_closest(const void* points, int n_points, int points_f64, con
                            const int32_t* faces, int n_faces, const int32_t* pair_desc, const int32_t* host_pair_desc, int n_pairs,
                            double* d2, int32_t* face, double* closest, double* weights, double* normal, void* workspace,
                            int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Generalized winding numbers: which side of a mesh a point is on.  w(P) = (1 / 4 pi) sum over the faces of the signed
+ * solid angle Omega_f(P) of face f seen from P: 1 inside and 0 outside a closed mesh wound outward, a smooth "how much
+ * inside" for a triangle soup (open, self-intersecting, inconsistently closed); no connectivity is used.  There is no
+ * counterpart in the reference: the rules below are this library's own, tests/winding_oracle.py restates them in numpy
+ * and at 50 digits.  All arithmetic is fp64 (fp32 points and vertices widen exactly first); products and sums may be
+ * fused.
+ *
+ * One face, vertices (V0, V1, V2) in the caller's order, seen from P:
+ *   a = V0 - P, b = V1 - P, c = V2 - P;  det = a . (b x c);  den = |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|;
+ *   t = atan2(det, den) / (2 pi) = Omega / 4 pi, in [-1/2, 1/2]; t = 0 when det == 0 (P in the face's plane, P on a
+ *   vertex, a zero-area face), whatever the sign of that zero.
+ * Fixed-point sum.  Each term is quantised, q = llrint(t 2^DPC_WINDING_FRAC_BITS), the terms of a point are added in
+ *   int64, and w = (double)sum 2^-DPC_WINDING_FRAC_BITS.  Integer addition is associative: the result is the same bit for
+ *   bit however the faces are cut into tiles and chunks, however the rows are ordered or batched, and whichever workgroup
+ *   finishes first.  |q| <= 2^39, so a row with more than 2^22 faces is refused (DPC_ERR_SHAPE).  Away from the
+ *   surface a term is right to about 1e-16 against the quantum 2^-40 ~ 9e-13, so a sum is within one quantum per usable
+ *   face of the sum of the exactly evaluated, quantised terms.
+ * dpc_mesh_winding.  The leading arguments, the table pair_desc / host_pair_desc [n_pairs,6] and the guards of
+ *   dpc_point_mesh_distance: a face with a NaN, infinite or >= DPC_MESH_VOXEL_MAX_COORD vertex is skipped (its term is 0)
+ *   and sets DPC_STATUS_NONFINITE; a face with an index outside its row's vertices is skipped and sets
+ *   DPC_STATUS_BAD_INDEX: it never becomes an address; a point with such a coordinate gets sum 0, w = NaN and
+ *   DPC_STATUS_NONFINITE; a device-table row outside its arrays sets DPC_STATUS_BAD_INDEX and nothing of it is read or
+ *   written.  sums int64 [sum point_count] and winding fp64 [sum point_count], the rows' points in row order; either may
+ *   be NULL, not both.  workspace: dpc_mesh_winding_workspace_bytes(host_pair_desc, n_pairs) bytes, sized from the host
+ *   table (three int32 prefixes and 8 bytes per slot; a row has point_count slots per chunk of its faces); 0 for
+ *   n_pairs <= 0, a NULL table or a table the call would refuse.
+ * dpc_mesh_winding_voxels.  The same sum for the node centres of one [D,H,W] grid per mesh, formed in the kernel (no
+ *   [M D H W, 3] array exists anywhere): verts, faces, mesh_desc / host_mesh_desc [meshes,4] as dpc_voxelise_meshes takes
+ *   them, 2 <= D, H, W <= DPC_VOXEL_MAX_SIDE; node n of axis c, of G_c nodes, sits at n / (G_c - 1) - 1/2, the division
+ *   and the subtraction each rounded on its own: dpc_voxelise_meshes' frame.  bits uint32 [meshes, ceil(D H W / 32)],
+ *   dpc_voxelise's layout; every word is written.  A bit is set iff sum > threshold_q, an integer compare
+ *   (threshold_q = llrint(threshold 2^40)); a mesh without faces gives an empty grid whatever the threshold.  Face
+ *   guards as above; a device-table row outside its arrays sets DPC_STATUS_BAD_INDEX and its words are not written.
+ *   workspace: dpc_mesh_winding_voxels_workspace_bytes(host_mesh_desc, meshes, D, H, W) bytes (8 bytes per slot, D H W
+ *   slots per mesh and chunk of the largest mesh's faces); 0 for what the call would refuse.  DPC_ERR_SHAPE also for a
+ *   mesh of more than 2^22 faces and for more than 2^31 - 1 work items, slots or words.
+ * Kernels (csrc/dpc_winding.hip): dpc_point_mesh_distance's decomposition -- a lane owns a point or a node, a workgroup of
+ *   DPC_PM_BLOCK lanes stages DPC_PM_FACE_TILE faces per round in LDS, nine doubles a face, widened once there; a call
+ *   whose point blocks alone would not fill the device splits the face ranges into chunks of whole tiles, at least
+ *   DPC_PM_CHUNK_TILES each.  A work item writes its lanes' partial sums to its own workspace slots [chunk][point]; an
+ *   epilogue adds a point's slots and writes the outputs (for a grid: compares and packs the bits).
+ * Every check runs before any launch and dpc_mesh_winding returns what dpc_point_mesh_distance returns for the same
+ * table (DPC_ERR_SHAPE also for a row of more than 2^22 faces and for more than 2^31 - 1 slots); valid arguments with
+ * NULL device pointers return DPC_ERR_NULL without touching a device; nothing to do returns DPC_OK with nothing launched.
+ * No host synchronisation, no allocation, no atomics but the status word's.  Added without a new ABI number: no existing
+ * entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_mesh_winding_workspace_bytes(const int32_t* host_pair_desc, int n_pairs);
+int dpc_mesh_winding(const void* points, int n_points, int points_f64, const void* verts, int n_verts, int verts_f64,
+                     const int32_t* faces, int n_faces, const int32_t* pair_desc, const int32_t* host_pair_desc, int n_pairs,
+                     int64_t* sums, double* winding, void* workspace, int32_t* status, void* stream);
+size_t dpc_mesh_winding_voxels_workspace_bytes(const int32_t* host_mesh_desc, int meshes, int D, int H, int W);
+int dpc_mesh_winding_voxels(const void* verts, int n_verts, int is_f64, const int32_t* faces, int n_faces, const int32_t* mesh_desc,
+                            const int32_t* host_mesh_desc, int meshes, int D, int H, int W, int64_t threshold_q, uint32_t* bits,
+                            void* workspace, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Batched k-nearest-neighbour search, and surface normals from the neighbours' covariance (PCA): the building blocks of
