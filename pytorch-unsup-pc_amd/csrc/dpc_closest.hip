@@ -4,16 +4,17 @@
 // and pm_d2 of dpc_point_mesh.h, so d2 here equals d2 there.
 //
 // k_pm_scan<1>   the distance's scan (dpc_point_mesh.h), which here also builds the per-row prefix of workspace slots.
-// k_pc_arg<fp64 points, fp64 vertices>   k_pm_dist's decomposition: one workgroup of DPC_PM_BLOCK lanes per work item (row,
-//     block of points, chunk of faces), a lane owns one point, DPC_PM_FACE_TILE faces staged in LDS per round and read by
-//     every lane as a broadcast.  A lane walks its chunk's faces in ascending order and keeps (best, arg) with a strict <:
-//     one compare and two selects on top of pm_d2's 80 operations, the lowest index among equal d2, and a NaN (a skipped
-//     face) never wins.  The lane's pair goes to the workspace slot [chunk][point] of its row, which no other lane writes:
-//     there is no atomic, and no slot is read before the kernel has ended.
+// k_pc_arg<fp64 points, fp64 vertices>   k_pm_dist's decomposition, from pm_item and pm_walk of dpc_point_mesh.h: one
+//     workgroup of DPC_PM_BLOCK lanes per work item (row, block of points, chunk of faces), a lane owns one point,
+//     DPC_PM_FACE_TILE faces staged in LDS per round and read by every lane as a broadcast.  A lane walks its chunk's
+//     faces in ascending order and keeps (best, arg) with a strict <: one compare and two selects on top of pm_d2's 80
+//     operations, the lowest index among equal d2, and a NaN (a skipped face) never wins.  The lane's pair goes to the
+//     workspace slot [chunk][point] of its row, which no other lane writes: there is no atomic, and no slot is read
+//     before the kernel has ended.
 // k_pc_finish<fp64 points, fp64 vertices>   one lane per output point: reduces the point's slots in ascending chunk order
-//     with a strict < (so the lowest face index among equal d2 wins whatever the chunk size), stages the winning face
-//     alone, decides its region with pm_d2's own terms and writes d2, face, Q, the weights in the caller's vertex order
-//     and the normal.
+//     with a strict < (so the lowest face index among equal d2 wins whatever the chunk size), fetches the winning face's
+//     vertices once (pm_fetch) for its record and its normal, decides its region with pm_d2's own terms and writes d2,
+//     face, Q, the weights in the caller's vertex order and the normal.
 // The result depends on neither the chunk size, nor the batching, nor the order in which workgroups run.
 // Every index is checked against the device table before it becomes an address; every loop is bounded by a checked count.
 #include <hip/hip_runtime.h>
@@ -25,27 +26,15 @@
 
 namespace {
 
-struct PcWork {
-  int32_t* work;   // [pairs + 1] exclusive prefix of work items
-  int32_t* out;    // [pairs + 1] exclusive prefix of output points
-  int32_t* slot;   // [pairs + 1] exclusive prefix of workspace slots: a row has chunks * points of them
-  double* best;    // [slots]
-  int32_t* arg;    // [slots]
+struct PcWork : PmWork {   // a row has chunks * points slots
+  double* best;            // [slots]
+  int32_t* arg;            // [slots]
 };
-
-// slots of a host table that pm_check has accepted
-int64_t pc_slots(int pairs, const int32_t* desc, int chunk) {
-  int64_t n = 0;
-  for (int p = 0; p < pairs; ++p) n += (int64_t)desc[6 * p + 1] * pm_chunks(desc[6 * p + 1], desc[6 * p + 5], chunk);
-  return n;
-}
 
 size_t pc_carve(int pairs, int64_t slots, char* base, PcWork* w) {
   Carver c{base};
   PcWork t;
-  t.work = c.take<int32_t>((size_t)pairs + 1);
-  t.out = c.take<int32_t>((size_t)pairs + 1);
-  t.slot = c.take<int32_t>((size_t)pairs + 1);
+  static_cast<PmWork&>(t) = pm_carve<1>(c, pairs);
   t.best = c.take<double>((size_t)slots);
   t.arg = c.take<int32_t>((size_t)slots);
   if (w) *w = t;
@@ -57,58 +46,29 @@ __global__ __launch_bounds__(kPmBlock) void k_pc_arg(const void* __restrict__ pt
                                                      int n_verts, const int32_t* __restrict__ faces, int n_faces,
                                                      const int32_t* __restrict__ desc, int pairs, int chunk, PcWork pre, int n_slots,
                                                      int32_t* __restrict__ status) {
-  using T = std::conditional_t<PF64 != 0, double, float>;
   __shared__ double2 tile[kPmTile * kPmRec];
-  const int t = threadIdx.x;
-  const int item = blockIdx.x;
-  if (item >= pre.work[pairs]) return;
-  const int p = owner(pre.work, pairs, item);
-  PmRow r;
-  if (!pm_row(desc, p, n_pts, n_verts, n_faces, &r)) return;   // k_pm_scan has reported it
-  const int nb = pm_blocks(r.np), nc = pm_chunks(r.np, r.nf, chunk);
-  const int local = item - pre.work[p];
-  if (local < 0 || (int64_t)local >= (int64_t)nb * nc) return;
-  const int b = local % nb, c = local / nb;   // the point blocks of one chunk are adjacent: they read the same faces
-  const int i = b * kPmBlock + t;
-  const bool live = i < r.np;
-  const int f0 = c * chunk;                                    // < nf
-  const int f1 = r.nf - f0 < chunk ? r.nf : f0 + chunk;
-  double px = 0.0, py = 0.0, pz = 0.0;
-  if (live) {
-    const T* q = static_cast<const T*>(pts_) + 3 * ((size_t)r.ps + i);
-    px = (double)q[0]; py = (double)q[1]; pz = (double)q[2];
-  }
-  int flags = 0;
-  const bool finite = fabs(px) < DPC_MESH_VOXEL_MAX_COORD && fabs(py) < DPC_MESH_VOXEL_MAX_COORD && fabs(pz) < DPC_MESH_VOXEL_MAX_COORD;
-  if (!finite) {
-    flags = kPmNonFinite;
-    px = py = pz = 0.0;
-  }
+  PmItem it;
+  if (!pm_item<PF64>(pts_, n_pts, n_verts, n_faces, desc, pairs, chunk, pre, &it)) return;
   double best = std::numeric_limits<double>::infinity();
   int arg = -1;
-  for (int base = f0; base < f1; base += kPmTile) {   // the same trip count in every thread: barriers inside
-    const int n = f1 - base < kPmTile ? f1 - base : kPmTile;
-    __syncthreads();
-    if (t < n) flags |= pm_stage<VF64>(verts, faces, r, base + t, tile + t * kPmRec);
-    __syncthreads();
-#pragma unroll 2
-    for (int k = 0; k < n; ++k) {
-      const double d = pm_d2(tile + k * kPmRec, px, py, pz);
-      const bool wins = d < best;   // false for a NaN and for an equal d2: the lower index stays
-      best = wins ? d : best;
-      arg = wins ? base + k : arg;
-    }
-  }
-  if (!finite) {
+  pm_walk<kPmRec>(
+      it.f0, it.f1, tile, &it.flags, [&](int f, double2* rec) { return pm_stage<VF64>(verts, faces, it.r, f, rec); },
+      [&](int f, const double2* rec) {
+        const double d = pm_d2(rec, it.px, it.py, it.pz);
+        const bool wins = d < best;   // false for a NaN and for an equal d2: the lower index stays
+        best = wins ? d : best;
+        arg = wins ? f : arg;
+      });
+  if (!it.finite) {
     best = std::numeric_limits<double>::infinity();
     arg = -1;
   }
-  const int64_t s = (int64_t)pre.slot[p] + (int64_t)c * r.np + i;
-  if (live && s >= 0 && s < n_slots) {
+  const int64_t s = pm_slot(pre, it.p, it.r.np, it.c, it.i, n_slots);
+  if (it.live && s >= 0) {
     pre.best[s] = best;
     pre.arg[s] = arg;
   }
-  if (flags && status) atomicOr(status, (flags & kPmBadIndex ? (int)DPC_STATUS_BAD_INDEX : 0) | (flags & kPmNonFinite ? (int)DPC_STATUS_NONFINITE : 0));
+  pm_report(it.flags, status);
 }
 
 // The unit normal of (v0, v1, v2) in that winding, (v1 - v0) x (v2 - v0) over its length, each operation rounded on its
@@ -167,27 +127,22 @@ __device__ inline void pc_closest(const double2* __restrict__ rec, const double*
 }
 
 template <int PF64, int VF64>
-__global__ __launch_bounds__(256) void k_pc_finish(const void* __restrict__ pts_, int n_pts, const void* __restrict__ verts_, int n_verts,
-                                                   const int32_t* __restrict__ faces, int n_faces, const int32_t* __restrict__ desc,
-                                                   int pairs, int chunk, PcWork pre, int n_slots, int n_out, double* __restrict__ d2,
-                                                   int32_t* __restrict__ face, double* __restrict__ closest,
-                                                   double* __restrict__ weights, double* __restrict__ normal) {
+__global__ __launch_bounds__(kPmOutBlock) void k_pc_finish(const void* __restrict__ pts_, int n_pts, const void* __restrict__ verts,
+                                                           int n_verts, const int32_t* __restrict__ faces, int n_faces,
+                                                           const int32_t* __restrict__ desc, int pairs, int chunk, PcWork pre,
+                                                           int n_slots, int n_out, double* __restrict__ d2, int32_t* __restrict__ face,
+                                                           double* __restrict__ closest, double* __restrict__ weights,
+                                                           double* __restrict__ normal) {
   using T = std::conditional_t<PF64 != 0, double, float>;
-  using TV = std::conditional_t<VF64 != 0, double, float>;
-  const int64_t o64 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (o64 >= n_out || o64 >= pre.out[pairs]) return;
-  const int o = (int)o64;
-  const int p = owner(pre.out, pairs, o);
-  PmRow r;
-  if (!pm_row(desc, p, n_pts, n_verts, n_faces, &r)) return;
-  const int i = o - pre.out[p];
-  if (i < 0 || i >= r.np) return;
-  const int nc = pm_chunks(r.np, r.nf, chunk);   // <= nf
+  PmOut out;
+  if (!pm_out(n_pts, n_verts, n_faces, desc, pairs, chunk, pre, n_out, &out)) return;
+  const PmRow& r = out.r;
+  const int o = out.o, i = out.i;
   double best = std::numeric_limits<double>::infinity();
   int arg = -1;
-  for (int c = 0; c < nc; ++c) {   // ascending chunks hold ascending faces: strict < keeps the lowest index
-    const int64_t s = (int64_t)pre.slot[p] + (int64_t)c * r.np + i;
-    if (s < 0 || s >= n_slots) continue;
+  for (int c = 0; c < out.nc; ++c) {   // ascending chunks hold ascending faces: strict < keeps the lowest index
+    const int64_t s = pm_slot(pre, out.p, r.np, c, i, n_slots);
+    if (s < 0) continue;
     const double b = pre.best[s];
     const int a = pre.arg[s];
     const bool wins = b < best;
@@ -196,18 +151,11 @@ __global__ __launch_bounds__(256) void k_pc_finish(const void* __restrict__ pts_
   }
   const double nan = std::numeric_limits<double>::quiet_NaN();
   double q[3] = {nan, nan, nan}, w[3] = {nan, nan, nan}, n[3] = {0.0, 0.0, 0.0};
-  double2 rec[kPmRec];
-  int rot = 0;
-  if ((unsigned)arg < (unsigned)r.nf && pm_stage<VF64>(verts_, faces, r, arg, rec, &rot) == 0) {
-    // pm_stage has checked the three indices against the row's vertex count
-    const int32_t* f = faces + 3 * ((size_t)r.fs + arg);
-    double v[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const TV* x = static_cast<const TV*>(verts_) + 3 * ((size_t)r.vs + f[k]);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) v[k][c] = (double)x[c];
-    }
+  double2 rec[kPmRec];   // for a skipped face only pm_fetch's NaN target: nothing reads it then
+  double v[3][3];
+  if ((unsigned)arg < (unsigned)r.nf && pm_fetch<VF64, kPmRec>(verts, faces, r, arg, v, rec) == 0) {
+    int rot = 0;
+    pm_record(v, rec, &rot);
     const T* x = static_cast<const T*>(pts_) + 3 * ((size_t)r.ps + i);
     const int ib = rot == 0 ? 1 : rot == 1 ? 2 : 0;
     double B[3], ws[3];
@@ -242,24 +190,10 @@ int pc_launch(const void* pts, int n_pts, const void* verts, int n_verts, const 
               double* normal, int32_t* status, hipStream_t st) {
   DPC_LAUNCH("k_pc_arg", dpc_kid("k_pc_arg", PF64, VF64), (k_pc_arg<PF64, VF64>), dim3((unsigned)g.work), dim3(kPmBlock), 0, st, pts,
              n_pts, verts, n_verts, faces, n_faces, desc, pairs, g.chunk, w, (int)slots, status);
-  DPC_LAUNCH("k_pc_finish", dpc_kid("k_pc_finish", PF64, VF64), (k_pc_finish<PF64, VF64>), dim3((unsigned)((g.points + 255) / 256)),
-             dim3(256), 0, st, pts, n_pts, verts, n_verts, faces, n_faces, desc, pairs, g.chunk, w, (int)slots, (int)g.points, d2, face,
-             closest, weights, normal);
+  DPC_LAUNCH("k_pc_finish", dpc_kid("k_pc_finish", PF64, VF64), (k_pc_finish<PF64, VF64>),
+             dim3((unsigned)((g.points + kPmOutBlock - 1) / kPmOutBlock)), dim3(kPmOutBlock), 0, st, pts, n_pts, verts, n_verts, faces,
+             n_faces, desc, pairs, g.chunk, w, (int)slots, (int)g.points, d2, face, closest, weights, normal);
   return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
-}
-
-// the checks of both entry points: DPC_OK with the geometry and the slot count, or the code to return
-int pc_plan(int n_points, int n_verts, int n_faces, const int32_t* host_pair_desc, int n_pairs, PmGeom* g, int64_t* slots, int64_t* total) {
-  if (n_points < 0 || n_verts < 0 || n_faces < 0 || n_pairs < 0) return DPC_ERR_SHAPE;
-  *g = PmGeom{0, 0, 0, kPmTile * DPC_PM_CHUNK_TILES};
-  *slots = *total = 0;
-  if (n_pairs == 0) return DPC_OK;
-  if (!host_pair_desc) return DPC_ERR_NULL;
-  const int rc = pm_check(n_pairs, host_pair_desc, n_points, n_verts, n_faces, total);
-  if (rc != DPC_OK) return rc;
-  *g = pm_geometry(n_pairs, host_pair_desc);
-  *slots = pc_slots(n_pairs, host_pair_desc, g->chunk);
-  return g->work > INT32_MAX || *slots > INT32_MAX ? DPC_ERR_SHAPE : DPC_OK;
 }
 
 }  // namespace
@@ -270,7 +204,7 @@ size_t dpc_point_mesh_closest_workspace_bytes(const int32_t* host_pair_desc, int
   if (n_pairs <= 0 || !host_pair_desc) return 0;
   PmGeom g;
   int64_t slots, total;
-  if (pc_plan(INT32_MAX, INT32_MAX, INT32_MAX, host_pair_desc, n_pairs, &g, &slots, &total) != DPC_OK) return 0;
+  if (pm_plan(INT32_MAX, INT32_MAX, INT32_MAX, host_pair_desc, n_pairs, INT32_MAX, &g, &slots, &total) != DPC_OK) return 0;
   return pc_carve(n_pairs, slots, nullptr, nullptr);
 }
 
@@ -280,7 +214,7 @@ int dpc_point_mesh_closest(const void* points, int n_points, int points_f64, con
                            int32_t* status, void* stream) {
   PmGeom g;
   int64_t slots, total;
-  const int rc = pc_plan(n_points, n_verts, n_faces, host_pair_desc, n_pairs, &g, &slots, &total);
+  const int rc = pm_plan(n_points, n_verts, n_faces, host_pair_desc, n_pairs, INT32_MAX, &g, &slots, &total);
   if (rc != DPC_OK) return rc;
   if (n_pairs == 0 || total == 0) return DPC_OK;
   if (!points || !verts || !faces || !pair_desc || !d2 || !face || !closest || !weights || !workspace) return DPC_ERR_NULL;
@@ -289,15 +223,10 @@ int dpc_point_mesh_closest(const void* points, int n_points, int points_f64, con
   pc_carve(n_pairs, slots, static_cast<char*>(workspace), &w);
   DPC_LAUNCH("k_pm_scan", dpc_kid("k_pm_scan", 1), (k_pm_scan<1>), dim3(1), dim3(kPmScanThreads), 0, st, pair_desc, n_pairs, n_points,
              n_verts, n_faces, g.chunk, w.work, w.out, w.slot, status);
-  if (points_f64)
-    return verts_f64 ? pc_launch<1, 1>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w, slots, d2, face,
-                                       closest, weights, normal, status, st)
-                     : pc_launch<1, 0>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w, slots, d2, face,
-                                       closest, weights, normal, status, st);
-  return verts_f64 ? pc_launch<0, 1>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w, slots, d2, face,
-                                     closest, weights, normal, status, st)
-                   : pc_launch<0, 0>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w, slots, d2, face,
-                                     closest, weights, normal, status, st);
+  return pm_dispatch(points_f64, verts_f64, [&](auto pf, auto vf) {
+    return pc_launch<decltype(pf)::value, decltype(vf)::value>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w,
+                                                               slots, d2, face, closest, weights, normal, status, st);
+  });
 }
 
 }  // extern "C"

@@ -23,6 +23,9 @@
 //     atomic min: a non-negative double orders like its bit pattern, min is exact and order-free, so the result does not
 //     depend on how the faces were split or on which workgroup arrives first.
 // A row with few points and many faces is split over chunks of faces so that the call fills the device (pm_geometry).
+// The decomposition is dpc_point_mesh.h's, which dpc_closest.hip and dpc_winding.hip use through pm_item (the prologue)
+// and pm_walk (the tile loop).  k_pm_dist keeps both written out, to be kept in step with them: over the two helpers it
+// came out at 80 VGPRs for 81, so 6 waves per SIMD for 5, and 0.9 to 1.3 % slower on large batches (LAB_NOTES.md, 21).
 // Every index is checked against the device table before it becomes an address; every loop is bounded by a checked count.
 #include <hip/hip_runtime.h>
 
@@ -33,16 +36,9 @@
 
 namespace {
 
-struct PmWork {
-  int32_t* work;   // [pairs + 1] exclusive prefix of work items
-  int32_t* out;    // [pairs + 1] exclusive prefix of output points
-};
-
-size_t pm_carve(int pairs, char* base, PmWork* w) {
+size_t pm_workspace(int pairs, char* base, PmWork* w) {
   Carver c{base};
-  PmWork t;
-  t.work = c.take<int32_t>((size_t)pairs + 1);
-  t.out = c.take<int32_t>((size_t)pairs + 1);
+  const PmWork t = pm_carve<0>(c, pairs);
   if (w) *w = t;
   return c.off + 16;
 }
@@ -97,7 +93,7 @@ __global__ __launch_bounds__(kPmBlock) void k_pm_dist(const void* __restrict__ p
   const int o = pre.out[p] + i;
   if (live && (unsigned)o < (unsigned)n_out)
     atomicMin(reinterpret_cast<unsigned long long*>(d2 + o), (unsigned long long)__double_as_longlong(best));
-  if (flags && status) atomicOr(status, (flags & kPmBadIndex ? (int)DPC_STATUS_BAD_INDEX : 0) | (flags & kPmNonFinite ? (int)DPC_STATUS_NONFINITE : 0));
+  pm_report(flags, status);
 }
 
 template <int PF64, int VF64>
@@ -112,7 +108,7 @@ int pm_launch(const void* pts, int n_pts, const void* verts, int n_verts, const 
 
 extern "C" {
 
-size_t dpc_point_mesh_workspace_bytes(int n_pairs) { return n_pairs > 0 ? pm_carve(n_pairs, nullptr, nullptr) : 0; }
+size_t dpc_point_mesh_workspace_bytes(int n_pairs) { return n_pairs > 0 ? pm_workspace(n_pairs, nullptr, nullptr) : 0; }
 
 int dpc_point_mesh_distance(const void* points, int n_points, int points_f64, const void* verts, int n_verts, int verts_f64,
                             const int32_t* faces, int n_faces, const int32_t* pair_desc, const int32_t* host_pair_desc, int n_pairs,
@@ -129,15 +125,14 @@ int dpc_point_mesh_distance(const void* points, int n_points, int points_f64, co
   if (!points || !verts || !faces || !pair_desc || !d2 || !workspace) return DPC_ERR_NULL;
   hipStream_t st = (hipStream_t)stream;
   PmWork w;
-  pm_carve(n_pairs, static_cast<char*>(workspace), &w);
+  pm_workspace(n_pairs, static_cast<char*>(workspace), &w);
   DPC_LAUNCH("k_pm_scan", dpc_kid("k_pm_scan", 0), (k_pm_scan<0>), dim3(1), dim3(kPmScanThreads), 0, st, pair_desc, n_pairs, n_points,
-             n_verts, n_faces, g.chunk, w.work, w.out, static_cast<int32_t*>(nullptr), status);
+             n_verts, n_faces, g.chunk, w.work, w.out, w.slot, status);
   DPC_LAUNCH("k_pm_fill", dpc_kid("k_pm_fill"), k_pm_fill, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d2, (int)total);
-  if (points_f64)
-    return verts_f64 ? pm_launch<1, 1>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w, d2, status, st)
-                     : pm_launch<1, 0>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w, d2, status, st);
-  return verts_f64 ? pm_launch<0, 1>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w, d2, status, st)
-                   : pm_launch<0, 0>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w, d2, status, st);
+  return pm_dispatch(points_f64, verts_f64, [&](auto pf, auto vf) {
+    return pm_launch<decltype(pf)::value, decltype(vf)::value>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w,
+                                                               d2, status, st);
+  });
 }
 
 }  // extern "C"

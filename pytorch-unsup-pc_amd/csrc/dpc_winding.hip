@@ -6,11 +6,11 @@
 //
 // k_pm_scan<1>   the distance's scan (dpc_point_mesh.h): checks the device table's rows and builds the per-row prefixes of
 //     work items, output points and workspace slots.
-// k_wn_sum<fp64 points, fp64 vertices>   k_pm_dist's decomposition: one workgroup of DPC_PM_BLOCK lanes per work item (row,
-//     block of points, chunk of faces), a lane owns one point.  Per round the workgroup stages DPC_PM_FACE_TILE faces in
-//     LDS, one lane per face: the three vertices in the caller's order, nine doubles widened once (a skipped face as NaNs,
-//     whose term is 0).  Then every lane walks the tile; all lanes read the same record, an LDS broadcast.  Per face and
-//     point, branch-free:
+// k_wn_sum<fp64 points, fp64 vertices>   k_pm_dist's decomposition, from pm_item, pm_walk and pm_fetch of
+//     dpc_point_mesh.h: one workgroup of DPC_PM_BLOCK lanes per work item (row, block of points, chunk of faces), a lane
+//     owns one point.  Per round the workgroup stages DPC_PM_FACE_TILE faces in LDS, one lane per face: the three
+//     vertices in the caller's order, nine doubles widened once (a skipped face as NaNs, whose term is 0).  Then every
+//     lane walks the tile; all lanes read the same record, an LDS broadcast.  Per face and point, branch-free:
 //         a = V0 - P, b = V1 - P, c = V2 - P
 //         det = a . (b x c),  den = |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|
 //         q = det != 0 ? rint(atan2(det, den) / (2 pi) * 2^40) : 0          an int64
@@ -40,53 +40,26 @@ constexpr int kWnMaxFaces = 1 << 22;                       // |q| <= 2^39: 2^22 
 static_assert(DPC_WINDING_FRAC_BITS - 1 + 22 < 63 && DPC_WINDING_FRAC_BITS < 51, "the sum cannot wrap; wn_term's rounding is exact");
 static_assert(kPmTile * kWnRec * 16 <= 64 * 1024, "the tile fits the default LDS limit");
 
-struct WnWork {
-  int32_t* work;   // [pairs + 1] exclusive prefix of work items
-  int32_t* out;    // [pairs + 1] exclusive prefix of output points
-  int32_t* slot;   // [pairs + 1] exclusive prefix of workspace slots: a row has chunks * points of them
-  int64_t* part;   // [slots]
+struct WnWork : PmWork {   // a row has chunks * points slots
+  int64_t* part;           // [slots]
 };
 
 size_t wn_carve(int pairs, int64_t slots, char* base, WnWork* w) {
   Carver c{base};
   WnWork t;
-  t.work = c.take<int32_t>((size_t)pairs + 1);
-  t.out = c.take<int32_t>((size_t)pairs + 1);
-  t.slot = c.take<int32_t>((size_t)pairs + 1);
+  static_cast<PmWork&>(t) = pm_carve<1>(c, pairs);
   t.part = c.take<int64_t>((size_t)slots);
   if (w) *w = t;
   return c.off + 16;
 }
 
-// Stages face i of the row into rec[0 .. kWnRec): the caller's three vertices; returns the flags of the face.  A face that
-// is skipped is staged as NaNs.  An index outside the mesh never becomes an address.
+// Stages face i of the row into rec[0 .. kWnRec): the caller's three vertices; returns the flags of the face (pm_fetch's
+// rules).
 template <int VF64>
-__device__ inline int wn_stage(const void* __restrict__ verts_, const int32_t* __restrict__ faces, const PmRow& r, int i, double2* rec) {
-  using T = std::conditional_t<VF64 != 0, double, float>;
-  const T* __restrict__ verts = static_cast<const T*>(verts_);
-  const int32_t* f = faces + 3 * ((size_t)r.fs + i);
-  const int idx[3] = {f[0], f[1], f[2]};
-  int flags = 0;
+__device__ inline int wn_stage(const void* __restrict__ verts, const int32_t* __restrict__ faces, const PmRow& r, int i, double2* rec) {
   double v[3][3];
-  if ((unsigned)idx[0] >= (unsigned)r.nv || (unsigned)idx[1] >= (unsigned)r.nv || (unsigned)idx[2] >= (unsigned)r.nv) {
-    flags = kPmBadIndex;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const T* q = verts + 3 * ((size_t)r.vs + idx[k]);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        v[k][c] = (double)q[c];
-        if (!(fabs(v[k][c]) < DPC_MESH_VOXEL_MAX_COORD)) flags = kPmNonFinite;   // a NaN too
-      }
-    }
-  }
-  if (flags) {
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-#pragma unroll
-    for (int j = 0; j < kWnRec; ++j) rec[j] = make_double2(nan, nan);
-    return flags;
-  }
+  const int flags = pm_fetch<VF64, kWnRec>(verts, faces, r, i, v, rec);
+  if (flags) return flags;
   rec[0] = make_double2(v[0][0], v[0][1]);
   rec[1] = make_double2(v[0][2], v[1][0]);
   rec[2] = make_double2(v[1][1], v[1][2]);
@@ -119,21 +92,11 @@ __device__ inline int64_t wn_term(const double2* __restrict__ rec, double px, do
 template <int VF64>
 __device__ inline int64_t wn_walk(const void* __restrict__ verts, const int32_t* __restrict__ faces, const PmRow& r, int f0, int f1,
                                   double px, double py, double pz, double2* tile, int* flags) {
-  const int t = threadIdx.x;
   int64_t sum = 0;
-  for (int base = f0; base < f1; base += kPmTile) {
-    const int n = f1 - base < kPmTile ? f1 - base : kPmTile;
-    __syncthreads();
-    if (t < n) *flags |= wn_stage<VF64>(verts, faces, r, base + t, tile + t * kWnRec);
-    __syncthreads();
-#pragma unroll 2
-    for (int k = 0; k < n; ++k) sum += wn_term(tile + k * kWnRec, px, py, pz);
-  }
+  pm_walk<kWnRec>(
+      f0, f1, tile, flags, [&](int f, double2* rec) { return wn_stage<VF64>(verts, faces, r, f, rec); },
+      [&](int, const double2* rec) { sum += wn_term(rec, px, py, pz); });
   return sum;
-}
-
-__device__ inline void wn_report(int flags, int32_t* status) {
-  if (flags && status) atomicOr(status, (flags & kPmBadIndex ? (int)DPC_STATUS_BAD_INDEX : 0) | (flags & kPmNonFinite ? (int)DPC_STATUS_NONFINITE : 0));
 }
 
 template <int PF64, int VF64>
@@ -141,60 +104,31 @@ __global__ __launch_bounds__(kPmBlock) void k_wn_sum(const void* __restrict__ pt
                                                      int n_verts, const int32_t* __restrict__ faces, int n_faces,
                                                      const int32_t* __restrict__ desc, int pairs, int chunk, WnWork pre, int n_slots,
                                                      int32_t* __restrict__ status) {
-  using T = std::conditional_t<PF64 != 0, double, float>;
   __shared__ double2 tile[kPmTile * kWnRec];
-  const int t = threadIdx.x;
-  const int item = blockIdx.x;
-  if (item >= pre.work[pairs]) return;
-  const int p = owner(pre.work, pairs, item);
-  PmRow r;
-  if (!pm_row(desc, p, n_pts, n_verts, n_faces, &r)) return;   // k_pm_scan has reported it
-  const int nb = pm_blocks(r.np), nc = pm_chunks(r.np, r.nf, chunk);
-  const int local = item - pre.work[p];
-  if (local < 0 || (int64_t)local >= (int64_t)nb * nc) return;
-  const int b = local % nb, c = local / nb;   // the point blocks of one chunk are adjacent: they read the same faces
-  const int i = b * kPmBlock + t;
-  const bool live = i < r.np;
-  const int f0 = c * chunk;                                    // < nf
-  const int f1 = r.nf - f0 < chunk ? r.nf : f0 + chunk;
-  double px = 0.0, py = 0.0, pz = 0.0;
-  if (live) {
-    const T* q = static_cast<const T*>(pts_) + 3 * ((size_t)r.ps + i);
-    px = (double)q[0]; py = (double)q[1]; pz = (double)q[2];
-  }
-  int flags = 0;
-  const bool finite = fabs(px) < DPC_MESH_VOXEL_MAX_COORD && fabs(py) < DPC_MESH_VOXEL_MAX_COORD && fabs(pz) < DPC_MESH_VOXEL_MAX_COORD;
-  if (!finite) {
-    flags = kPmNonFinite;
-    px = py = pz = 0.0;
-  }
-  int64_t sum = wn_walk<VF64>(verts, faces, r, f0, f1, px, py, pz, tile, &flags);
-  if (!finite) sum = 0;
-  const int64_t s = (int64_t)pre.slot[p] + (int64_t)c * r.np + i;
-  if (live && s >= 0 && s < n_slots) pre.part[s] = sum;
-  wn_report(flags, status);
+  PmItem it;
+  if (!pm_item<PF64>(pts_, n_pts, n_verts, n_faces, desc, pairs, chunk, pre, &it)) return;
+  int64_t sum = wn_walk<VF64>(verts, faces, it.r, it.f0, it.f1, it.px, it.py, it.pz, tile, &it.flags);
+  if (!it.finite) sum = 0;
+  const int64_t s = pm_slot(pre, it.p, it.r.np, it.c, it.i, n_slots);
+  if (it.live && s >= 0) pre.part[s] = sum;
+  pm_report(it.flags, status);
 }
 
 template <int PF64>
-__global__ __launch_bounds__(256) void k_wn_finish(const void* __restrict__ pts_, int n_pts, int n_verts, int n_faces,
-                                                   const int32_t* __restrict__ desc, int pairs, int chunk, WnWork pre, int n_slots,
-                                                   int n_out, int64_t* __restrict__ sums, double* __restrict__ winding) {
+__global__ __launch_bounds__(kPmOutBlock) void k_wn_finish(const void* __restrict__ pts_, int n_pts, int n_verts, int n_faces,
+                                                           const int32_t* __restrict__ desc, int pairs, int chunk, WnWork pre,
+                                                           int n_slots, int n_out, int64_t* __restrict__ sums,
+                                                           double* __restrict__ winding) {
   using T = std::conditional_t<PF64 != 0, double, float>;
-  const int64_t o64 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (o64 >= n_out || o64 >= pre.out[pairs]) return;
-  const int o = (int)o64;
-  const int p = owner(pre.out, pairs, o);
-  PmRow r;
-  if (!pm_row(desc, p, n_pts, n_verts, n_faces, &r)) return;
-  const int i = o - pre.out[p];
-  if (i < 0 || i >= r.np) return;
-  const int nc = pm_chunks(r.np, r.nf, chunk);   // <= nf
+  PmOut out;
+  if (!pm_out(n_pts, n_verts, n_faces, desc, pairs, chunk, pre, n_out, &out)) return;
+  const int o = out.o;
   int64_t sum = 0;
-  for (int c = 0; c < nc; ++c) {
-    const int64_t s = (int64_t)pre.slot[p] + (int64_t)c * r.np + i;
-    if (s >= 0 && s < n_slots) sum += pre.part[s];
+  for (int c = 0; c < out.nc; ++c) {
+    const int64_t s = pm_slot(pre, out.p, out.r.np, c, out.i, n_slots);
+    if (s >= 0) sum += pre.part[s];
   }
-  const T* q = static_cast<const T*>(pts_) + 3 * ((size_t)r.ps + i);
+  const T* q = static_cast<const T*>(pts_) + 3 * ((size_t)out.r.ps + out.i);
   const double px = (double)q[0], py = (double)q[1], pz = (double)q[2];
   const bool finite = fabs(px) < DPC_MESH_VOXEL_MAX_COORD && fabs(py) < DPC_MESH_VOXEL_MAX_COORD && fabs(pz) < DPC_MESH_VOXEL_MAX_COORD;
   if (sums) sums[o] = finite ? sum : 0;
@@ -207,26 +141,9 @@ int wn_launch(const void* pts, int n_pts, const void* verts, int n_verts, const 
               hipStream_t st) {
   DPC_LAUNCH("k_wn_sum", dpc_kid("k_wn_sum", PF64, VF64), (k_wn_sum<PF64, VF64>), dim3((unsigned)g.work), dim3(kPmBlock), 0, st, pts,
              n_pts, verts, n_verts, faces, n_faces, desc, pairs, g.chunk, w, (int)slots, status);
-  DPC_LAUNCH("k_wn_finish", dpc_kid("k_wn_finish", PF64), (k_wn_finish<PF64>), dim3((unsigned)((g.points + 255) / 256)), dim3(256), 0,
-             st, pts, n_pts, n_verts, n_faces, desc, pairs, g.chunk, w, (int)slots, (int)g.points, sums, winding);
+  DPC_LAUNCH("k_wn_finish", dpc_kid("k_wn_finish", PF64), (k_wn_finish<PF64>), dim3((unsigned)((g.points + kPmOutBlock - 1) / kPmOutBlock)),
+             dim3(kPmOutBlock), 0, st, pts, n_pts, n_verts, n_faces, desc, pairs, g.chunk, w, (int)slots, (int)g.points, sums, winding);
   return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
-}
-
-// the checks of both pair entry points: DPC_OK with the geometry and the slot count, or the code to return
-int wn_plan(int n_points, int n_verts, int n_faces, const int32_t* host_pair_desc, int n_pairs, PmGeom* g, int64_t* slots, int64_t* total) {
-  if (n_points < 0 || n_verts < 0 || n_faces < 0 || n_pairs < 0) return DPC_ERR_SHAPE;
-  *g = PmGeom{0, 0, 0, kPmTile * DPC_PM_CHUNK_TILES};
-  *slots = *total = 0;
-  if (n_pairs == 0) return DPC_OK;
-  if (!host_pair_desc) return DPC_ERR_NULL;
-  const int rc = pm_check(n_pairs, host_pair_desc, n_points, n_verts, n_faces, total);
-  if (rc != DPC_OK) return rc;
-  for (int p = 0; p < n_pairs; ++p)
-    if (host_pair_desc[6 * p + 5] > kWnMaxFaces) return DPC_ERR_SHAPE;
-  *g = pm_geometry(n_pairs, host_pair_desc);
-  for (int p = 0; p < n_pairs; ++p)
-    *slots += (int64_t)host_pair_desc[6 * p + 1] * pm_chunks(host_pair_desc[6 * p + 1], host_pair_desc[6 * p + 5], g->chunk);
-  return g->work > INT32_MAX || *slots > INT32_MAX ? DPC_ERR_SHAPE : DPC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -250,12 +167,8 @@ int wv_plan(int n_verts, int n_faces, const int32_t* host_mesh_desc, int meshes,
   if (rc != DPC_OK) return rc;
   int max_nf = 0;
   for (int m = 0; m < meshes; ++m) max_nf = host_mesh_desc[4 * m + 3] > max_nf ? host_mesh_desc[4 * m + 3] : max_nf;
-  // pm_geometry's rule: one chunk when the node blocks alone fill the device
-  const int64_t blocks = (int64_t)meshes * g->nb;
-  const int64_t want = (kPmFill + blocks - 1) / blocks;
-  const int64_t per = (max_nf + want - 1) / want;
-  const int64_t tiles = (per + kPmTile - 1) / kPmTile;
-  g->chunk = kPmTile * (int)(tiles > DPC_PM_CHUNK_TILES ? tiles : DPC_PM_CHUNK_TILES);
+  const int64_t blocks = (int64_t)meshes * g->nb;   // > 0
+  g->chunk = pm_chunk(blocks, max_nf);
   g->ncmax = (max_nf + g->chunk - 1) / g->chunk;
   g->work = blocks * g->ncmax;
   g->slots = (int64_t)meshes * g->ncmax * g->V;
@@ -294,7 +207,7 @@ __global__ __launch_bounds__(kPmBlock) void k_wn_vox(const void* __restrict__ ve
   int flags = 0;
   const int64_t sum = wn_walk<VF64>(verts, faces, r, f0, f1, px, py, pz, tile, &flags);
   if (live) part[((int64_t)mesh * ncmax + c) * V + i] = sum;
-  wn_report(flags, status);
+  pm_report(flags, status);
 }
 
 __global__ __launch_bounds__(kPmBlock) void k_wn_vox_finish(const int32_t* __restrict__ desc, int n_verts, int n_faces, int meshes, int V,
@@ -339,7 +252,7 @@ size_t dpc_mesh_winding_workspace_bytes(const int32_t* host_pair_desc, int n_pai
   if (n_pairs <= 0 || !host_pair_desc) return 0;
   PmGeom g;
   int64_t slots, total;
-  if (wn_plan(INT32_MAX, INT32_MAX, INT32_MAX, host_pair_desc, n_pairs, &g, &slots, &total) != DPC_OK) return 0;
+  if (pm_plan(INT32_MAX, INT32_MAX, INT32_MAX, host_pair_desc, n_pairs, kWnMaxFaces, &g, &slots, &total) != DPC_OK) return 0;
   return wn_carve(n_pairs, slots, nullptr, nullptr);
 }
 
@@ -348,7 +261,7 @@ int dpc_mesh_winding(const void* points, int n_points, int points_f64, const voi
                      int64_t* sums, double* winding, void* workspace, int32_t* status, void* stream) {
   PmGeom g;
   int64_t slots, total;
-  const int rc = wn_plan(n_points, n_verts, n_faces, host_pair_desc, n_pairs, &g, &slots, &total);
+  const int rc = pm_plan(n_points, n_verts, n_faces, host_pair_desc, n_pairs, kWnMaxFaces, &g, &slots, &total);
   if (rc != DPC_OK) return rc;
   if (n_pairs == 0 || total == 0) return DPC_OK;
   if (!points || !verts || !faces || !pair_desc || (!sums && !winding) || !workspace) return DPC_ERR_NULL;
@@ -357,11 +270,10 @@ int dpc_mesh_winding(const void* points, int n_points, int points_f64, const voi
   wn_carve(n_pairs, slots, static_cast<char*>(workspace), &w);
   DPC_LAUNCH("k_pm_scan", dpc_kid("k_pm_scan", 1), (k_pm_scan<1>), dim3(1), dim3(kPmScanThreads), 0, st, pair_desc, n_pairs, n_points,
              n_verts, n_faces, g.chunk, w.work, w.out, w.slot, status);
-  if (points_f64)
-    return verts_f64 ? wn_launch<1, 1>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w, slots, sums, winding, status, st)
-                     : wn_launch<1, 0>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w, slots, sums, winding, status, st);
-  return verts_f64 ? wn_launch<0, 1>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w, slots, sums, winding, status, st)
-                   : wn_launch<0, 0>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w, slots, sums, winding, status, st);
+  return pm_dispatch(points_f64, verts_f64, [&](auto pf, auto vf) {
+    return wn_launch<decltype(pf)::value, decltype(vf)::value>(points, n_points, verts, n_verts, faces, n_faces, pair_desc, n_pairs, g, w,
+                                                               slots, sums, winding, status, st);
+  });
 }
 
 size_t dpc_mesh_winding_voxels_workspace_bytes(const int32_t* host_mesh_desc, int meshes, int D, int H, int W) {

@@ -54,9 +54,6 @@ class _ClosestPlan(_Plan):
                          _native.ptr(weights), _native.ptr(normal), _native.ptr(ws), _native.ptr(status_word(dev)))
         return d2, face, point, weights, normal
 
-    def split(self, t):
-        return list(torch.split(t, [len(c) for c in self.clouds]))
-
 
 def closest_points_on_meshes(clouds, meshes, mesh_of=None, normals=False):
     """The closest surface point of every point of every cloud: one record per cloud, (d2 [n], face [n] int32, point [n,3],

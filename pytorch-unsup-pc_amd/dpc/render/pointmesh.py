@@ -85,15 +85,23 @@ class _Plan:
         return keep, (_native.ptr(pts), n_pts, int(pdt == torch.float64), _native.ptr(verts), n_verts, int(vdt == torch.float64),
                       _native.ptr(faces), n_faces, _native.ptr(desc_d), self.desc.ctypes.data, len(self.desc))
 
-    def run(self, dev):
-        """The packed squared distances [sum n_i] float64 on dev, in cloud order: one native call."""
+    def distance(self, dev, args):
+        """The packed squared distances [sum n_i] float64 on dev, in cloud order, for packed()'s args: one native call."""
         d2 = torch.empty((self.sizes[0],), dtype=torch.float64, device=dev)
-        if self.sizes[0] == 0:
-            return d2
-        keep, args = self.packed(dev)
         ws = _batch.workspace(_native.lib().dpc_point_mesh_workspace_bytes(len(self.desc)), dev)
         _native.call(dev, "dpc_point_mesh_distance", *args, _native.ptr(d2), _native.ptr(ws), _native.ptr(status_word(dev)))
         return d2
+
+    def run(self, dev):
+        """distance() on arguments packed here; an empty tensor when there is no point."""
+        if self.sizes[0] == 0:
+            return torch.empty((0,), dtype=torch.float64, device=dev)
+        keep, args = self.packed(dev)
+        return self.distance(dev, args)
+
+    def split(self, t):
+        """The packed tensor t as one tensor per cloud."""
+        return list(torch.split(t, [len(c) for c in self.clouds]))
 
 
 def point_mesh_distance(clouds, meshes, mesh_of=None, squared=False):

@@ -59,9 +59,6 @@ class _WindingPlan(_Plan):
         _native.call(dev, "dpc_mesh_winding", *args, _native.ptr(sums), _native.ptr(w), _native.ptr(ws), _native.ptr(status_word(dev)))
         return sums, w
 
-    def split(self, t):
-        return list(torch.split(t, [len(c) for c in self.clouds]))
-
 
 def winding_numbers(clouds, meshes, mesh_of=None, return_sums=False):
     """The generalized winding number of every point of every cloud about its mesh: a list of float64 device tensors [n_i],
@@ -115,9 +112,7 @@ def signed_point_mesh_distance(clouds, meshes, mesh_of=None, threshold=0.5, squa
     if plan.sizes[0] == 0:
         return [torch.empty((0,), dtype=torch.float64, device=dev) for _ in plan.clouds]
     keep, args = plan.packed(dev)
-    d2 = torch.empty((plan.sizes[0],), dtype=torch.float64, device=dev)
-    ws = _batch.workspace(_native.lib().dpc_point_mesh_workspace_bytes(len(plan.desc)), dev)
-    _native.call(dev, "dpc_point_mesh_distance", *args, _native.ptr(d2), _native.ptr(ws), _native.ptr(status_word(dev)))
+    d2 = plan.distance(dev, args)
     sums, _ = plan.sums(dev, args, False)
     mag = d2 if squared else torch.sqrt(d2)
     return plan.split(torch.where((sums > tq) & torch.isfinite(mag), -mag, mag))

@@ -167,7 +167,9 @@ def test_header_prototypes_match_the_bindings():
     for name in ("winding_numbers", "points_inside_meshes", "signed_point_mesh_distance", "winding_voxels"):
         assert name in R.__all__ and callable(getattr(R, name)), name
     src = open(os.path.join(ROOT, "pytorch-unsup-pc_amd", "csrc", "dpc_winding.hip")).read()
-    assert '#include "dpc_point_mesh.h"' in src and "atomicAdd" not in src and "pm_geometry(" in src
+    assert '#include "dpc_point_mesh.h"' in src and "atomicAdd" not in src and "pm_plan(" in src
+    shared = open(os.path.join(ROOT, "pytorch-unsup-pc_amd", "csrc", "dpc_point_mesh.h")).read()
+    assert "pm_geometry(" in shared[shared.index("inline int pm_plan("):]          # the distance's geometry, through the shared plan
 
 
 def _tab(rows, width=6):
