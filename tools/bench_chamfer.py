@@ -13,14 +13,12 @@ size is not known here (the same assumption as tools/bench_icp.py), and the cost
 The per-view loop and the cKDTree baseline run on --loop-models / --ckdtree-models models (the first ones of the split)
 and are scaled to the split; max_abs_diff compares path (a) with (b) on the models both computed."""
 import argparse
-import json
 import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "pytorch-unsup-pc_amd")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
 import torch
 
@@ -60,13 +58,7 @@ def main():
     # (a) batched, end to end
     call = lambda: R.chamfer_of_split(preds, gts, models_per_call=a.models_per_call)
     out = call()
-    walls = []
-    for _ in range(a.reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = call()
-        torch.cuda.synchronize()
-        walls.append(time.perf_counter() - t0)
+    walls = [ms / 1e3 for ms in BL.walls_ms(call, a.reps, warmup=0)]
     wall = min(walls)
     prof = _native.profile_kernels(call, dev)
     kern_ms = {k: round(sum(v), 3) for k, v in prof.items()}
@@ -74,11 +66,10 @@ def main():
     # (b) the per-view loop on the first --loop-models models, scaled to the split
     nl = min(a.loop_models, a.models)
     R.chamfer_of_predictions(preds[0][0], gts[0])      # warm-up
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    old = np.stack([R.chamfer_of_predictions(preds[m][0], gts[m]) for m in range(nl)])
-    torch.cuda.synchronize()
-    loop_s = (time.perf_counter() - t0) / nl * a.models
+    old = []
+    loop = lambda: old.extend(R.chamfer_of_predictions(preds[m][0], gts[m]) for m in range(nl))
+    loop_s = BL.walls_ms(loop, 1, warmup=0)[0] / 1e3 / nl * a.models
+    old = np.stack(old)
     diff = float(np.abs(old - out[:nl]).max())
 
     res = {
@@ -106,7 +97,7 @@ def main():
         res["cpu_ckdtree16_s_scaled"] = round((time.perf_counter() - t0) / nk * a.models, 3)
         res["cpu_ckdtree16_models_timed"] = nk
     res["device"] = torch.cuda.get_device_name(0)
-    print(json.dumps(res))
+    BL.emit(res)
 
 
 if __name__ == "__main__":

@@ -13,30 +13,17 @@ as tools/bench_chamfer.py and tools/bench_icp.py), and the cost scales linearly 
 kernel_ms_*: the library's own event timing of one call (dpc_profile_enable), summed per kernel; the backward's kernels
 (k_chamfer_bwd_*) are to be read against the forward's k_chamfer_partial of the same run."""
 import argparse
-import json
 import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "pytorch-unsup-pc_amd")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
 import torch
 
 import dpc.render as R
 from dpc.render import _native
 from bench_chamfer import shape_cloud
-
-
-def timed(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / reps * 1e3
 
 
 def torch_pair(pred, gt, squared):
@@ -54,7 +41,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--torch-reps", type=int, default=3)
     ap.add_argument("--squared", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "chamfer_loss_bench.jsonl"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "chamfer_loss_bench.jsonl"))
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     dev = torch.device("cuda")
@@ -70,8 +57,8 @@ def main():
         preds.grad = None
         R.chamfer_loss(preds, gts, squared=a.squared).sum().backward()
 
-    fwd_ms = timed(forward, a.reps)
-    both_ms = timed(forward_backward, a.reps)
+    fwd_ms = BL.batch_ms(forward, a.reps)
+    both_ms = BL.batch_ms(forward_backward, a.reps)
     prof = _native.profile_kernels(forward_backward, dev)
     kern = {k: round(sum(v), 4) for k, v in prof.items()}
     bwd_kernels = sum(v for k, v in kern.items() if k.startswith("k_chamfer_bwd"))
@@ -89,8 +76,8 @@ def main():
 
     t_fwd = t_both = diff = None
     if a.torch_reps > 0:    # --torch-reps 0: the library alone (a run under rocprofv3 --kernel-trace --stats)
-        t_fwd = timed(torch_forward, a.torch_reps) * a.pairs
-        t_both = timed(torch_forward_backward, a.torch_reps) * a.pairs
+        t_fwd = BL.batch_ms(torch_forward, a.torch_reps) * a.pairs
+        t_both = BL.batch_ms(torch_forward_backward, a.torch_reps) * a.pairs
         # the two agree on the pair both computed
         ours = R.chamfer_loss(preds[:1].detach(), gts[:1], squared=a.squared).sum()
         diff = abs(float(ours) - float(torch_forward()))
@@ -108,11 +95,7 @@ def main():
         res.update({"torch_bruteforce_forward_ms_scaled": round(t_fwd, 2),
                     "torch_bruteforce_forward_backward_ms_scaled": round(t_both, 2), "torch_pairs_timed": 1,
                     "speedup_forward_backward_vs_torch": round(t_both / both_ms, 2), "abs_diff_vs_torch_one_pair": diff})
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "a") as fh:
-            fh.write(line + "\n")
+    BL.emit(res, a.out)
 
 
 if __name__ == "__main__":

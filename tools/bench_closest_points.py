@@ -20,48 +20,23 @@ appended to profiles/closest_points_bench.jsonl (--out).
 
 Times are medians of --reps calls after a warm-up call, each call ended by a device synchronise."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "pytorch-unsup-pc_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
 
 import bench_point_mesh as PM
 
 FLOPS_PER_TEST = PM.FLOPS_PER_TEST + 3      # pm_d2 and, in place of the running min, one compare and two selects
-mesh, median_ms = PM.mesh, PM.median_ms
+mesh = PM.mesh
 
 
 def resource_usage(path):
-    """hipcc -Rpass-analysis=kernel-resource-usage on csrc/dpc_closest.hip, summarised by tools/resource_usage.py."""
-    import tempfile
-
-    csrc = os.path.join(PKG, "csrc")
-    with tempfile.TemporaryDirectory() as tmp:
-        log = os.path.join(tmp, "remarks.txt")
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics", "-mllvm",
-               "-pragma-unroll-threshold=400000", "-Rpass-analysis=kernel-resource-usage", "-c", "dpc_closest.hip", "-o",
-               os.path.join(tmp, "x.o")]
-        res = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True, check=True)
-        open(log, "w").write(res.stderr)
-        rows = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), log], capture_output=True,
-                              text=True, check=True).stdout
-    text = ("# csrc/dpc_closest.hip, hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage\n"
-            "# k_pc_arg<fp64 points, fp64 vertices>: lds= is the face tile, DPC_PM_FACE_TILE records of 12 double2 (static);\n"
-            "# k_pc_finish: one lane per output point, the winning face's record in registers\n" + rows)
-    open(path, "w").write(text)
-    print(text, end="")
-
-
-def kernels(fn, dev, prefix):
-    from dpc.render import _native
-
-    return {k: round(float(sum(v)), 4) for k, v in _native.profile_kernels(fn, dev).items() if k.startswith(prefix)}
+    BL.resource_usage("dpc_closest.hip", path, [
+        "# k_pc_arg<fp64 points, fp64 vertices>: lds= is the face tile, DPC_PM_FACE_TILE records of 12 double2 (static);",
+        "# k_pc_finish: one lane per output point, the winning face's record in registers"])
 
 
 def measure(clouds, meshes, mesh_of, reps, torch, dev):
@@ -72,14 +47,14 @@ def measure(clouds, meshes, mesh_of, reps, torch, dev):
     a, b = dist(), close()
     assert all(torch.equal(x, y.d2) for x, y in zip(a, b))                  # the same squared distances, bit for bit
     out = {"tests": int(sum(len(clouds[i]) * len(meshes[k][1]) for i, k in enumerate(mesh_of))), "rows": len(clouds),
-           "distance_wall_ms_median_min_max": median_ms(dist, reps), "closest_wall_ms_median_min_max": median_ms(close, reps),
-           "distance_kernel_ms": kernels(dist, dev, "k_pm_"), "closest_kernel_ms": kernels(close, dev, ("k_pc_", "k_pm_scan"))}
+           "distance_wall_ms_median_min_max": BL.median_ms(dist, reps), "closest_wall_ms_median_min_max": BL.median_ms(close, reps),
+           "distance_kernel_ms": BL.kernel_ms(dist, dev, "k_pm_"), "closest_kernel_ms": BL.kernel_ms(close, dev, ("k_pc_", "k_pm_scan"))}
     out["wall_ratio_closest_over_distance"] = round(out["closest_wall_ms_median_min_max"][0] / out["distance_wall_ms_median_min_max"][0], 4)
     out["kernel_ratio_k_pc_arg_over_k_pm_dist"] = round(out["closest_kernel_ms"]["k_pc_arg"] / out["distance_kernel_ms"]["k_pm_dist"], 4)
     out["kernel_ratio_all_k_pc_over_all_k_pm"] = round(sum(out["closest_kernel_ms"].values()) / sum(out["distance_kernel_ms"].values()), 4)
     dev_clouds = [torch.from_numpy(c).to(dev).requires_grad_(True) for c in clouds]
-    out["loss_forward_ms_median_min_max"] = median_ms(lambda: R.point_surface_loss(dev_clouds, meshes, mesh_of), reps)
-    out["loss_forward_backward_ms_median_min_max"] = median_ms(lambda: R.point_surface_loss(dev_clouds, meshes, mesh_of).sum().backward(), reps)
+    out["loss_forward_ms_median_min_max"] = BL.median_ms(lambda: R.point_surface_loss(dev_clouds, meshes, mesh_of), reps)
+    out["loss_forward_backward_ms_median_min_max"] = BL.median_ms(lambda: R.point_surface_loss(dev_clouds, meshes, mesh_of).sum().backward(), reps)
     return out
 
 
@@ -102,8 +77,8 @@ def main():
     ap.add_argument("--faces", type=int, nargs="+", default=[1000, 20000])
     ap.add_argument("--kinds", nargs="+", default=["icosphere", "soup"])
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "closest_points_bench.jsonl"))
-    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(ROOT, "profiles", "closest_points_resource_usage.txt"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "closest_points_bench.jsonl"))
+    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(BL.ROOT, "profiles", "closest_points_resource_usage.txt"))
     a = ap.parse_args()
     if a.resource_usage:
         resource_usage(a.resource_usage)
@@ -113,11 +88,7 @@ def main():
     dev = torch.device("cuda")
     for kind in a.kinds:
         for faces in a.faces:
-            line = json.dumps(bench(a, kind, faces, torch, dev))
-            print(line, flush=True)
-            if a.out:
-                with open(a.out, "a") as fh:
-                    fh.write(line + "\n")
+            BL.emit(bench(a, kind, faces, torch, dev), a.out)
 
 
 if __name__ == "__main__":

@@ -15,15 +15,13 @@ most any model needed), found by a run that reads the counter after every round.
 host oracle (a heap restatement of the reference) on one mesh.  reference_cpu_s_per_model is not measured by this tool:
 it is the reference's own densify_model time for a 6 252-face mesh, passed in with --reference-s."""
 import argparse
-import json
 import os
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "pytorch-unsup-pc_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
 import torch
 
@@ -55,15 +53,14 @@ def main():
     faces = int(np.mean([len(m[2]) for m in meshes]))
     names = list(range(a.models))
     dev = torch.device("cuda")
-    call = lambda: R.densify_split(names, meshes.__getitem__, a.num_points, models_per_call=a.models_per_call)
+    out = None
+
+    def call():
+        nonlocal out
+        out = R.densify_split(names, meshes.__getitem__, a.num_points, models_per_call=a.models_per_call)
+
     R.densify_split(names[:2], meshes.__getitem__, 1000)  # warm-up: code objects, allocator
-    walls = []
-    for _ in range(a.reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = call()
-        torch.cuda.synchronize()
-        walls.append(time.perf_counter() - t0)
+    walls = [ms / 1e3 for ms in BL.walls_ms(call, a.reps, warmup=0)]
     wall = min(walls)
     prof = _native.profile_kernels(call, dev, capacity=65536)
     kern_ms = {k: round(sum(v), 3) for k, v in prof.items()}
@@ -91,7 +88,7 @@ def main():
     }
     if a.reference_s:
         res["speedup_vs_reference"] = round(a.reference_s * a.models / wall, 1)
-    print(json.dumps(res))
+    BL.emit(res)
 
 
 if __name__ == "__main__":

@@ -16,14 +16,11 @@ backward, for scale.
 GPU time by device events around `reps` back-to-back calls after `warmup` calls of the same shape; the two routes alternate
 in windows.  --route new|lazy with --reps small: one route alone, for a run under rocprofv3 --kernel-trace --stats."""
 import argparse
-import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "pytorch-unsup-pc_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import torch
 
 import dpc.render as R
@@ -31,16 +28,6 @@ import dpc.render as R
 
 class Cfg(dict):
     __getattr__ = dict.__getitem__
-
-
-def event_ms(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def torch_loss(cfg, pred, depths, f):
@@ -60,7 +47,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--route", default="both", choices=["both", "new", "lazy"])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "depth_loss_bench.jsonl"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "depth_loss_bench.jsonl"))
     a = ap.parse_args()
     dev = torch.device("cuda")
     B, N, G, f = a.clouds, a.points, a.grid, 2
@@ -134,31 +121,19 @@ def main():
                  "dgrid_voxels": diff.numel(), "dgrid_voxels_off_by_1e-5_scale": int((diff > 1e-5 * scale).sum()),
                  "dgrid_columns_off": int((diff > 1e-5 * scale).any(dim=1).sum()),
                  "ds_max_rel_diff": float(((s_new - sl.grad).abs() / sl.grad.abs().clamp_min(1.0)).max())}
-    for fn in fns.values():          # every shape the timed windows use
-        for _ in range(a.warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(a.windows):       # alternate the routes window by window
-        for k, fn in fns.items():
-            times[k].append(event_ms(fn, a.reps))
-    med = {k: round(sorted(v)[len(v) // 2], 4) for k, v in times.items()}
+    med, spread = BL.event_windows(fns, a.reps, a.warmup, a.windows)
     grid_mb = B * G * G * G * 4 / 1e6
     res = {"bench": "depth_loss", "clouds": B, "points": N, "grid": G, "gt_factor": f, "sigma_rel": 0.64, "taps": 21,
            "reps": a.reps, "warmup": a.warmup, "windows": a.windows, "route": a.route, "timing": "device events, median window",
            "grid_mb": round(grid_mb, 1), **med,
-           "spread_ms": {k: [round(min(v), 4), round(max(v), 4)] for k, v in times.items()},
+           "spread_ms": spread,
            "device": torch.cuda.get_device_name(0)}
     if a.route == "both":
         res["speedup_forward"] = round(med["lazy_forward_ms"] / med["new_forward_ms"], 2)
         res["speedup_forward_backward"] = round(med["lazy_forward_backward_ms"] / med["new_forward_backward_ms"], 2)
         res["speedup_step"] = round(med["step_lazy_ms"] / med["step_new_ms"], 3)
         res["agreement"] = agree
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "a") as fh:
-            fh.write(line + "\n")
+    BL.emit(res, a.out)
 
 
 if __name__ == "__main__":

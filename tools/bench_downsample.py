@@ -16,22 +16,18 @@ must move (8 B key read by k_ds_hist; 12 B key + row read and written by k_ds_sc
 passes' kernels, against the 8.0 TB/s HBM peak.  single_voxel_200k_ms is one call on a 200 000-point cloud that is one
 voxel: k_ds_average's longest serial chain."""
 import argparse
-import json
 import math
 import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "pytorch-unsup-pc_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
 import torch
 
 import dpc.render as R
 from dpc.render import _native
-
-HBM_PEAK = 8.0e12
 
 
 def box_surface(n, rng, boxes=4):
@@ -73,15 +69,14 @@ def main():
     names = list(range(a.models))
     dev = torch.device("cuda")
 
-    call = lambda: R.downsample_split(names, clouds.__getitem__, a.voxel, clouds_per_call=a.clouds_per_call)
+    out = None
+
+    def call():
+        nonlocal out
+        out = R.downsample_split(names, clouds.__getitem__, a.voxel, clouds_per_call=a.clouds_per_call)
+
     R.downsample_split(names[:8], clouds.__getitem__, a.voxel)            # warm-up: code objects, allocator
-    walls = []
-    for _ in range(a.reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = call()
-        torch.cuda.synchronize()
-        walls.append(time.perf_counter() - t0)
+    walls = [ms / 1e3 for ms in BL.walls_ms(call, a.reps, warmup=0)]
     wall = min(walls)
     prof = _native.profile_kernels(call, dev)
     kern_ms = {k: round(sum(v), 3) for k, v in prof.items()}
@@ -118,14 +113,14 @@ def main():
         "key_bits_first_call": key_bits(clouds[:a.clouds_per_call], a.voxel)[0],
         "sort_passes_first_call": key_bits(clouds[:a.clouds_per_call], a.voxel)[1],
         "sort_pass_bytes": moved, "sort_pass_kernel_ms": round(sort_ms, 3),
-        "sort_pass_bytes_per_s": moved / (sort_ms * 1e-3), "sort_pass_share_of_hbm_peak": moved / (sort_ms * 1e-3) / HBM_PEAK,
+        "sort_pass_bytes_per_s": moved / (sort_ms * 1e-3), "sort_pass_share_of_hbm_peak": moved / (sort_ms * 1e-3) / BL.HBM_PEAK,
         "voxels_per_cloud": {"mean": float(sizes.mean()), "min": int(sizes.min()), "max": int(sizes.max())},
         "numpy_oracle_s_scaled": round(oracle_s, 2), "numpy_oracle_models_timed": no,
         "speedup_vs_numpy_oracle": round(oracle_s / wall, 1),
         "single_voxel_200k_ms": {k: round(sum(v), 3) for k, v in prof1.items() if k in ("k_ds_average", "k_ds_bounds")},
         "device": torch.cuda.get_device_name(0),
     }
-    print(json.dumps(res))
+    BL.emit(res)
 
 
 if __name__ == "__main__":

@@ -18,14 +18,11 @@ GPU time by device events around `reps` back-to-back calls after `warmup` calls 
 in windows.  --route new|composed with --reps small: one route alone, for a run under rocprofv3 --kernel-trace --stats.
 Bytes a kernel must move are computed from the shapes and printed next to the times."""
 import argparse
-import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "pytorch-unsup-pc_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import torch
 
 import dpc.render as R
@@ -33,16 +30,6 @@ import dpc.render as R
 
 class Cfg(dict):
     __getattr__ = dict.__getitem__
-
-
-def event_ms(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def torch_mask_loss(probs, masks, f):
@@ -69,7 +56,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--route", default="both", choices=["both", "new", "composed"])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "drc_loss_bench.jsonl"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "drc_loss_bench.jsonl"))
     a = ap.parse_args()
     dev = torch.device("cuda")
     B, N, G, f = a.clouds, a.points, a.grid, 2
@@ -176,15 +163,7 @@ def main():
                       "rgb_dvox_max_abs_diff_over_scale": float(vdiff.max()) / vscale,
                       "rgb_dvox_voxels_off_by_1e-5_scale": int((vdiff > 1e-5 * vscale).sum()),
                       "rgb_dC_max_abs_diff_over_scale": rel(c_new, C.grad)})
-    for fn in fns.values():          # every shape the timed windows use
-        for _ in range(a.warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(a.windows):       # alternate the routes window by window
-        for k, fn in fns.items():
-            times[k].append(event_ms(fn, a.reps))
-    med = {k: round(sorted(v)[len(v) // 2], 4) for k, v in times.items()}
+    med, spread = BL.event_windows(fns, a.reps, a.warmup, a.windows)
     grid_mb = B * G * G * G * 4 / 1e6
     # what each column kernel must move, from the shapes: grids in and out, ground truth read at the projection's size
     bytes_mb = {"k_drcmask_fwd": round(grid_mb + B * G * G * 4 / 1e6, 1), "k_drcmask_bwd": round(2 * grid_mb + B * G * G * 4 / 1e6, 1),
@@ -193,18 +172,14 @@ def main():
            "taps_rgb": 11, "divide_by_occupancies": True, "reps": a.reps, "warmup": a.warmup, "windows": a.windows,
            "route": a.route, "timing": "device events, median window", "grid_mb": round(grid_mb, 1),
            "kernel_bytes_mb": bytes_mb, **med,
-           "spread_ms": {k: [round(min(v), 4), round(max(v), 4)] for k, v in times.items()},
+           "spread_ms": spread,
            "device": torch.cuda.get_device_name(0)}
     if a.route == "both":
         for case in ("mask", "rgb"):
             for what in ("forward", "forward_backward"):
                 res["speedup_%s_%s" % (case, what)] = round(med["%s_composed_%s_ms" % (case, what)] / med["%s_new_%s_ms" % (case, what)], 2)
         res["agreement"] = agree
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "a") as fh:
-            fh.write(line + "\n")
+    BL.emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -10,56 +10,22 @@ profiles/emd_bench.jsonl (--out).
 
 Times are medians of --reps calls after two warm-up calls, each call ended by a device synchronise."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "pytorch-unsup-pc_amd")
-for p in (ROOT, PKG):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
 
 
 def resource_usage(path):
-    """hipcc -Rpass-analysis=kernel-resource-usage on csrc/dpc_emd.hip, summarised by tools/resource_usage.py."""
-    import tempfile
-
     from dpc.render import _native
 
-    csrc = os.path.join(PKG, "csrc")
-    with tempfile.TemporaryDirectory() as tmp:
-        log = os.path.join(tmp, "remarks.txt")
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics", "-mllvm",
-               "-pragma-unroll-threshold=400000", "-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage", "-c",
-               "dpc_emd.hip", "-o", os.path.join(tmp, "x.o")]
-        res = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True, check=True)
-        open(log, "w").write(res.stderr)
-        rows = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), log], capture_output=True,
-                              text=True, check=True).stdout
     L = _native.lib()
-    text = ("# csrc/dpc_emd.hip, hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -Rpass-analysis=kernel-resource-usage\n"
-            "# k_emd_auction: dynamic LDS, 76 bytes per point + %d: %d B at n = 1024, %d B at n = %d\n"
-            % (L.dpc_emd_lds_bytes(2) - 152, L.dpc_emd_lds_bytes(1024), L.dpc_emd_lds_bytes(_native.DPC_EMD_MAX_POINTS), _native.DPC_EMD_MAX_POINTS) + rows)
-    open(path, "w").write(text)
-    print(text, end="")
-
-
-def median_ms(fn, reps, warmup=2):
-    import torch
-
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(times)), float(min(times)), float(max(times))
+    BL.resource_usage("dpc_emd.hip", path, [
+        "# k_emd_auction: dynamic LDS, 76 bytes per point + %d: %d B at n = 1024, %d B at n = %d"
+        % (L.dpc_emd_lds_bytes(2) - 152, L.dpc_emd_lds_bytes(1024), L.dpc_emd_lds_bytes(_native.DPC_EMD_MAX_POINTS), _native.DPC_EMD_MAX_POINTS)])
 
 
 def main():
@@ -69,8 +35,8 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--scipy-pairs", type=int, default=4)
     ap.add_argument("--squared", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "emd_bench.jsonl"))
-    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(ROOT, "profiles", "emd_resource_usage.txt"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "emd_bench.jsonl"))
+    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(BL.ROOT, "profiles", "emd_resource_usage.txt"))
     a = ap.parse_args()
     if a.resource_usage:
         resource_usage(a.resource_usage)
@@ -96,8 +62,8 @@ def main():
                 preds.grad = None
                 R.emd_loss(preds, gts, squared=a.squared).sum().backward()
 
-            fwd = median_ms(forward, a.reps)
-            both = median_ms(forward_backward, a.reps)
+            fwd = BL.median_ms(forward, a.reps, warmup=2, digits=None)
+            both = BL.median_ms(forward_backward, a.reps, warmup=2, digits=None)
             emd, asg, _, rounds = R.emd_match(preds.detach(), gts, squared=a.squared)
             rounds = rounds.cpu().numpy()
             assert R.check_status() == 0 and not bool(torch.isnan(emd).any())
@@ -128,11 +94,7 @@ def main():
                             "scipy_host_ms_scaled_to_batch": round(float(np.median(host_ms)) * P, 1),
                             "excess_over_optimal_mean_max": max(excess),
                             "speedup_forward_vs_scipy_scaled": round(float(np.median(host_ms)) * P / fwd[0], 1)})
-            line = json.dumps(res)
-            print(line, flush=True)
-            if a.out:
-                with open(a.out, "a") as fh:
-                    fh.write(line + "\n")
+            BL.emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -17,55 +17,21 @@ profiles/fps_bench.jsonl (--out).
 
 Times are medians of --reps calls after two warm-up calls, each call ended by a device synchronise."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "pytorch-unsup-pc_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
 
 SHAPES = [(8000, "float32", 1024), (8000, "float32", 2048), (12647, "float64", 1024)]
 
 
 def resource_usage(path):
-    """hipcc -Rpass-analysis=kernel-resource-usage on csrc/dpc_fps.hip, summarised by tools/resource_usage.py."""
-    import tempfile
-
-    csrc = os.path.join(PKG, "csrc")
-    with tempfile.TemporaryDirectory() as tmp:
-        log = os.path.join(tmp, "remarks.txt")
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics", "-mllvm",
-               "-pragma-unroll-threshold=400000", "-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage", "-c",
-               "dpc_fps.hip", "-o", os.path.join(tmp, "x.o")]
-        res = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True, check=True)
-        open(log, "w").write(res.stderr)
-        rows = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), log], capture_output=True,
-                              text=True, check=True).stdout
-    text = ("# csrc/dpc_fps.hip, hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -Rpass-analysis=kernel-resource-usage\n"
-            "# k_fps<fp64 input, threads, points per thread>; lds= is the static part (what __syncthreads_or reserves), the\n"
-            "# dynamic part is 12 bytes per wave + 32, and for k_fps<1, 1024, 16> also dist, 8 bytes per point: 131296 B\n" + rows)
-    open(path, "w").write(text)
-    print(text, end="")
-
-
-def median_ms(fn, reps, warmup=2):
-    import torch
-
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(times)), float(min(times)), float(max(times))
+    BL.resource_usage("dpc_fps.hip", path, [
+        "# k_fps<fp64 input, threads, points per thread>; lds= is the static part (what __syncthreads_or reserves), the",
+        "# dynamic part is 12 bytes per wave + 32, and for k_fps<1, 1024, 16> also dist, 8 bytes per point: 131296 B"])
 
 
 def torch_loop(pts, m):
@@ -96,7 +62,7 @@ def bench_split(a, R, torch):
     res = {"bench": "emd_of_split_sampling", "models": a.models, "views": a.views, "pred_points": 8000, "gt_points": 12647,
            "num_points": 1024, "reps": a.split_reps, "device": torch.cuda.get_device_name(0)}
     for mode in ("random", "fps"):
-        t = median_ms(lambda: R.emd_of_split(preds, gts, num_points=1024, seed=0, sampling=mode), a.split_reps, warmup=1)
+        t = BL.median_ms(lambda: R.emd_of_split(preds, gts, num_points=1024, seed=0, sampling=mode), a.split_reps, warmup=1, digits=None)
         res["%s_ms" % mode] = round(t[0], 2)
         res["%s_ms_min_max" % mode] = [round(t[1], 2), round(t[2], 2)]
         res["%s_mean_emd" % mode] = float(R.emd_of_split(preds, gts, num_points=1024, seed=0, sampling=mode).mean())
@@ -114,8 +80,8 @@ def main():
     ap.add_argument("--models", type=int, default=32)
     ap.add_argument("--views", type=int, default=4)
     ap.add_argument("--split-reps", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fps_bench.jsonl"))
-    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(ROOT, "profiles", "fps_resource_usage.txt"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "fps_bench.jsonl"))
+    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(BL.ROOT, "profiles", "fps_resource_usage.txt"))
     a = ap.parse_args()
     if a.resource_usage:
         resource_usage(a.resource_usage)
@@ -133,13 +99,13 @@ def main():
         rng = np.random.default_rng(1000 * n + m)
         host = (rng.random((B, n, 3)) - 0.5).astype(dtype)
         pts = torch.from_numpy(host).to(dev)
-        wall = median_ms(lambda: R.farthest_point_sample(pts, m), a.reps)
+        wall = BL.median_ms(lambda: R.farthest_point_sample(pts, m), a.reps, warmup=2, digits=None)
         prof = _native.profile_kernels(lambda: R.farthest_point_sample(pts, m), dev)
         kernel_ms = float(sum(sum(v) for k, v in prof.items() if k.startswith("k_fps")))
         ids = sorted(i for i in _native.launched_instantiations(lambda: R.farthest_point_sample(pts, m), dev) if i.startswith("k_fps"))
         idx = R.farthest_point_sample(pts, m)
         assert R.check_status() == 0
-        loop = median_ms(lambda: torch_loop(pts, m), a.torch_reps, warmup=1)
+        loop = BL.median_ms(lambda: torch_loop(pts, m), a.torch_reps, warmup=1, digits=None)
         agree = float((torch_loop(pts, m) == idx.long()).all(dim=1).double().mean())
         k = min(a.host_clouds, B)
         host_ms = []
@@ -163,11 +129,7 @@ def main():
     if a.split:
         lines.append(bench_split(a, R, torch))
     for res in lines:
-        line = json.dumps(res)
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "a") as fh:
-                fh.write(line + "\n")
+        BL.emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -6,14 +6,11 @@ Synthetic images/masks, random-init weights, fp32.  One JSON line per variant:
   keep=0.07d the same with the dropout drawn on the device
   keep=1.0   all 8000 points (the end of the schedule)
 """
-import json
 import os
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "pytorch-unsup-pc_amd")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import torch
 
 from dpc.harness import TrainStep, chair_unsupervised
@@ -32,20 +29,18 @@ def main():
         g = torch.Generator().manual_seed(3)
         images = torch.rand(nimg, 3, 128, 128, generator=g).to(dev)
         masks = (torch.rand(nimg, 1, 128, 128, generator=g) > 0.5).float().to(dev)
-        run = step
-        for _ in range(warmup):
-            run(images, masks)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            loss = run(images, masks)
-        torch.cuda.synchronize()
-        wall = (time.perf_counter() - t0) / steps
+        loss = None
+
+        def run():
+            nonlocal loss
+            loss = step(images, masks)
+
+        wall = BL.batch_ms(run, steps, warmup) / 1e3
         prof = _native.profile_kernels(lambda: [step(images, masks) for _ in range(5)], dev)
         floor = 0.5 * _native.event_pair_overhead_ms(dev)
         render_us = sum(1e3 * (sorted(v)[len(v) // 2] - floor) for v in prof.values())
         nparam = sum(p.numel() for p in step.nets.parameters())
-        print(json.dumps({
+        BL.emit({
             "metric": "chair_unsupervised train steps/sec (fwd + loss + bwd + Adam)", "value": 1.0 / wall, "unit": "steps/sec",
             "ms_per_step": 1e3 * wall, "images_per_sec": nimg / wall,
             "clouds_per_sec": nimg * cfg.pose_predict_num_candidates / wall, "dtype": "f32", "data": "synthetic",
@@ -53,7 +48,7 @@ def main():
                                    "128 clouds, %s, 64^3 grid, 21 taps sigma_rel=3.0, eager launches" % label,
                        "parameters": nparam},
             "renderer_kernels_us_per_step": render_us, "renderer_kernels": {k: len(v) // 5 for k, v in prof.items()},
-            "loss": float(loss)}))
+            "loss": float(loss)})
 
 
 if __name__ == "__main__":

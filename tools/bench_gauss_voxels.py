@@ -18,16 +18,11 @@ for the composed route at the default shapes."""
 import argparse
 import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "pytorch-unsup-pc_amd")
-for p in (ROOT, PKG):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 
-PEAK_FP32 = 157.3e12
 MAGIC = 1.78984352254
 
 
@@ -36,37 +31,9 @@ class Cfg(dict):
 
 
 def resource_usage(path):
-    """hipcc -Rpass-analysis=kernel-resource-usage on csrc/dpc_gauss_voxels.hip, summarised by tools/resource_usage.py."""
-    import tempfile
-
-    csrc = os.path.join(PKG, "csrc")
-    with tempfile.TemporaryDirectory() as tmp:
-        log = os.path.join(tmp, "remarks.txt")
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics", "-mllvm",
-               "-pragma-unroll-threshold=400000", "-Rpass-analysis=kernel-resource-usage", "-c", "dpc_gauss_voxels.hip", "-o",
-               os.path.join(tmp, "x.o")]
-        res = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True, check=True)
-        open(log, "w").write(res.stderr)
-        rows = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), log], capture_output=True,
-                              text=True, check=True).stdout
-    rows = "".join(l + "\n" for l in rows.splitlines() if "k_gauss_voxels" in l)
-    text = ("# csrc/dpc_gauss_voxels.hip, hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage\n"
-            "# backward: dynamic LDS, (W + 64 (W + 1) + 384 W) * 4 bytes at the compiled width W = 2 KS: 57,728 B for G <= 32, "
-            "115,200 B for G <= 64\n" + rows)
-    open(path, "w").write(text)
-    print(text, end="")
-
-
-def event_ms(fn, reps):
-    import torch
-
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
+    BL.resource_usage("dpc_gauss_voxels.hip", path, [
+        "# backward: dynamic LDS, (W + 64 (W + 1) + 384 W) * 4 bytes at the compiled width W = 2 KS: 57,728 B for G <= 32, "
+        "115,200 B for G <= 64"], keep="k_gauss_voxels")
 
 
 def torch_voxels(tr, G, sigma, chunk):
@@ -129,34 +96,22 @@ def bench_shape(a, G):
         raise SystemExit("the two routes disagree at G = %d: %s" % (G, json.dumps(agree)))
     fns = {"new_forward_ms": new_fwd, "composed_forward_ms": composed_fwd, "new_forward_backward_ms": new_both,
            "composed_forward_backward_ms": composed_both}
-    for fn in fns.values():
-        for _ in range(a.warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(a.windows):
-        for k, fn in fns.items():
-            times[k].append(event_ms(fn, a.reps))
-    med = {k: round(sorted(v)[len(v) // 2], 4) for k, v in times.items()}
+    med, spread = BL.event_windows(fns, a.reps, a.warmup, a.windows)
     flop_fwd = 2.0 * B * N * G ** 3
     fwd_tf = flop_fwd / (med["new_forward_ms"] * 1e-3) / 1e12
     both_tf = 3.0 * flop_fwd / (med["new_forward_backward_ms"] * 1e-3) / 1e12
     res = {"bench": "gauss_voxels", "clouds": B, "points": N, "grid": G, "sigma_rel": a.sigma_rel, "normalise": "analytical",
            "reps": a.reps, "warmup": a.warmup, "windows": a.windows, "composed_chunk": a.chunk,
            "timing": "device events, median window", **med,
-           "spread_ms": {k: [round(min(v), 4), round(max(v), 4)] for k, v in times.items()},
+           "spread_ms": spread,
            "forward_gflop": round(flop_fwd / 1e9, 1), "new_forward_tflops": round(fwd_tf, 1),
-           "new_forward_fraction_of_fp32_peak": round(fwd_tf * 1e12 / PEAK_FP32, 3),
+           "new_forward_fraction_of_fp32_peak": round(fwd_tf * 1e12 / BL.FP32_VECTOR_PEAK, 3),
            "new_forward_backward_tflops": round(both_tf, 1),
-           "new_forward_backward_fraction_of_fp32_peak": round(both_tf * 1e12 / PEAK_FP32, 3),
+           "new_forward_backward_fraction_of_fp32_peak": round(both_tf * 1e12 / BL.FP32_VECTOR_PEAK, 3),
            "speedup_forward": round(med["composed_forward_ms"] / med["new_forward_ms"], 2),
            "speedup_forward_backward": round(med["composed_forward_backward_ms"] / med["new_forward_backward_ms"], 2),
            "agreement": agree, "device": torch.cuda.get_device_name(0)}
-    line = json.dumps(res)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "a") as fh:
-            fh.write(line + "\n")
+    BL.emit(res, a.out)
     return res
 
 
@@ -170,8 +125,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--chunk", type=int, default=0, help="points per matmul of the composed route (0: all at once)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gauss_voxels_bench.jsonl"))
-    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(ROOT, "profiles", "gauss_voxels_resource_usage.txt"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "gauss_voxels_bench.jsonl"))
+    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(BL.ROOT, "profiles", "gauss_voxels_resource_usage.txt"))
     a = ap.parse_args()
     if a.resource_usage:
         resource_usage(a.resource_usage)

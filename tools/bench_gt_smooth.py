@@ -18,55 +18,19 @@ anything is timed; more than 1e-5 apart ends the run.  The step: dpc.harness.con
 objects (64^3, 8000 points, 4 pose candidates, 128 x 128 masks, no point dropout), eager, with and without the key: a host
 clock around `--step-reps` steps that end in a synchronise, the two configurations alternating in windows, medians."""
 import argparse
-import json
 import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "pytorch-unsup-pc_amd")
-for p in (ROOT, PKG):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-PEAK_HBM = 8.0e12
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 
 SHAPES = (("masks", 32, 128, 64, 11, 1.5), ("masks", 32, 128, 64, 21, 3.0), ("images", 32, 128, 64, 11, 1.5))
 
 
 def resource_usage(path):
-    """hipcc -Rpass-analysis=kernel-resource-usage on csrc/dpc_gt_smooth.hip, summarised by tools/resource_usage.py."""
-    import tempfile
-
-    csrc = os.path.join(PKG, "csrc")
-    with tempfile.TemporaryDirectory() as tmp:
-        log = os.path.join(tmp, "remarks.txt")
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics", "-mllvm",
-               "-pragma-unroll-threshold=400000", "-Rpass-analysis=kernel-resource-usage", "-c", "dpc_gt_smooth.hip", "-o",
-               os.path.join(tmp, "x.o")]
-        res = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True, check=True)
-        open(log, "w").write(res.stderr)
-        rows = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), log], capture_output=True,
-                              text=True, check=True).stdout
-    rows = "".join(l + "\n" for l in rows.splitlines() if "k_gt_smooth" in l)
-    text = ("# csrc/dpc_gt_smooth.hip, hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage\n"
-            "# dynamic LDS on top of the static figure: (16 + 2c) x (128 + 2c) x 4 bytes for 2c + 1 taps: 14,352 B at 11 taps, "
-            "21,312 B at 21, 59,280 B at 63\n" + rows)
-    open(path, "w").write(text)
-    print(text, end="")
-
-
-def event_ms(fn, reps):
-    import torch
-
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
+    BL.resource_usage("dpc_gt_smooth.hip", path, [
+        "# dynamic LDS on top of the static figure: (16 + 2c) x (128 + 2c) x 4 bytes for 2c + 1 taps: 14,352 B at 11 taps, "
+        "21,312 B at 21, 59,280 B at 63"], keep="k_gt_smooth")
 
 
 def composed(gt, C, f, mode_mean, w):
@@ -107,35 +71,24 @@ def bench_shape(a, kind, S, src, dst, taps, sigma):
     fns = {"new": new, "torch": old}
     if a.route:
         fns = {a.route: fns[a.route]}
-    for fn in fns.values():
-        for _ in range(a.warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(a.windows):
-        for k, fn in fns.items():
-            times[k].append(event_ms(fn, a.reps))
-    med = {k + "_wall_ms": round(sorted(v)[len(v) // 2], 5) for k, v in times.items()}
+    med, spread = BL.event_windows(fns, a.reps, a.warmup, a.windows, digits=5)
+    med = {k + "_wall_ms": v for k, v in med.items()}
     nbytes = 4 * S * C * (src * src + dst * dst)
     res = {"bench": "gt_smooth", "kind": kind, "samples": S, "channels": C, "source": src, "size": dst, "taps": taps,
            "reps": a.reps, "warmup": a.warmup, "windows": a.windows, "timing": "device events, median window", **med,
-           "spread_ms": {k: [round(min(v), 5), round(max(v), 5)] for k, v in times.items()},
+           "spread_ms": spread,
            "bytes_moved": nbytes, "max_abs_diff_of_routes": diff, "device": torch.cuda.get_device_name(0)}
     if "new" in fns:
         rec = _native.profile_kernels(lambda: [new() for _ in range(a.reps)], dev).get("k_gt_smooth", [])
         if rec:
-            k_ms = sorted(rec)[len(rec) // 2]
+            k_ms = BL.upper_median(rec)
             res.update(new_kernel_ms=round(k_ms, 5), new_kernel_launches_per_call=len(rec) / a.reps,
                        empty_event_pair_ms=round(_native.event_pair_overhead_ms(dev), 5),
                        kernel_timing="the library's event pair around the launch, median; includes what an empty pair reads",
-                       new_fraction_of_hbm_peak=round(nbytes / (k_ms * 1e-3) / PEAK_HBM, 4))
+                       new_fraction_of_hbm_peak=BL.share(nbytes, k_ms, BL.HBM_PEAK, 4))
     if "new_wall_ms" in med and "torch_wall_ms" in med:
         res["speedup_wall"] = round(med["torch_wall_ms"] / med["new_wall_ms"], 2)
-    line = json.dumps(res)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "a") as fh:
-            fh.write(line + "\n")
+    BL.emit(res, a.out)
 
 
 def bench_step(a):
@@ -160,12 +113,7 @@ def bench_step(a):
     masks = (torch.rand(views, 1, side, side, generator=gen) < 0.45).float().to(dev)
 
     def run(key, n):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            steps[key][1](images, masks)
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3 / n
+        return BL.batch_ms(lambda: steps[key][1](images, masks), n, warmup=0)
 
     for key in steps:
         run(key, a.step_warmup)
@@ -173,7 +121,7 @@ def bench_step(a):
     for _ in range(a.windows):
         for key in steps:
             times[key].append(run(key, a.step_reps))
-    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    med = {k: BL.upper_median(v) for k, v in times.items()}
     res = {"bench": "gt_smooth_step", "views": views, "grid": cfg.vox_size, "points": cfg.pc_num_points,
            "candidates": cfg.pose_predict_num_candidates, "mask_side": side, "taps": cfg.pc_gauss_kernel_size,
            "reps": a.step_reps, "warmup": a.step_warmup, "windows": a.windows,
@@ -182,11 +130,7 @@ def bench_step(a):
            "spread_ms": {"without": [round(min(times[False]), 4), round(max(times[False]), 4)],
                          "with": [round(min(times[True]), 4), round(max(times[True]), 4)]},
            "added_ms": round(med[True] - med[False], 4), "device": torch.cuda.get_device_name(0)}
-    line = json.dumps(res)
-    print(line, flush=True)
-    if a.out:
-        with open(a.out, "a") as fh:
-            fh.write(line + "\n")
+    BL.emit(res, a.out)
 
 
 def main():
@@ -199,8 +143,8 @@ def main():
     ap.add_argument("--step-batch", type=int, default=8)
     ap.add_argument("--step-reps", type=int, default=20)
     ap.add_argument("--step-warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gt_smooth_bench.jsonl"))
-    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(ROOT, "profiles", "gt_smooth_resource_usage.txt"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "gt_smooth_bench.jsonl"))
+    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(BL.ROOT, "profiles", "gt_smooth_resource_usage.txt"))
     a = ap.parse_args()
     if a.resource_usage:
         resource_usage(a.resource_usage)

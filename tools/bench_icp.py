@@ -11,14 +11,12 @@ is not known here: the GT size is an assumption, and the cost scales linearly wi
 The CPU baseline runs --cpu-pairs pairs (cKDTree query with workers=16, Umeyama by SVD, same stopping rule) and is
 scaled to the whole batch."""
 import argparse
-import json
 import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "pytorch-unsup-pc_amd")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
 import torch
 
@@ -98,15 +96,8 @@ def main():
     inits = np.stack(inits)
     call = lambda: R.icp_point_to_point(sources, targets, 0.2, init=inits, target_of=target_of)
     out = call()
-    torch.cuda.synchronize()
-    walls = []
-    for _ in range(a.reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = call()
-        torch.cuda.synchronize()
-        walls.append(time.perf_counter() - t0)
-    wall = sorted(walls)[len(walls) // 2]
+    walls = [ms / 1e3 for ms in BL.walls_ms(call, a.reps, warmup=0)]
+    wall = BL.upper_median(walls)
     iters = out[3].cpu().numpy()
     rounds = iters.astype(np.float64) + 1   # evaluations per pair
     pair_evals = float((rounds * a.n_src * a.n_tgt).sum())
@@ -123,7 +114,7 @@ def main():
     cpu_per_pair = (time.perf_counter() - t0) / len(idx)
     cpu_total = cpu_per_pair * P
     hist = np.bincount(iters, minlength=31).tolist()
-    print(json.dumps({
+    BL.emit({
         "bench": "icp_point_to_point", "pairs": P, "n_src": a.n_src, "n_tgt": a.n_tgt, "gt_size_assumed": True,
         "wall_s": round(wall, 4), "walls_s": [round(w, 4) for w in walls],
         "pair_evals": pair_evals, "pair_evals_per_s": pair_evals / wall,
@@ -132,7 +123,7 @@ def main():
         "cpu_ckdtree16_s_per_pair": round(cpu_per_pair, 4), "cpu_ckdtree16_s_scaled": round(cpu_total, 2),
         "cpu_pairs_timed": len(idx), "cpu_iterations": cpu_iters, "speedup_vs_cpu": round(cpu_total / wall, 1),
         "device": torch.cuda.get_device_name(0),
-    }))
+    })
 
 
 if __name__ == "__main__":

@@ -13,15 +13,13 @@ temporary directory, one run.  oracle_s_per_view: the numpy oracle of tests/mesh
 of the first models, per view, on the host that runs the benchmark.  Blender itself cannot be timed here (none is
 installed): no comparison with it is made."""
 import argparse
-import json
 import os
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "pytorch-unsup-pc_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
 import torch
 
@@ -39,7 +37,7 @@ def main():
     ap.add_argument("--supersample", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--oracle-views", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_render_bench.jsonl"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "mesh_render_bench.jsonl"))
     a = ap.parse_args()
     kd = np.array([[0.3, 0.3, 0.9], [0.9, 0.9, 0.2]])
     scenes = [O.grid_mesh(max(1, int(round((a.faces[i % len(a.faces)] / 2) ** 0.5))), seed=i) + (kd,) for i in range(a.models)]
@@ -49,14 +47,7 @@ def main():
     S, ss = a.image_size, a.supersample
     R.render_mesh_views(scenes[:2], pos[:2], image_size=32)  # warm-up: code object, allocator
     run = lambda: R.render_mesh_views(scenes, pos, image_size=S, supersample=ss)
-    run()
-    torch.cuda.synchronize(dev)
-    times = []
-    for _ in range(a.reps):
-        t0 = time.perf_counter()
-        run()
-        torch.cuda.synchronize(dev)
-        times.append((time.perf_counter() - t0) * 1e3)
+    times = BL.walls_ms(run, a.reps)
     kernels = {k: float(np.sum(v)) for k, v in _native.profile_kernels(run, dev).items()}
     names = ["m%03d" % i for i in range(a.models)]
     with tempfile.TemporaryDirectory() as tmp:
@@ -77,9 +68,7 @@ def main():
                 render_ms_min=min(times), render_ms_max=max(times), reps=a.reps,
                 views_per_s=a.models * a.views / (np.median(times) / 1e3), kernel_ms=kernels, tool_s=tool_s,
                 oracle_s_per_view=oracle_s, oracle_views=a.oracle_views, device=torch.cuda.get_device_name(dev))
-    print(json.dumps(line))
-    with open(a.out, "a") as fh:
-        fh.write(json.dumps(line) + "\n")
+    BL.emit(line, a.out)
 
 
 if __name__ == "__main__":

@@ -26,11 +26,9 @@ import json
 import os
 import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "pytorch-unsup-pc_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 
 
 def arguments():
@@ -46,7 +44,7 @@ def arguments():
     ap.add_argument("--parent-lib", default="")
     ap.add_argument("--child", choices=["flat", "shaded"], default="")
     ap.add_argument("--child-timeout", type=int, default=240)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_shaded_bench.jsonl"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "mesh_shaded_bench.jsonl"))
     return ap.parse_args()
 
 
@@ -71,17 +69,14 @@ def child(a):
     S, ss = a.image_size, a.supersample
 
     def measure(scenes):
-        run = lambda: R.render_mesh_views(scenes, pos, image_size=S, supersample=ss)
+        out = None
+
+        def run():
+            nonlocal out
+            out = R.render_mesh_views(scenes, pos, image_size=S, supersample=ss)
+
         R.render_mesh_views(scenes[:2], pos[:2], image_size=32)   # warm-up: code object, allocator
-        run()
-        torch.cuda.synchronize(dev)
-        times = []
-        for _ in range(a.reps):
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            out = run()
-            torch.cuda.synchronize(dev)
-            times.append((time.perf_counter() - t0) * 1e3)
+        times = BL.walls_ms(run, a.reps)
         kernels = {k: float(np.sum(v)) for k, v in _native.profile_kernels(run, dev).items()}
         return dict(render_ms_median=float(np.median(times)), render_ms_min=min(times), render_ms_max=max(times),
                     kernel_ms=kernels), out
@@ -144,9 +139,7 @@ def main():
                                flat_passes=bool(np.median(med["this"]) <= np.median(med["parent"]) + spread))
     res = run_child(a, "shaded", "")
     line.update(res)
-    print(json.dumps(line))
-    with open(a.out, "a") as fh:
-        fh.write(json.dumps(line) + "\n")
+    BL.emit(line, a.out)
 
 
 if __name__ == "__main__":

@@ -24,70 +24,30 @@ profiles/mesh_voxels_bench.jsonl (--out).
 
 Times are medians of --reps calls after a warm-up call, each call ended by a device synchronise."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "pytorch-unsup-pc_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
-
-HBM_PEAK = 8.0e12   # bytes per second, the data sheet's
 
 
 def resource_usage(path):
-    """hipcc -Rpass-analysis=kernel-resource-usage on csrc/dpc_mesh_voxels.hip, summarised by tools/resource_usage.py."""
-    import tempfile
-
-    csrc = os.path.join(PKG, "csrc")
-    with tempfile.TemporaryDirectory() as tmp:
-        log = os.path.join(tmp, "remarks.txt")
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics", "-mllvm",
-               "-pragma-unroll-threshold=400000", "-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage", "-c",
-               "dpc_mesh_voxels.hip", "-o", os.path.join(tmp, "x.o")]
-        res = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True, check=True)
-        open(log, "w").write(res.stderr)
-        rows = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), log], capture_output=True,
-                              text=True, check=True).stdout
-    text = ("# csrc/dpc_mesh_voxels.hip, hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -Rpass-analysis=kernel-resource-usage\n"
-            "# k_mv_surface<fp64 input, words per workgroup, threads>, k_mv_parity<fp64 input, threads>, k_mv_carve<threads>; lds= is\n"
-            "# the static part, all LDS is dynamic: k_mv_surface 4 bytes per word + 32 + 8 per thread (6176, 36896, 69664 B);\n"
-            "# k_mv_carve 4 (2 (zs + halo) + 2) PW and k_mv_parity 4 ((zs + halo + 2) PW + threads + 2 + threads / 64 + 1) for\n"
-            "# zs + halo planes of PW = H ceil(W / 32) words: at most 65536 B and 38988 B\n" + rows)
-    open(path, "w").write(text)
-    print(text, end="")
-
-
-def alternate(fns, reps):
-    """Median / min / max milliseconds of each fn of {name: fn}, the variants taking turns within every round."""
-    import torch
-
-    for fn in fns.values():
-        fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(reps):
-        for k, fn in fns.items():
-            t0 = time.perf_counter()
-            fn()
-            torch.cuda.synchronize()
-            times[k].append((time.perf_counter() - t0) * 1e3)
-    return {k: [round(float(np.median(v)), 3), round(float(min(v)), 3), round(float(max(v)), 3)] for k, v in times.items()}
+    BL.resource_usage("dpc_mesh_voxels.hip", path, [
+        "# k_mv_surface<fp64 input, words per workgroup, threads>, k_mv_parity<fp64 input, threads>, k_mv_carve<threads>; lds= is",
+        "# the static part, all LDS is dynamic: k_mv_surface 4 bytes per word + 32 + 8 per thread (6176, 36896, 69664 B);",
+        "# k_mv_carve 4 (2 (zs + halo) + 2) PW and k_mv_parity 4 ((zs + halo + 2) PW + threads + 2 + threads / 64 + 1) for",
+        "# zs + halo planes of PW = H ceil(W / 32) words: at most 65536 B and 38988 B"])
 
 
 def kernel_ms(fn, dev):
-    from dpc.render import _native
-
     fn()
-    return {k: round(float(sum(v)), 4) for k, v in _native.profile_kernels(fn, dev).items() if k.startswith("k_mv_")}
+    return BL.kernel_ms(fn, dev, "k_mv_")
 
 
 def share(nbytes, ms):
-    return round(nbytes / (ms * 1e-3) / HBM_PEAK, 5) if ms else None
+    return BL.share(nbytes, ms, BL.HBM_PEAK, 5)
 
 
 # --- the same rules from torch ops ---------------------------------------------------------------------------------
@@ -294,7 +254,7 @@ def bench_grid(a, G, fill, meshes, torch, R, O, dev):
     tg, topen = torch_voxelise(verts, faces, desc, shape, fill, a.torch_chunk)
     differs = int((tg != grids).sum()) + int((topen != ginfo[:, 1]).sum())
     del tg
-    t = alternate({"native_wall": lambda: R.voxelise_meshes(meshes, G, fill=fill), "native_call": native_call,
+    t = BL.alternate({"native_wall": lambda: R.voxelise_meshes(meshes, G, fill=fill), "native_call": native_call,
                    "torch": lambda: torch_voxelise(verts, faces, desc, shape, fill, a.torch_chunk)}, a.reps)
     km = kernel_ms(native_call, dev)
     n_faces, n_verts = int(faces.shape[0]), int(verts.shape[0])
@@ -330,8 +290,8 @@ def main():
     ap.add_argument("--grids", type=int, nargs="+", default=[32, 64, 128])
     ap.add_argument("--fills", nargs="+", default=["none", "carve", "parity"])
     ap.add_argument("--once", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_voxels_bench.jsonl"))
-    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(ROOT, "profiles", "mesh_voxels_resource_usage.txt"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "mesh_voxels_bench.jsonl"))
+    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(BL.ROOT, "profiles", "mesh_voxels_resource_usage.txt"))
     a = ap.parse_args()
     if a.resource_usage:
         resource_usage(a.resource_usage)
@@ -346,13 +306,8 @@ def main():
     for G in a.grids:
         for fill in a.fills:
             res = bench_grid(a, G, fill, meshes, torch, R, O, dev)
-            if res is None:
-                continue
-            line = json.dumps(res)
-            print(line, flush=True)
-            if a.out:
-                with open(a.out, "a") as fh:
-                    fh.write(line + "\n")
+            if res is not None:
+                BL.emit(res, a.out)
 
 
 if __name__ == "__main__":

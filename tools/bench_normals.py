@@ -27,41 +27,21 @@ to profiles/normals_bench.jsonl (--out).
 
 Times are medians of --reps calls after a warm-up call, each call ended by a device synchronise."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "pytorch-unsup-pc_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
 
-FP32_PEAK = 157.3e12   # vector fp32 operations per second, the data sheet's (an fma counted as two)
 OPS_PER_PAIR = 8       # csrc/dpc_knn.hip pair_d2: 3 sub, 3 mul, 2 add, nothing fused
 
 
 def resource_usage(path):
-    """hipcc -Rpass-analysis=kernel-resource-usage on csrc/dpc_knn.hip, summarised by tools/resource_usage.py."""
-    import tempfile
-
-    csrc = os.path.join(PKG, "csrc")
-    with tempfile.TemporaryDirectory() as tmp:
-        log = os.path.join(tmp, "remarks.txt")
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics", "-mllvm",
-               "-pragma-unroll-threshold=400000", "-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage", "-c", "dpc_knn.hip",
-               "-o", os.path.join(tmp, "x.o")]
-        res = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True, check=True)
-        open(log, "w").write(res.stderr)
-        rows = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), log], capture_output=True,
-                              text=True, check=True).stdout
-    text = ("# csrc/dpc_knn.hip, hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -Rpass-analysis=kernel-resource-usage\n"
-            "# k_knn<T, B>: lds= is the static part (the row prefix's partial sums); the lists and the tile are dynamic,\n"
-            "# B k (sizeof(T) + 4) + 3 x 512 sizeof(T) bytes: 38 KiB (fp32) / 60 KiB (fp64) at the top of each k band\n" + rows)
-    open(path, "w").write(text)
-    print(text, end="")
+    BL.resource_usage("dpc_knn.hip", path, [
+        "# k_knn<T, B>: lds= is the static part (the row prefix's partial sums); the lists and the tile are dynamic,",
+        "# B k (sizeof(T) + 4) + 3 x 512 sizeof(T) bytes: 38 KiB (fp32) / 60 KiB (fp64) at the top of each k band"])
 
 
 def clouds(a):
@@ -76,20 +56,6 @@ def clouds(a):
         for v in range(a.views):
             preds[m * a.views + v] = g[rng.integers(0, len(g), size=a.points)] + 0.004 * rng.normal(size=(a.points, 3))
     return preds, gts, [m for m in range(a.models) for _ in range(a.views)]
-
-
-def median_ms(fn, reps):
-    import torch
-
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append((time.perf_counter() - t0) * 1e3)
-    return [round(float(np.median(times)), 3), round(float(min(times)), 3), round(float(max(times)), 3)]
 
 
 def torch_normals(P, k):
@@ -125,7 +91,6 @@ def bench(a, k, preds, gts, gt_of, torch, dev):
 
     knn_call()
     pca_call()
-    torch.cuda.synchronize()
     assert R.check_status(dev) == 0
     split_in = [(preds[m * a.views:(m + 1) * a.views], None) for m in range(a.models)]
     if a.once:
@@ -133,16 +98,15 @@ def bench(a, k, preds, gts, gt_of, torch, dev):
         return None
     pairs = n_clouds * n * n
     res = {"bench": "normals", "k": k, "models": a.models, "views": a.views, "points": n, "gt_points": a.gt_points, "reps": a.reps,
-           "block": _native.knn_block(k), "pairs": pairs, "ops_per_pair": OPS_PER_PAIR, "fp32_vector_peak_flops": FP32_PEAK}
-    res["knn_wall_ms_median_min_max"] = median_ms(lambda: R.knn_batched(preds.reshape(-1, 3), rows, k), a.reps)
-    res["knn_native_call_ms_median_min_max"] = median_ms(knn_call, a.reps)
-    res["pca_native_call_ms_median_min_max"] = median_ms(pca_call, a.reps)
-    km = _native.profile_kernels(lambda: (knn_call(), pca_call()), dev)
-    res["kernel_ms"] = {name: round(float(sum(v)), 4) for name, v in km.items()}
+           "block": _native.knn_block(k), "pairs": pairs, "ops_per_pair": OPS_PER_PAIR, "fp32_vector_peak_flops": BL.FP32_VECTOR_PEAK}
+    res["knn_wall_ms_median_min_max"] = BL.median_ms(lambda: R.knn_batched(preds.reshape(-1, 3), rows, k), a.reps)
+    res["knn_native_call_ms_median_min_max"] = BL.median_ms(knn_call, a.reps)
+    res["pca_native_call_ms_median_min_max"] = BL.median_ms(pca_call, a.reps)
+    res["kernel_ms"] = BL.kernel_ms(lambda: (knn_call(), pca_call()), dev)
     knn_s = res["kernel_ms"]["k_knn"] * 1e-3
     res["knn_pairs_per_s"] = round(pairs / knn_s, 1)
-    res["knn_share_of_fp32_vector_peak"] = round(pairs * OPS_PER_PAIR / knn_s / FP32_PEAK, 4)
-    res["split_wall_ms_median_min_max"] = median_ms(lambda: R.normal_consistency_of_split(split_in, gts, k=k), max(1, a.reps // 2))
+    res["knn_share_of_fp32_vector_peak"] = BL.share(pairs * OPS_PER_PAIR, res["kernel_ms"]["k_knn"], BL.FP32_VECTOR_PEAK, 4)
+    res["split_wall_ms_median_min_max"] = BL.median_ms(lambda: R.normal_consistency_of_split(split_in, gts, k=k), max(1, a.reps // 2))
     # the torch composition, one cloud at a time
     t = min(a.torch_clouds, n_clouds)
     Pt = [packed[i * n:(i + 1) * n] for i in range(t)]
@@ -155,7 +119,7 @@ def bench(a, k, preds, gts, gt_of, torch, dev):
     res["torch_clouds"] = t
     res["share_of_list_entries_equal_to_torch"] = round(min(same_idx), 6)
     res["median_sin_angle_to_torch_normals"] = worst
-    t_ms = median_ms(lambda: [torch_normals(p, k) for p in Pt], max(1, a.reps // 2))
+    t_ms = BL.median_ms(lambda: [torch_normals(p, k) for p in Pt], max(1, a.reps // 2))
     res["torch_ms_median_min_max"] = t_ms
     res["torch_ms_per_cloud"] = round(t_ms[0] / t, 4)
     native = (res["knn_native_call_ms_median_min_max"][0] + res["pca_native_call_ms_median_min_max"][0]) / n_clouds
@@ -182,11 +146,11 @@ def nearest_context(a, preds, torch, dev):
     n_clouds, n = preds.shape[0], preds.shape[1]
     packed = torch.from_numpy(preds.reshape(-1, 3)).to(dev)
     rows = np.asarray([(i * n, n, i * n, n) for i in range(n_clouds)], dtype=np.int32)
-    knn = median_ms(lambda: normals._knn(packed, rows, 1, dev, True), a.reps)
-    near = median_ms(lambda: R.nearest_batched(packed, rows, return_distances=True), a.reps)
-    km = _native.profile_kernels(lambda: (normals._knn(packed, rows, 1, dev, True), R.nearest_batched(packed, rows, return_distances=True)), dev)
+    knn = BL.median_ms(lambda: normals._knn(packed, rows, 1, dev, True), a.reps)
+    near = BL.median_ms(lambda: R.nearest_batched(packed, rows, return_distances=True), a.reps)
+    km = BL.kernel_ms(lambda: (normals._knn(packed, rows, 1, dev, True), R.nearest_batched(packed, rows, return_distances=True)), dev)
     return {"bench": "normals_k1_context", "clouds": n_clouds, "points": n, "knn_k1_ms_median_min_max": knn,
-            "nearest_batched_ms_median_min_max": near, "kernel_ms": {name: round(float(sum(v)), 4) for name, v in km.items()},
+            "nearest_batched_ms_median_min_max": near, "kernel_ms": km,
             "device": torch.cuda.get_device_name(0)}
 
 
@@ -201,8 +165,8 @@ def main():
     ap.add_argument("--torch-clouds", type=int, default=5)
     ap.add_argument("--oracle-points", type=int, default=2000)
     ap.add_argument("--once", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "normals_bench.jsonl"))
-    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(ROOT, "profiles", "normals_resource_usage.txt"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "normals_bench.jsonl"))
+    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(BL.ROOT, "profiles", "normals_resource_usage.txt"))
     a = ap.parse_args()
     if a.resource_usage:
         resource_usage(a.resource_usage)
@@ -213,13 +177,8 @@ def main():
     preds, gts, gt_of = clouds(a)
     for k in list(a.k) + ([] if a.once else [None]):
         res = nearest_context(a, preds, torch, dev) if k is None else bench(a, k, preds, gts, gt_of, torch, dev)
-        if res is None:
-            continue
-        line = json.dumps(res)
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "a") as fh:
-                fh.write(line + "\n")
+        if res is not None:
+            BL.emit(res, a.out)
 
 
 if __name__ == "__main__":

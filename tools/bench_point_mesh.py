@@ -29,40 +29,19 @@ profiles/point_mesh_bench.jsonl (--out).
 Times are medians of --reps calls after a warm-up call, each call ended by a device synchronise."""
 import argparse
 import ctypes
-import json
 import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "pytorch-unsup-pc_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
 
-FP64_PEAK = 78.6e12      # vector fp64 operations per second, the data sheet's
 FLOPS_PER_TEST = 80      # 25 fma x 2 + 14 mul + 7 add / sub + 9 min / max (csrc/dpc_point_mesh.hip: pm_d2 and the running min)
 
 
 def resource_usage(path):
-    """hipcc -Rpass-analysis=kernel-resource-usage on csrc/dpc_point_mesh.hip, summarised by tools/resource_usage.py."""
-    import tempfile
-
-    csrc = os.path.join(PKG, "csrc")
-    with tempfile.TemporaryDirectory() as tmp:
-        log = os.path.join(tmp, "remarks.txt")
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics", "-mllvm",
-               "-pragma-unroll-threshold=400000", "-Rpass-analysis=kernel-resource-usage", "-c", "dpc_point_mesh.hip", "-o",
-               os.path.join(tmp, "x.o")]
-        res = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True, check=True)
-        open(log, "w").write(res.stderr)
-        rows = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), log], capture_output=True,
-                              text=True, check=True).stdout
-    text = ("# csrc/dpc_point_mesh.hip, hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage\n"
-            "# k_pm_dist<fp64 points, fp64 vertices>: lds= is the face tile, DPC_PM_FACE_TILE records of 12 double2 (static)\n" + rows)
-    open(path, "w").write(text)
-    print(text, end="")
+    BL.resource_usage("dpc_point_mesh.hip", path, [
+        "# k_pm_dist<fp64 points, fp64 vertices>: lds= is the face tile, DPC_PM_FACE_TILE records of 12 double2 (static)"])
 
 
 _base = {}
@@ -128,20 +107,6 @@ def torch_d2(P, tri, pairs):
     return out
 
 
-def median_ms(fn, reps):
-    import torch
-
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append((time.perf_counter() - t0) * 1e3)
-    return [round(float(np.median(times)), 3), round(float(min(times)), 3), round(float(max(times)), 3)]
-
-
 def measure(clouds, meshes, mesh_of, reps, once, torch, dev):
     """Times of one workload: wall, native call, kernel; and the packed buffers' native result."""
     from dpc.render import _batch, _native, pointmesh
@@ -164,19 +129,17 @@ def measure(clouds, meshes, mesh_of, reps, once, torch, dev):
         _native.check(rc, "dpc_point_mesh_distance")
 
     native_call()
-    torch.cuda.synchronize()
     assert int(status.item()) == 0
     tests = int(sum(int(r[1]) * int(r[5]) for r in plan.desc))
     if once:
         return {"tests": tests}, d2
-    wall = median_ms(lambda: pointmesh.point_mesh_distance(clouds, meshes, mesh_of, squared=True), reps)
-    call = median_ms(native_call, reps)
-    km = _native.profile_kernels(native_call, dev)
-    k_ms = {k: round(float(sum(v)), 4) for k, v in km.items() if k.startswith("k_pm_")}
+    wall = BL.median_ms(lambda: pointmesh.point_mesh_distance(clouds, meshes, mesh_of, squared=True), reps)
+    call = BL.median_ms(native_call, reps)
+    k_ms = BL.kernel_ms(native_call, dev, "k_pm_")
     dist_s = k_ms["k_pm_dist"] * 1e-3
     return {"tests": tests, "rows": len(plan.desc), "wall_ms_median_min_max": wall, "native_call_ms_median_min_max": call,
             "kernel_ms": k_ms, "tests_per_s": round(tests / dist_s, 1),
-            "share_of_fp64_vector_peak": round(tests * FLOPS_PER_TEST / dist_s / FP64_PEAK, 4)}, d2
+            "share_of_fp64_vector_peak": BL.share(tests * FLOPS_PER_TEST, k_ms["k_pm_dist"], BL.FP64_VECTOR_PEAK, 4)}, d2
 
 
 def bench(a, kind, faces, torch, dev):
@@ -197,12 +160,12 @@ def bench(a, kind, faces, torch, dev):
     got = d2[:k * a.views * a.points]
     S = max(float(pts[:k * a.views].__abs__().max()), max(float(np.abs(V).max()) for V, _ in meshes[:k]))
     differs = float((got - ref).abs().max()) / (2.0 ** -52 * S * S)
-    t_ms = median_ms(run, max(1, a.reps // 2))
+    t_ms = BL.median_ms(run, max(1, a.reps // 2))
     torch_tests = k * a.views * a.points * len(meshes[0][1])
     torch_ns = t_ms[0] * 1e6 / torch_tests
     native_ns = batch["native_call_ms_median_min_max"][0] * 1e6 / batch["tests"]
     return {"bench": "point_mesh", "kind": kind, "faces_per_mesh": len(meshes[0][1]), "models": a.models, "views": a.views,
-            "points": a.points, "reps": a.reps, "flops_per_test": FLOPS_PER_TEST, "fp64_vector_peak_flops": FP64_PEAK,
+            "points": a.points, "reps": a.reps, "flops_per_test": FLOPS_PER_TEST, "fp64_vector_peak_flops": BL.FP64_VECTOR_PEAK,
             "batch": batch, "single_view": single, "torch_models": k, "torch_pairs_per_chunk": a.torch_pairs,
             "torch_ms_median_min_max": t_ms, "torch_ns_per_test": round(torch_ns, 5), "native_call_ns_per_test": round(native_ns, 6),
             "ratio_torch_over_native_per_test": round(torch_ns / native_ns, 1), "max_difference_from_torch_in_units": round(differs, 3),
@@ -220,8 +183,8 @@ def main():
     ap.add_argument("--torch-models", type=int, default=1)
     ap.add_argument("--torch-pairs", type=int, default=1 << 24)
     ap.add_argument("--once", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "point_mesh_bench.jsonl"))
-    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(ROOT, "profiles", "point_mesh_resource_usage.txt"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "point_mesh_bench.jsonl"))
+    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(BL.ROOT, "profiles", "point_mesh_resource_usage.txt"))
     a = ap.parse_args()
     if a.resource_usage:
         resource_usage(a.resource_usage)
@@ -232,13 +195,8 @@ def main():
     for kind in a.kinds:
         for faces in a.faces:
             res = bench(a, kind, faces, torch, dev)
-            if res is None:
-                continue
-            line = json.dumps(res)
-            print(line, flush=True)
-            if a.out:
-                with open(a.out, "a") as fh:
-                    fh.write(line + "\n")
+            if res is not None:
+                BL.emit(res, a.out)
 
 
 if __name__ == "__main__":

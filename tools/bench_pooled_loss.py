@@ -17,7 +17,6 @@ JSON line per variant: median and spread (min, max) of the per-step time in us.
 (--variants: time only these, e.g. one variant per process under rocprofv3 --kernel-trace --stats for its kernel times)
 """
 import argparse
-import json
 import os
 import statistics
 import sys
@@ -25,10 +24,8 @@ import sys
 import torch
 import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "pytorch-unsup-pc_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 
 import dpc.render as R  # noqa: E402
 
@@ -74,10 +71,8 @@ def main():
         plan, pc, q, s, masks, w = setup(name, device)
         pre = F.avg_pool2d(masks, 2).permute(0, 2, 3, 1).contiguous()
         plan.run(pc, q, s, pre)
-        torch.cuda.synchronize()
-        a = outputs(plan)
+        a = outputs(plan)          # clones on the stream the plan ran on
         plan.run(pc, q, s, masks)
-        torch.cuda.synchronize()
         b = outputs(plan)
         for what, x, y in zip(("loss", "proj", "winner", "dpc", "dq", "ds"), a, b):
             assert torch.equal(x, y), "%s: %s differs between pre-pooled and in-kernel pooled masks" % (name, what)
@@ -88,24 +83,12 @@ def main():
             "torch": lambda: plan.run(pc, q, s, F.avg_pool2d(masks, 2).permute(0, 2, 3, 1).contiguous()),
         }
         variants = {k: variants[k] for k in args.variants.split(",")}
-        for fn in variants.values():
-            for _ in range(args.warmup):
-                fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in variants}
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for _ in range(args.windows):
-            for k, fn in variants.items():
-                ev0.record()
-                for _ in range(args.steps):
-                    fn()
-                ev1.record()
-                ev1.synchronize()
-                times[k].append(1e3 * ev0.elapsed_time(ev1) / args.steps)
-        for k, t in times.items():
-            print(json.dumps({"tool": "bench_pooled_loss", "config": name, "variant": k, "us_per_step_median": round(statistics.median(t), 3),
-                              "us_min": round(min(t), 3), "us_max": round(max(t), 3), "windows": args.windows,
-                              "steps_per_window": args.steps, "bit_identical_pre_vs_kernel": True}), flush=True)
+        times = BL.event_window_times(variants, args.steps, args.warmup, args.windows)
+        for k, ms in times.items():
+            t = [1e3 * x for x in ms]
+            BL.emit({"tool": "bench_pooled_loss", "config": name, "variant": k, "us_per_step_median": round(statistics.median(t), 3),
+                     "us_min": round(min(t), 3), "us_max": round(max(t), 3), "windows": args.windows,
+                     "steps_per_window": args.steps, "bit_identical_pre_vs_kernel": True})
 
 
 if __name__ == "__main__":

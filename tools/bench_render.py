@@ -12,15 +12,13 @@ warm-up, over --reps repeats (median, min, max).  tool_s: the runner end to end 
 run.  oracle_s_per_image: the numpy oracle of tests/render_oracle.py on --oracle-images images, per image, on the host
 that runs the benchmark.  Blender itself cannot be timed here (none is installed): no comparison with it is made."""
 import argparse
-import json
 import os
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "pytorch-unsup-pc_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
 import torch
 
@@ -37,7 +35,7 @@ def main():
     ap.add_argument("--supersample", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--oracle-images", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "render_bench.jsonl"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "render_bench.jsonl"))
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     clouds = [(np.tanh(rng.standard_normal((a.points, 3))) * 0.5).astype(np.float32) for _ in range(a.clouds)]
@@ -45,14 +43,7 @@ def main():
     R.render_point_clouds(clouds[:2], image_size=64)  # warm-up: code object, allocator
     for S in a.sizes:
         run = lambda: R.render_point_clouds(clouds, image_size=S, supersample=a.supersample)
-        run()
-        torch.cuda.synchronize(dev)
-        times = []
-        for _ in range(a.reps):
-            t0 = time.perf_counter()
-            run()
-            torch.cuda.synchronize(dev)
-            times.append((time.perf_counter() - t0) * 1e3)
+        times = BL.walls_ms(run, a.reps)
         with tempfile.TemporaryDirectory() as tmp:
             t0 = time.perf_counter()
             R.render_split(list(range(a.clouds)), lambda i: clouds[i][None],
@@ -69,9 +60,7 @@ def main():
                     reps=a.reps, images_per_s=a.clouds / (np.median(times) / 1e3), tool_s=tool_s,
                     oracle_s_per_image=oracle_s, oracle_images=a.oracle_images,
                     oracle_s_split_scaled=oracle_s * a.clouds, device=torch.cuda.get_device_name(dev))
-        print(json.dumps(line))
-        with open(a.out, "a") as fh:
-            fh.write(json.dumps(line) + "\n")
+        BL.emit(line, a.out)
 
 
 if __name__ == "__main__":

@@ -23,14 +23,11 @@ deterministic route fed colour sets [clouds / set-replicas, points, 3] and a poi
 cloud), and "replicate_rgb", the replicate_rgb call (and its autograd backward) that the default route needs in front of it
 for the same sets and index.  --route new|fixed: one route alone.  Lines go to profiles/rgb_splat_fixed_bench.jsonl."""
 import argparse
-import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "pytorch-unsup-pc_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import torch
 
 import dpc.render as R
@@ -42,16 +39,6 @@ CONFIGS = {"default": {}, "divide_by_occupancies": {"pc_rgb_divide_by_occupancie
 
 class Cfg(dict):
     __getattr__ = dict.__getitem__
-
-
-def event_ms(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
 
 
 def torch_rgb_loss(cfg, geom, tr, rgb, vox, kernel, images, f):
@@ -172,32 +159,20 @@ def run_config(a, name, dev):
             agree[nm + "_max_abs_diff_over_scale"] = float((gn - x.grad).abs().max()) / max(1.0, float(x.grad.abs().max()))
         if a.deterministic:   # the point of the route: the same bits from call to call
             agree["fixed_loss_bit_equal_on_repeat"] = bool(torch.equal(fns["fixed_forward_ms"](), fns["fixed_forward_ms"]()))
-    for fn in fns.values():          # every shape the timed windows use
-        for _ in range(a.warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(a.windows):       # alternate the routes window by window
-        for k, fn in fns.items():
-            times[k].append(event_ms(fn, a.reps))
-    med = {k: round(sorted(v)[len(v) // 2], 4) for k, v in times.items()}
+    med, spread = BL.event_windows(fns, a.reps, a.warmup, a.windows)
     res = {"bench": "rgb_splat_fixed" if a.deterministic else "rgb_loss", "config": name, "clouds": B, "points": N, "grid": G, "gt_factor": f, "sigma_rel": 1.5, "taps": 11,
            "reps": a.reps, "warmup": a.warmup, "windows": a.windows, "route": a.route, "timing": "device events, median window",
            "colour_grid_mb": round(B * 3 * G * G * G * 4 / 1e6, 1), "splat_atomic_mb": round(B * N * 8 * 3 * 4 / 1e6, 1),
            **({"fixed_workspace_mb": round((B * 3 * G * G * G * 8 + B * 4) / 1e6, 1), "fixed_atomic_mb": round(B * N * 8 * 3 * 8 / 1e6, 1),
                "set_replicas": a.set_replicas} if a.deterministic else {}), **med,
-           "spread_ms": {k: [round(min(v), 4), round(max(v), 4)] for k, v in times.items()},
+           "spread_ms": spread,
            "device": torch.cuda.get_device_name(0)}
     if a.route == "both":
         if not a.deterministic:
             res["speedup_forward"] = round(med["torch_forward_ms"] / med["new_forward_ms"], 2)
             res["speedup_forward_backward"] = round(med["torch_forward_backward_ms"] / med["new_forward_backward_ms"], 2)
         res["agreement"] = agree
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "a") as fh:
-            fh.write(line + "\n")
+    BL.emit(res, a.out)
 
 
 def main():
@@ -216,7 +191,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "rgb_splat_fixed_bench.jsonl" if a.deterministic else "rgb_loss_bench.jsonl")
+        a.out = os.path.join(BL.ROOT, "profiles", "rgb_splat_fixed_bench.jsonl" if a.deterministic else "rgb_loss_bench.jsonl")
     if (a.route == "fixed" and not a.deterministic) or (a.route == "torch" and a.deterministic):
         ap.error("--route fixed goes with --deterministic, --route torch without it")
     if a.deterministic and (a.set_replicas < 1 or a.clouds % a.set_replicas):

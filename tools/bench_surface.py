@@ -14,40 +14,20 @@ oracle's for those grids before anything is timed.  There is no pass mark: nothi
 
 Times are medians of --reps calls after a warm-up call, each call ended by a device synchronise."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "pytorch-unsup-pc_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
 
-HBM_PEAK = 8.0e12   # bytes per second, the data sheet's
 TILE = 1024         # nodes of a workgroup (csrc/dpc_surface.hip)
 
 
 def resource_usage(path):
-    """hipcc -Rpass-analysis=kernel-resource-usage on csrc/dpc_surface.hip, summarised by tools/resource_usage.py."""
-    import tempfile
-
-    csrc = os.path.join(PKG, "csrc")
-    with tempfile.TemporaryDirectory() as tmp:
-        log = os.path.join(tmp, "remarks.txt")
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics", "-mllvm",
-               "-pragma-unroll-threshold=400000", "-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage", "-c",
-               "dpc_surface.hip", "-o", os.path.join(tmp, "x.o")]
-        res = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True, check=True)
-        open(log, "w").write(res.stderr)
-        rows = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), log], capture_output=True,
-                              text=True, check=True).stdout
-    text = ("# csrc/dpc_surface.hip, hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -Rpass-analysis=kernel-resource-usage\n"
-            "# k_surface_tiles<fp64 input>, k_surface_verts<fp64 input>; all LDS is static\n" + rows)
-    open(path, "w").write(text)
-    print(text, end="")
+    BL.resource_usage("dpc_surface.hip", path, [
+        "# k_surface_tiles<fp64 input>, k_surface_verts<fp64 input>; all LDS is static"])
 
 
 def clouds(B, n, seed):
@@ -65,8 +45,6 @@ class _Cfg:
 
 
 def bench(a, G, torch, R, O, dev):
-    from dpc.render import _native
-
     B = a.grids
     if G <= 64:
         pts = torch.from_numpy(clouds(B, 8000, G)).to(dev)
@@ -88,14 +66,8 @@ def bench(a, G, torch, R, O, dev):
         assert np.array_equal(meshes[i][0].cpu().numpy(), verts) and np.array_equal(meshes[i][1].cpu().numpy(), faces), "differs from the oracle"
     host_ms = (time.perf_counter() - t0) * 1e3 / max(k, 1)
     assert R.check_status() == 0
-    torch.cuda.synchronize()
-    wall = []
-    for _ in range(a.reps):
-        t0 = time.perf_counter()
-        run()
-        torch.cuda.synchronize()
-        wall.append((time.perf_counter() - t0) * 1e3)
-    km = {n: round(float(sum(v)), 4) for n, v in _native.profile_kernels(run, dev).items() if n.startswith("k_surface")}
+    wall = BL.walls_ms(run, a.reps, warmup=0)         # run() above was the warm-up call
+    km = BL.kernel_ms(run, dev, "k_surface")
     nodes, tiles = B * G ** 3, B * -(-G ** 3 // TILE)
     # what each kernel must move: tiles and scan run in both calls; the map is one int32 a node
     nbytes = {"k_surface_tiles": 2 * (nodes * 4 + tiles * 8), "k_surface_scan": 2 * (2 * tiles * 8),
@@ -103,9 +75,9 @@ def bench(a, G, torch, R, O, dev):
     return {
         "bench": "surface", "measured_on": "%s (%s)" % (torch.cuda.get_device_name(0), torch.cuda.get_device_properties(0).gcnArchName.split(":")[0]), "grid": G, "grids": B, "source": source, "iso_level": iso,
         "vertices": nv, "faces": nf, "reps": a.reps,
-        "wall_ms_median_min_max": [round(float(np.median(wall)), 3), round(min(wall), 3), round(max(wall), 3)],
+        "wall_ms_median_min_max": BL.stats(wall),
         "kernel_ms": km, "kernel_bytes": nbytes,
-        "kernel_share_of_hbm_peak": {n: (round(b / (km[n] * 1e-3) / HBM_PEAK, 4) if km.get(n) else None) for n, b in nbytes.items()},
+        "kernel_share_of_hbm_peak": {n: BL.share(b, km.get(n), BL.HBM_PEAK, 4) for n, b in nbytes.items()},
         "numpy_grids_timed": k, "numpy_host_ms_per_grid": round(host_ms, 1), "numpy_host_ms_scaled_to_batch": round(host_ms * B, 1),
     }
 
@@ -115,8 +87,8 @@ def main():
     ap.add_argument("--grids", type=int, default=32)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--host-items", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "surface_bench.jsonl"))
-    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(ROOT, "profiles", "surface_resource_usage.txt"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "surface_bench.jsonl"))
+    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(BL.ROOT, "profiles", "surface_resource_usage.txt"))
     a = ap.parse_args()
     if a.resource_usage:
         resource_usage(a.resource_usage)
@@ -128,11 +100,7 @@ def main():
 
     dev = torch.device("cuda")
     for G in (64, 128):
-        line = json.dumps(bench(a, G, torch, R, O, dev))
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "a") as fh:
-                fh.write(line + "\n")
+        BL.emit(bench(a, G, torch, R, O, dev), a.out)
 
 
 if __name__ == "__main__":

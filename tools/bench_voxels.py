@@ -19,69 +19,28 @@ appended to profiles/voxels_bench.jsonl (--out).
 
 Times are medians of --reps calls after a warm-up call, each call ended by a device synchronise."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "pytorch-unsup-pc_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
-
-HBM_PEAK = 8.0e12   # bytes per second, the data sheet's
 
 
 def resource_usage(path):
-    """hipcc -Rpass-analysis=kernel-resource-usage on csrc/dpc_voxels.hip, summarised by tools/resource_usage.py."""
-    import tempfile
-
-    csrc = os.path.join(PKG, "csrc")
-    with tempfile.TemporaryDirectory() as tmp:
-        log = os.path.join(tmp, "remarks.txt")
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics", "-mllvm",
-               "-pragma-unroll-threshold=400000", "-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage", "-c",
-               "dpc_voxels.hip", "-o", os.path.join(tmp, "x.o")]
-        res = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True, check=True)
-        open(log, "w").write(res.stderr)
-        rows = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), log], capture_output=True,
-                              text=True, check=True).stdout
-    text = ("# csrc/dpc_voxels.hip, hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -Rpass-analysis=kernel-resource-usage\n"
-            "# k_voxelise<fp64 input, words per workgroup, threads>; lds= is the static part, k_voxelise's bits are dynamic:\n"
-            "# 4 bytes per word + 16, i.e. 4112, 32784 and 65552 B\n" + rows)
-    open(path, "w").write(text)
-    print(text, end="")
-
-
-def alternate(fns, reps):
-    """Median / min / max milliseconds of each fn of {name: fn}, the variants taking turns within every round."""
-    import torch
-
-    for fn in fns.values():
-        fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(reps):
-        for k, fn in fns.items():
-            t0 = time.perf_counter()
-            fn()
-            torch.cuda.synchronize()
-            times[k].append((time.perf_counter() - t0) * 1e3)
-    return {k: [round(float(np.median(v)), 3), round(float(min(v)), 3), round(float(max(v)), 3)] for k, v in times.items()}
+    BL.resource_usage("dpc_voxels.hip", path, [
+        "# k_voxelise<fp64 input, words per workgroup, threads>; lds= is the static part, k_voxelise's bits are dynamic:",
+        "# 4 bytes per word + 16, i.e. 4112, 32784 and 65552 B"])
 
 
 def kernel_ms(fn, dev):
-    """{kernel family: milliseconds, summed over its launches} of one call of fn, from the library's launch record."""
-    from dpc.render import _native
-
     fn()
-    return {k: round(float(sum(v)), 4) for k, v in _native.profile_kernels(fn, dev).items() if k.startswith("k_vox")}
+    return BL.kernel_ms(fn, dev, "k_vox")
 
 
 def share(nbytes, ms):
-    return round(nbytes / (ms * 1e-3) / HBM_PEAK, 4) if ms else None
+    return BL.share(nbytes, ms, BL.HBM_PEAK, 4)
 
 
 # --- the same rules from torch ops ---------------------------------------------------------------------------------
@@ -171,7 +130,7 @@ def bench_split(a, G, torch, R, O, dev):
     gb, _ = VX._bits_of_clouds(gt_list, shape, dev, "bench")
     pg, _ = torch_voxelise(pred_d, shape)
     gg, _ = torch_voxelise(gt_d, shape)
-    t = alternate({
+    t = BL.alternate({
         "native_split": lambda: R.iou_of_split(pred_h, gt_h, vox_size=G),
         "native_stages": native_stages, "torch_stages": torch_stages,
         "native_voxelise_pred": lambda: VX._bits_of_clouds(pred_list, shape, dev, "bench"),
@@ -236,7 +195,7 @@ def bench_grids(a, torch, R, O, dev):
         assert O.stats(O.threshold(vh[i], 0.5, True), gh[gt_of[i]]).tolist() == ns[i].cpu().tolist()
         assert O.voxel2pc(vh[i], 0.5)[0].tobytes() == pts[i].cpu().numpy().tobytes()
     host_ms = (time.perf_counter() - t0) * 1e3 / max(k, 1)
-    t = alternate({
+    t = BL.alternate({
         "native_threshold": lambda: VX._bits_of_grids(v, 0.5, True, dev), "torch_threshold": lambda: v >= 0.5,
         "native_stats": lambda: VX._pair_stats(pb, gb, pairs, shape), "torch_stats": lambda: torch_stats(occ.view(P, -1), gflat, gt_of_d),
         "native_threshold_stats": lambda: R.voxel_stats(v, gt, gt_of=gt_of.tolist(), threshold=0.5),
@@ -266,8 +225,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--host-items", type=int, default=2)
     ap.add_argument("--once", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "voxels_bench.jsonl"))
-    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(ROOT, "profiles", "voxels_resource_usage.txt"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "voxels_bench.jsonl"))
+    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(BL.ROOT, "profiles", "voxels_resource_usage.txt"))
     a = ap.parse_args()
     if a.resource_usage:
         resource_usage(a.resource_usage)
@@ -280,13 +239,8 @@ def main():
     dev = torch.device("cuda")
     lines = [bench_split(a, 64, torch, R, O, dev), bench_split(a, 128, torch, R, O, dev), bench_grids(a, torch, R, O, dev)]
     for res in lines:
-        if res is None:
-            continue
-        line = json.dumps(res)
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "a") as fh:
-                fh.write(line + "\n")
+        if res is not None:
+            BL.emit(res, a.out)
 
 
 if __name__ == "__main__":

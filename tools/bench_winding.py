@@ -17,44 +17,22 @@ per shape, appended to profiles/winding_bench.jsonl (--out).
 
 Times are medians of --reps calls after a warm-up call, each call ended by a device synchronise."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "pytorch-unsup-pc_amd")
-for p in (ROOT, PKG, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib as BL
 import numpy as np
-
-import bench_point_mesh as PM
 
 POINTS_SHAPE = (100000, 20000)      # query points, faces
 VOXELS_SHAPE = (32, 32)             # meshes, grid side
 VOXEL_FACES = 1280
-median_ms = PM.median_ms
 
 
 def resource_usage(path):
-    """hipcc -Rpass-analysis=kernel-resource-usage on csrc/dpc_winding.hip, summarised by tools/resource_usage.py."""
-    import tempfile
-
-    csrc = os.path.join(PKG, "csrc")
-    with tempfile.TemporaryDirectory() as tmp:
-        log = os.path.join(tmp, "remarks.txt")
-        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics", "-mllvm",
-               "-pragma-unroll-threshold=400000", "-Rpass-analysis=kernel-resource-usage", "-c", "dpc_winding.hip", "-o",
-               os.path.join(tmp, "x.o")]
-        res = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True, check=True)
-        open(log, "w").write(res.stderr)
-        rows = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), log], capture_output=True,
-                              text=True, check=True).stdout
-    text = ("# csrc/dpc_winding.hip, hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage\n"
-            "# k_wn_sum<fp64 points, fp64 vertices>, k_wn_vox<fp64 vertices>: lds= is the face tile, DPC_PM_FACE_TILE records of\n"
-            "# 5 double2 (static); k_wn_finish, k_wn_vox_finish: one lane per output point / node\n" + rows)
-    open(path, "w").write(text)
-    print(text, end="")
+    BL.resource_usage("dpc_winding.hip", path, [
+        "# k_wn_sum<fp64 points, fp64 vertices>, k_wn_vox<fp64 vertices>: lds= is the face tile, DPC_PM_FACE_TILE records of",
+        "# 5 double2 (static); k_wn_finish, k_wn_vox_finish: one lane per output point / node"])
 
 
 def mesh(faces, seed=0):
@@ -87,9 +65,7 @@ def torch_sums(P, tri, pairs):
 
 
 def kernels(fn, dev):
-    from dpc.render import _native
-
-    return {k: round(float(sum(v)), 4) for k, v in _native.profile_kernels(fn, dev).items() if k.startswith(("k_wn_", "k_pm_scan"))}
+    return BL.kernel_ms(fn, dev, ("k_wn_", "k_pm_scan"))
 
 
 def rates(out, pairs):
@@ -114,8 +90,8 @@ def bench_points(a, torch, dev):
     diff = int((run()[1][0] - comp()).abs().max())
     assert diff <= f, diff
     out = {"bench": "winding", "shape": "points", "points": n, "faces": f, "reps": a.reps, "torch_pairs_per_step": a.pairs,
-           "max_quanta_kernel_minus_torch": diff, "wall_ms_median_min_max": median_ms(run, a.reps), "kernel_ms": kernels(run, dev),
-           "torch_wall_ms_median_min_max": median_ms(comp, a.reps), "device": torch.cuda.get_device_name(0)}
+           "max_quanta_kernel_minus_torch": diff, "wall_ms_median_min_max": BL.median_ms(run, a.reps), "kernel_ms": kernels(run, dev),
+           "torch_wall_ms_median_min_max": BL.median_ms(comp, a.reps), "device": torch.cuda.get_device_name(0)}
     return rates(out, n * f)
 
 
@@ -134,8 +110,8 @@ def bench_voxels(a, torch, dev):
     differ = int((got != want).sum())           # a node within a few quanta of the threshold may differ; none does here
     out = {"bench": "winding", "shape": "voxels", "meshes": M, "side": G, "faces_per_mesh": VOXEL_FACES, "reps": a.reps,
            "torch_pairs_per_step": a.pairs, "nodes_that_differ_from_torch": differ, "occupied": int(got.sum()),
-           "wall_ms_median_min_max": median_ms(run, a.reps), "kernel_ms": kernels(run, dev),
-           "torch_wall_ms_median_min_max": median_ms(comp, a.reps), "device": torch.cuda.get_device_name(0)}
+           "wall_ms_median_min_max": BL.median_ms(run, a.reps), "kernel_ms": kernels(run, dev),
+           "torch_wall_ms_median_min_max": BL.median_ms(comp, a.reps), "device": torch.cuda.get_device_name(0)}
     return rates(out, M * G ** 3 * VOXEL_FACES)
 
 
@@ -144,8 +120,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--pairs", type=int, default=1 << 24)
     ap.add_argument("--shapes", nargs="+", default=["points", "voxels"])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "winding_bench.jsonl"))
-    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(ROOT, "profiles", "winding_resource_usage.txt"))
+    ap.add_argument("--out", default=os.path.join(BL.ROOT, "profiles", "winding_bench.jsonl"))
+    ap.add_argument("--resource-usage", nargs="?", const=os.path.join(BL.ROOT, "profiles", "winding_resource_usage.txt"))
     a = ap.parse_args()
     if a.resource_usage:
         resource_usage(a.resource_usage)
@@ -154,11 +130,7 @@ def main():
 
     dev = torch.device("cuda")
     for shape in a.shapes:
-        line = json.dumps({"points": bench_points, "voxels": bench_voxels}[shape](a, torch, dev))
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "a") as fh:
-                fh.write(line + "\n")
+        BL.emit({"points": bench_points, "voxels": bench_voxels}[shape](a, torch, dev), a.out)
 
 
 if __name__ == "__main__":
