@@ -63,6 +63,8 @@ extern "C" {
 #define DPC_PM_CHUNK_TILES 8
 /* dpc_mesh_winding: the fractional bits of a face's quantised term, and so of the int64 sums (the unit is 2^-40). */
 #define DPC_WINDING_FRAC_BITS 40
+/* dpc_ray_mesh_intersect: the LDS of a workgroup, DPC_PM_FACE_TILE staged faces of nine doubles padded to five double2. */
+#define DPC_RAY_LDS_BYTES 10240
 /* dpc_knn_batched / dpc_pca_normals: the most neighbours per query, and the references a workgroup stages in LDS per
  * round.  A workgroup holds DPC_KNN_BLOCK(k) queries, one lane each: 256 for k <= 16, 128 for k <= 32, 64 above, so that
  * the lanes' sorted lists (k slots of a d2 and an int32 each) fit next to the tile. */
@@ -1132,6 +1134,67 @@ size_t dpc_mesh_winding_voxels_workspace_bytes(const int32_t* host_mesh_desc, in
 int dpc_mesh_winding_voxels(const void* verts, int n_verts, int is_f64, const int32_t* faces, int n_faces, const int32_t* mesh_desc,
                             const int32_t* host_mesh_desc, int meshes, int D, int H, int W, int64_t threshold_q, uint32_t* bits,
                             void* workspace, int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Ray-mesh intersection: what a ray hits first, and how many faces it crosses.  For every ray of a ragged batch of
+ * (ray bundle, mesh) rows: the smallest hit parameter t, the face hit there, the hit's weights on that face's vertices,
+ * the face's unit normal and the number of faces hit.  Occlusion tests between a viewpoint and surface samples, partial
+ * scans and a crossing-parity inside test are built on it (dpc/render/raycast.py).  There is no counterpart in the
+ * reference: the rules below are this library's own, tests/raycast_oracle.py restates them in numpy and in exact rational
+ * arithmetic.  All arithmetic is fp64 (fp32 rays and vertices widen exactly first) and NOTHING IS FUSED: every product,
+ * sum and quotient below is rounded on its own, so numpy's elementwise arithmetic reproduces every bit.
+ *
+ * Ray.  O + t D; D is NOT normalised, t is in units of |D|: t = 1 is the point O + D.
+ * One ray, one face with the vertices (V0, V1, V2) in the caller's order; dot(a, b) = (ax*bx + ay*by) + az*bz and
+ * a x b = (ay*bz - az*by, az*bx - ax*bz, ax*by - ay*bx) (Moeller-Trumbore), in this order:
+ *   E1 = V1 - V0;  E2 = V2 - V0;  Pv = D x E2;  det = E1 . Pv
+ *   no hit when !(fabs(det) > 0)                        (D parallel to the face, a zero-area face, D = 0, a NaN)
+ *   T = O - V0;  a = T . Pv;  Q = T x E1;  b = D . Q
+ *   s = det > 0 ? 1 : -1;  a' = s*a;  b' = s*b;  m = fabs(det)
+ *   inside iff a' >= 0 && b' >= 0 && a' + b' <= m       (inclusive; products only, no division)
+ *   with cull_backfaces a face with det < 0 is no hit
+ *   t = (E2 . Q) / det;  hit iff inside && t_min <= t && t <= t_max      (both ends inclusive)
+ *   u = a / det;  v = b / det;  weights = ((1 - u) - v, u, v) on (V0, V1, V2) in the caller's order
+ *   The three IEEE divisions run only for a face the ray is inside of.
+ *   This test is not watertight along shared edges and vertices: a ray through an edge may report both faces or, after
+ *   rounding, neither.
+ * One ray, the faces of its row:
+ *   hits     int32, NULL to skip: the number of faces hit (an integer: it does not depend on any order).
+ *   t, face  fp64, int32: the smallest t among the hits and its face's index within the row's face range, as the caller
+ *            numbered it; among faces whose t are bit-equal the lowest index wins.  A miss: t = +inf, face = -1.
+ *   weights  fp64 [.,3]: as above for the face reported; NaN for a miss.
+ *   normal   fp64 [.,3], NULL to skip: dpc_point_mesh_closest's normal of faces[face] (each operation rounded on its own,
+ *            zeros for a cross product without length); zeros for a miss.
+ * Arguments.  origins, directions [n_rays,3], fp64 when rays_f64 else fp32; verts, faces as dpc_point_mesh_distance takes
+ *   them; pair_desc / host_pair_desc [n_pairs,6]: (ray_start, ray_count, vert_start, vert_count, face_start, face_count),
+ *   the table of dpc_point_mesh_distance with rays for points.  The outputs hold the rows' rays in row order,
+ *   sum ray_count of them.  A row with rays and no faces is allowed: every ray misses.
+ * Guards.  A face with a vertex that is NaN, infinite or >= DPC_MESH_VOXEL_MAX_COORD in magnitude is skipped and sets
+ *   DPC_STATUS_NONFINITE; a face with an index outside its row's vertices is skipped and sets DPC_STATUS_BAD_INDEX: it
+ *   never becomes an address.  A ray with such an origin or direction component gets t = NaN, face = -1, hits = 0,
+ *   weights NaN, normal zero, and sets DPC_STATUS_NONFINITE.  A device-table row outside the packed arrays sets
+ *   DPC_STATUS_BAD_INDEX; nothing of it is read or written.
+ * Kernels (csrc/dpc_raycast.hip): dpc_point_mesh_closest's decomposition -- (row, DPC_PM_BLOCK rays, chunk of faces) per
+ *   workgroup, a lane owns a ray, DPC_PM_FACE_TILE faces staged per round as (V0, E1, E2), DPC_RAY_LDS_BYTES of LDS --
+ *   with every lane keeping (t, face, hits) while it walks the faces in ascending order under a strict <.  A work item
+ *   writes its lanes' triples to its own workspace slots [chunk][ray]; a per-ray epilogue reduces the chunks in ascending
+ *   order with a strict <, adds the counts, stages the winning face alone and recomputes u, v and the normal with the same
+ *   expressions.  The result is the same bit for bit however the faces are cut into tiles and chunks, however the rows
+ *   are ordered or batched, and whichever workgroup finishes first.
+ * workspace: dpc_ray_mesh_workspace_bytes(host_pair_desc, n_pairs) bytes, sized from the host table (three int32 prefixes
+ *   and 16 bytes per slot; a row has ray_count slots per chunk of its faces); 0 for n_pairs <= 0, a NULL table or a table
+ *   the call would refuse.
+ * Every check runs before any launch: DPC_ERR_SHAPE for a negative size, a table row outside the sizes given, more than
+ *   2^31 - 1 rays, work items or slots, a NaN t_min or t_max and t_min > t_max (t_max = +inf is allowed); valid arguments
+ *   with NULL device pointers (hits and normal apart) return DPC_ERR_NULL without touching a device; no rows or no rays
+ *   return DPC_OK with nothing launched.  No host synchronisation, no allocation, no atomics but the status word's.  Added
+ *   without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+size_t dpc_ray_mesh_workspace_bytes(const int32_t* host_pair_desc, int n_pairs);
+int dpc_ray_mesh_intersect(const void* origins, const void* directions, int n_rays, int rays_f64, const void* verts, int n_verts,
+                           int verts_f64, const int32_t* faces, int n_faces, const int32_t* pair_desc, const int32_t* host_pair_desc,
+                           int n_pairs, double t_min, double t_max, int cull_backfaces, double* t, int32_t* face, double* weights,
+                           int32_t* hits, double* normal, void* workspace, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Batched k-nearest-neighbour search, and surface normals from the neighbours' covariance (PCA): the building blocks of

@@ -71,21 +71,6 @@ __global__ __launch_bounds__(kPmBlock) void k_pc_arg(const void* __restrict__ pt
   pm_report(it.flags, status);
 }
 
-// The unit normal of (v0, v1, v2) in that winding, (v1 - v0) x (v2 - v0) over its length, each operation rounded on its
-// own as numpy's elementwise arithmetic rounds it (nothing fused: a contracted cross product of a sliver differs from the
-// plain one by far more than an ulp); zeros when the cross product has no length.
-__device__ inline void pc_normal(const double (&v)[3][3], double* n) {
-#pragma clang fp contract(off)
-  const double ax = v[1][0] - v[0][0], ay = v[1][1] - v[0][1], az = v[1][2] - v[0][2];
-  const double bx = v[2][0] - v[0][0], by = v[2][1] - v[0][1], bz = v[2][2] - v[0][2];
-  const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
-  const double len = sqrt((cx * cx + cy * cy) + cz * cz);
-  const bool area = len > 0.0;
-  n[0] = area ? cx / len : 0.0;
-  n[1] = area ? cy / len : 0.0;
-  n[2] = area ? cz / len : 0.0;
-}
-
 // Q on the staged face (A, B, C) and its weights on (A, B, C), from pm_d2's own terms: the foot point of the plane in the
 // inside region, else the point of the nearest of the three segments (the first of equals in the order AB, AC, BC; where
 // two tie, at a vertex, they name the same point).
@@ -169,7 +154,7 @@ __global__ __launch_bounds__(kPmOutBlock) void k_pc_finish(const void* __restric
 #pragma unroll
     for (int k = 0; k < 3; ++k)   // a weight of exactly 1: Q is that vertex itself, on whichever segment it was reached
       if (w[k] == 1.0) { q[0] = v[k][0]; q[1] = v[k][1]; q[2] = v[k][2]; }
-    pc_normal(v, n);
+    pm_normal(v, n);
   } else {
     best = std::numeric_limits<double>::infinity();
     arg = -1;

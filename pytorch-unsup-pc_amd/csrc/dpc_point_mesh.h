@@ -1,15 +1,17 @@
 // What the brute-force "every point of a row meets every face of its mesh" pipelines share -- dpc_point_mesh.hip (the
-// distance), dpc_closest.hip (the nearest face, the closest point, its weights and the face normal) and dpc_winding.hip
-// (the winding number of points and of grid nodes).  One decomposition: a work item is (row, block of points, chunk of
+// distance), dpc_closest.hip (the nearest face, the closest point, its weights and the face normal), dpc_winding.hip
+// (the winding number of points and of grid nodes) and dpc_raycast.hip (the first hit and the hit count of rays, whose
+// origins are "the points").  One decomposition: a work item is (row, block of points, chunk of
 // faces), a lane owns a point, the workgroup stages a tile of faces in LDS and every lane walks it.
 //   host     pm_check, pm_geometry (pm_chunk: the chunk-size rule), pm_slots and pm_plan (the checks of an entry point
-//            with workspace slots), PmWork / pm_carve (the prefix arrays of the workspace), pm_dispatch (the dtypes)
+//            with workspace slots; empty_ok: rows with points and no faces pass, for the rays, which then all miss), PmWork / pm_carve (the prefix arrays of the workspace), pm_dispatch (the dtypes)
 //   device   pm_row (the checked table row), k_pm_scan (the prefixes), pm_item (the prologue of a work item), pm_walk (the
 //            tile loop with its barriers), pm_fetch (a face's checked indices and widened vertices), pm_slot (the guarded
 //            slot index), pm_out (the prologue of an output point), pm_report (the status word)
 //   faces    pm_stage forms the distance's record of a face once, pm_d2 is the squared distance from a point to a staged
 //            face: the distance and the closest kernels inline the same two, so they compute the same d2 for the same
-//            (point, face).  The winding's record and term are in dpc_winding.hip.
+//            (point, face).  The winding's record and term are in dpc_winding.hip, the ray's in dpc_raycast.hip.
+//            pm_normal is the unit normal of a face in the caller's winding, which closest and raycast report.
 // The contract is in include/dpc_render.h (dpc_point_mesh_distance); the formulation is described at the head of
 // dpc_point_mesh.hip.
 #pragma once
@@ -354,24 +356,41 @@ __device__ inline double pm_d2(const double2* __restrict__ rec, double px, doubl
   return inside ? plane : edge;
 }
 
-// the host check of a pair table: DPC_ERR_SHAPE, or DPC_OK with the number of output points in *total
-inline int pm_check(int pairs, const int32_t* desc, int64_t n_pts, int64_t n_verts, int64_t n_faces, int64_t* total) {
+// The unit normal of (v0, v1, v2) in that winding, (v1 - v0) x (v2 - v0) over its length, each operation rounded on its
+// own as numpy's elementwise arithmetic rounds it (nothing fused: a contracted cross product of a sliver differs from the
+// plain one by far more than an ulp); zeros when the cross product has no length.
+__device__ inline void pm_normal(const double (&v)[3][3], double* n) {
+#pragma clang fp contract(off)
+  const double ax = v[1][0] - v[0][0], ay = v[1][1] - v[0][1], az = v[1][2] - v[0][2];
+  const double bx = v[2][0] - v[0][0], by = v[2][1] - v[0][1], bz = v[2][2] - v[0][2];
+  const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+  const double len = sqrt((cx * cx + cy * cy) + cz * cz);
+  const bool area = len > 0.0;
+  n[0] = area ? cx / len : 0.0;
+  n[1] = area ? cy / len : 0.0;
+  n[2] = area ? cz / len : 0.0;
+}
+
+// the host check of a pair table: DPC_ERR_SHAPE, or DPC_OK with the number of output points in *total.  empty_ok: a row
+// with points and no faces is accepted (an entry point whose answer over an empty set of faces is defined)
+inline int pm_check(int pairs, const int32_t* desc, int64_t n_pts, int64_t n_verts, int64_t n_faces, int64_t* total,
+                    bool empty_ok = false) {
   const int64_t len[3] = {n_pts, n_verts, n_faces};
-  return check_desc<6, 3>(desc, pairs, len, INT32_MAX, total, [](const int32_t* d) {
-    return !(d[5] == 0 && d[1] > 0);   // the minimum over an empty set of faces
+  return check_desc<6, 3>(desc, pairs, len, INT32_MAX, total, [empty_ok](const int32_t* d) {
+    return empty_ok || !(d[5] == 0 && d[1] > 0);   // the minimum over an empty set of faces
   });
 }
 
 // The checks of a pair entry point with workspace slots, and of its workspace size: DPC_OK with the geometry, the slot
 // count and the number of output points, or the code to return.  max_faces: the most faces a row may have.
 inline int pm_plan(int n_points, int n_verts, int n_faces, const int32_t* host_pair_desc, int n_pairs, int max_faces, PmGeom* g,
-                   int64_t* slots, int64_t* total) {
+                   int64_t* slots, int64_t* total, bool empty_ok = false) {
   if (n_points < 0 || n_verts < 0 || n_faces < 0 || n_pairs < 0) return DPC_ERR_SHAPE;
   *g = PmGeom{0, 0, 0, kPmTile * DPC_PM_CHUNK_TILES};
   *slots = *total = 0;
   if (n_pairs == 0) return DPC_OK;
   if (!host_pair_desc) return DPC_ERR_NULL;
-  const int rc = pm_check(n_pairs, host_pair_desc, n_points, n_verts, n_faces, total);
+  const int rc = pm_check(n_pairs, host_pair_desc, n_points, n_verts, n_faces, total, empty_ok);
   if (rc != DPC_OK) return rc;
   for (int p = 0; p < n_pairs; ++p)
     if (host_pair_desc[6 * p + 5] > max_faces) return DPC_ERR_SHAPE;

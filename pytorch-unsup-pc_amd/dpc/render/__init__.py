@@ -39,6 +39,7 @@ from .pointmesh import fscore, fscore_of_split, point_mesh_distance  # noqa: F40
 from .normals import estimate_normals, knn_batched, normal_consistency, normal_consistency_of_split  # noqa: F401
 from .closest import closest_points_on_meshes, face_normals_at, point_surface_loss  # noqa: F401
 from .winding import points_inside_meshes, signed_point_mesh_distance, winding_numbers, winding_voxels  # noqa: F401
+from .raycast import ray_mesh_intersect, rays_hit_points, visible_points  # noqa: F401
 from .surface import augment_mesh, extract_surface, extract_surfaces, save_obj  # noqa: F401
 from .visualise import (camera_frame, read_png_any, render_point_cloud, render_point_clouds, render_split, write_png,  # noqa: F401
                         write_png_gray16, write_png_rgba)
@@ -65,6 +66,7 @@ __all__ = [
     "knn_batched", "estimate_normals", "normal_consistency", "normal_consistency_of_split",
     "closest_points_on_meshes", "point_surface_loss", "face_normals_at",
     "winding_numbers", "points_inside_meshes", "signed_point_mesh_distance", "winding_voxels",
+    "ray_mesh_intersect", "rays_hit_points", "visible_points",
     "extract_surfaces", "extract_surface", "augment_mesh", "save_obj",
     "load_obj_mesh", "densify_meshes", "densify_split", "MeshError",
     "camera_frame", "render_point_clouds", "render_point_cloud", "render_split", "write_png",

@@ -36,6 +36,7 @@ DPC_VOXEL_MAX_SIDE = 128
 DPC_MESH_FILL_NONE, DPC_MESH_FILL_CARVE, DPC_MESH_FILL_PARITY = 0, 1, 2
 DPC_PM_BLOCK, DPC_PM_FACE_TILE, DPC_PM_CHUNK_TILES = 256, 128, 8
 DPC_WINDING_FRAC_BITS = 40
+DPC_RAY_LDS_BYTES = 10240
 DPC_KNN_MAX_K, DPC_KNN_TILE = 64, 512
 DPC_GAUSS_NORM_NONE, DPC_GAUSS_NORM_ANALYTICAL, DPC_GAUSS_NORM_PER_POINT = 0, 1, 2
 DPC_GAUSS_MAX_SIDE = 64
@@ -138,6 +139,8 @@ _FUNCTIONS = (
     ("dpc_mesh_winding", _i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i] + [_vp] * 5),
     ("dpc_mesh_winding_voxels_workspace_bytes", _sz, [_vp, _i, _i, _i, _i]),
     ("dpc_mesh_winding_voxels", _i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i64] + [_vp] * 4),
+    ("dpc_ray_mesh_workspace_bytes", _sz, [_vp, _i]),
+    ("dpc_ray_mesh_intersect", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _d, _d, _i] + [_vp] * 8),
     ("dpc_knn_batched", _i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     ("dpc_pca_normals", _i, [_vp, _i, _i, _vp, _vp, _i, _i] + [_vp] * 6),
     ("dpc_downsample_workspace_bytes", _sz, [_i, _i]),

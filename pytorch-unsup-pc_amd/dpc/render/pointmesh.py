@@ -38,15 +38,17 @@ def _index_map(of, n_src, n_tgt, fn, name, src, tgt):
 
 
 class _Plan:
-    """A checked dpc_point_mesh_distance call: the clouds, the meshes it uses, and the host table."""
+    """A checked dpc_point_mesh_distance call: the clouds, the meshes it uses, and the host table.  empty_ok: a mesh
+    without faces may serve a cloud with points (an entry point that defines its answer over no faces, which then makes
+    its own dry run: dpc_point_mesh_distance refuses such a table)."""
 
-    def __init__(self, clouds, meshes, mesh_of, fn, cloud_name="clouds", map_name="mesh_of"):
+    def __init__(self, clouds, meshes, mesh_of, fn, cloud_name="clouds", map_name="mesh_of", empty_ok=False):
         self.fn, self.cloud_name = fn, cloud_name
         self.clouds = [_batch.cloud(c, "%s: %s[%d]" % (fn, cloud_name, i)) for i, c in enumerate(clouds)]
         items = [_mesh(m, i, fn) for i, m in enumerate(meshes)]
         self.mesh_of = _index_map(mesh_of, len(self.clouds), len(items), fn, map_name, cloud_name, "meshes")
         for i, k in enumerate(self.mesh_of):
-            if len(items[k][1]) == 0 and len(self.clouds[i]) > 0:
+            if len(items[k][1]) == 0 and len(self.clouds[i]) > 0 and not empty_ok:
                 raise MeshError("%s: mesh %d has no faces but %s[%d] has points (the minimum over an empty set)"
                                 % (fn, k, cloud_name, i))
         used = sorted(set(self.mesh_of))
@@ -61,6 +63,8 @@ class _Plan:
         self.desc = _batch.table(np.asarray(rows, dtype=np.int64) if rows else np.zeros((0, 6)), 6,
                                  "%s: table entries must fit int32" % fn)
         self.sizes = (int(ps[-1]), int(vs[-1]), int(fs[-1]))
+        if empty_ok:
+            return
         rc = _native.lib().dpc_point_mesh_distance(None, self.sizes[0], 0, None, self.sizes[1], 0, None, self.sizes[2], None,
                                                    self.desc.ctypes.data, len(rows), None, None, None, None)
         _batch.dry_run(rc, "%s: dpc_point_mesh_distance refused the table (too many points or work items in one call)" % fn)
@@ -68,13 +72,16 @@ class _Plan:
     def tensors(self):
         return self.clouds, [V for V, _ in self.items]
 
-    def packed(self, dev):
+    def packed(self, dev, pts=None):
         """The leading arguments both point-to-mesh entry points take, points to n_pairs, on dev (the tuple keeps the
-        packed tensors alive), after the one finiteness check of the points.  Needs at least one point."""
+        packed tensors alive), after the one finiteness check of the points.  Needs at least one point.  pts: the packed
+        points [sum n_i, 3] on dev when the caller has packed them itself; they are then not checked for finiteness."""
         n_pts, n_verts, n_faces = self.sizes
-        pdt, vdt = _batch.widest(self.clouds), _batch.widest(V for V, _ in self.items)
-        pts, _ = _batch.pack(self.clouds, dev, pdt)
-        if not bool(torch.isfinite(pts).all()):
+        pdt, vdt = _batch.widest(self.clouds) if pts is None else pts.dtype, _batch.widest(V for V, _ in self.items)
+        check = pts is None
+        if pts is None:
+            pts, _ = _batch.pack(self.clouds, dev, pdt)
+        if check and not bool(torch.isfinite(pts).all()):
             for i, c in enumerate(self.clouds):
                 if not bool(torch.isfinite(c).all()):
                     raise ValueError("%s: %s[%d] holds a NaN or inf coordinate" % (self.fn, self.cloud_name, i))
