@@ -50,6 +50,10 @@ extern "C" {
 /* Longest side of a grid of the dpc_voxel* entry points: a 128^3 bit grid is 256 KiB, four LDS slabs of dpc_voxelise,
  * and a flat voxel index stays far inside an int. */
 #define DPC_VOXEL_MAX_SIDE 128
+/* dpc_voxel_edt: the value of every voxel of a grid without a seed (INT32_MAX; the largest real value is 3 * 127^2), and
+ * the most thresholds of one dpc_voxel_edt_stats call. */
+#define DPC_VOXEL_EDT_NONE 2147483647
+#define DPC_VOXEL_EDT_MAX_THRESHOLDS 8
 /* The fills of dpc_voxelise_meshes, and the size from which a vertex coordinate counts as not finite there (below it no
  * product of the separating-axis tests can overflow). */
 #define DPC_MESH_FILL_NONE 0
@@ -911,6 +915,48 @@ int dpc_voxelise_meshes(const void* verts, int n_verts, int is_f64, const int32_
                         const int32_t* host_mesh_desc, int meshes, int D, int H, int W, int fill, uint32_t* bits, uint32_t* scratch,
                         int32_t* info, int32_t* status, void* stream);
 int dpc_voxel_carve(const uint32_t* bits, int B, int D, int H, int W, uint32_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Distance transforms of bit grids: the exact squared Euclidean distance of every voxel to the nearest seed, the surface
+ * shell of a grid, and the counts and sums a voxel F-score and a mean surface distance are made of.  There is no
+ * counterpart in the reference.  Everything is an integer in index units (voxel spacing 1 on every axis, whatever the
+ * grid's sides): there is one right answer and no tolerance.  tests/voxel_edt_oracle.py restates the rules in numpy.
+ *
+ * Bit grids: those of the voxel-grid evaluation above: [D,H,W], words = ceil(D*H*W / 32) uint32, voxel
+ *   f = (d*H + h)*W + w is bit f & 31 of word f >> 5.  Readers ignore the padding bits of the last word, writers leave
+ *   them zero.
+ * dpc_voxel_edt.  Seeds are the set voxels, or the clear voxels when of_clear is non-zero; padding bits are never seeds, in
+ *   either mode.  sq [B,D,H,W] int32: sq[b,d,h,w] = min over the seeds (d',h',w') of grid b of
+ *   (d-d')^2 + (h-h')^2 + (w-w')^2, so 0 at a seed; every voxel of a grid without a seed is DPC_VOXEL_EDT_NONE.  Three
+ *   separable min-plus passes (csrc/dpc_voxel_edt.hip): along W from the bits, along H, then along D in place on sq, which
+ *   is the only buffer between the passes: no workspace and no allocation.
+ * dpc_voxel_shell.  out [B, words]: the set voxels with at least one of their six face neighbours clear or outside the
+ *   grid.  The padding bits of out are written as zero.  out == bits is refused.
+ * dpc_voxel_edt_stats.  sq [n_fields, D,H,W] fields, bits [n_grids, words] grids; pair_desc / host_pair_desc [P,2] int32
+ *   rows of (field index, bit-grid index), DEVICE / HOST, the same values, as dpc_voxel_stats takes them (rows may share a
+ *   field or a grid); host_thresholds_sq [K] int32 on the HOST, 0 <= K <= DPC_VOXEL_EDT_MAX_THRESHOLDS,
+ *   0 <= t_k < DPC_VOXEL_EDT_NONE; out [P, 3 + K] int64 per pair:
+ *     n         the set voxels of the bit grid,
+ *     reached   those of them whose field value is not DPC_VOXEL_EDT_NONE,
+ *     sum_sq    the sum of the field over the reached voxels,
+ *     then, per threshold, the count of reached voxels with sq <= t_k.
+ *   A device-table row that fails its check against n_fields / n_grids is not read further, sets DPC_STATUS_BAD_INDEX and
+ *   leaves its output row untouched.  status: DEVICE int32, zeroed by the caller, NULL allowed.
+ *
+ * Limits: 1 <= D, H, W <= DPC_VOXEL_MAX_SIDE.  dpc_voxel_edt runs one of three size classes per pass: the plane pass by
+ * max(H, W) and the depth pass by D, each <= 32, <= 64 or above.
+ * Every check runs before any launch (DPC_ERR_SHAPE: a negative size, a side outside the limits, K out of range, a
+ * threshold out of range, a host table row outside its array; dpc_voxel_shell: out == bits); valid arguments with NULL
+ * device pointers (or a NULL host table that has rows) return DPC_ERR_NULL without touching a device; zero items return
+ * DPC_OK with nothing launched.  No host synchronisation, no allocation, no floating point anywhere and no global atomics
+ * but the OR into the status word: a pair's counts and sums leave its workgroup by the stores of one thread.  Added
+ * without a new ABI number: no existing entry point changed.
+ * ------------------------------------------------------------------------------------------------- */
+int dpc_voxel_edt(const uint32_t* bits, int B, int D, int H, int W, int of_clear, int32_t* sq, void* stream);
+int dpc_voxel_shell(const uint32_t* bits, int B, int D, int H, int W, uint32_t* out, void* stream);
+int dpc_voxel_edt_stats(const int32_t* sq, int n_fields, const uint32_t* bits, int n_grids, int D, int H, int W,
+                        const int32_t* pair_desc, const int32_t* host_pair_desc, int pairs, const int32_t* host_thresholds_sq, int K,
+                        int64_t* out, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Iso-surface extraction (dpc/util/voxel.py: extract_surface): occupancy grids to triangle meshes, for a ragged batch of

@@ -35,6 +35,8 @@ from .voxels import (evaluate_voxel_prediction, iou_of_split, render_voxels, vox
                      voxelise, voxels2pc_batched)
 from .densify import MeshError, densify_meshes, densify_split, load_obj_mesh  # noqa: F401
 from .meshvoxels import carve_voxels, solid_iou_of_split, voxelise_meshes  # noqa: F401
+from .voxeldist import (voxel_distance_transform, voxel_fscore, voxel_fscore_of_split, voxel_shell, voxel_signed_distance,  # noqa: F401
+                        voxel_surface_stats)
 from .pointmesh import fscore, fscore_of_split, point_mesh_distance  # noqa: F401
 from .normals import estimate_normals, knn_batched, normal_consistency, normal_consistency_of_split  # noqa: F401
 from .closest import closest_points_on_meshes, face_normals_at, point_surface_loss  # noqa: F401
@@ -62,6 +64,7 @@ __all__ = [
     "emd_loss", "emd_match", "emd_of_split", "farthest_point_sample",
     "voxelise", "voxel_stats", "voxel_iou", "evaluate_voxel_prediction", "voxel2pc", "voxels2pc_batched", "iou_of_split",
     "render_voxels", "voxelise_meshes", "carve_voxels", "solid_iou_of_split",
+    "voxel_distance_transform", "voxel_signed_distance", "voxel_shell", "voxel_surface_stats", "voxel_fscore", "voxel_fscore_of_split",
     "point_mesh_distance", "fscore", "fscore_of_split",
     "knn_batched", "estimate_normals", "normal_consistency", "normal_consistency_of_split",
     "closest_points_on_meshes", "point_surface_loss", "face_normals_at",

@@ -33,6 +33,8 @@ DPC_STATUS_EMD_NOT_CONVERGED = 64
 DPC_EMD_MAX_POINTS = 2048
 DPC_FPS_MAX_POINTS = 16384
 DPC_VOXEL_MAX_SIDE = 128
+DPC_VOXEL_EDT_NONE = 2 ** 31 - 1
+DPC_VOXEL_EDT_MAX_THRESHOLDS = 8
 DPC_MESH_FILL_NONE, DPC_MESH_FILL_CARVE, DPC_MESH_FILL_PARITY = 0, 1, 2
 DPC_PM_BLOCK, DPC_PM_FACE_TILE, DPC_PM_CHUNK_TILES = 256, 128, 8
 DPC_WINDING_FRAC_BITS = 40
@@ -128,6 +130,9 @@ _FUNCTIONS = (
     ("dpc_voxel2pc", _i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     ("dpc_voxelise_meshes", _i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     ("dpc_voxel_carve", _i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    ("dpc_voxel_edt", _i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    ("dpc_voxel_shell", _i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    ("dpc_voxel_edt_stats", _i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     ("dpc_surface_workspace_bytes", _sz, [_vp, _i, _i]),
     ("dpc_surface_count", _i, [_vp, _i, _i, _vp, _vp, _i] + [_vp] * 5),
     ("dpc_surface_extract", _i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i] + [_vp] * 5),
