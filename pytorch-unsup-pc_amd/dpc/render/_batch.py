@@ -5,6 +5,9 @@ Each packs its items (clouds, pairs of clouds, meshes) into one buffer in the wi
 host int32 table that also goes to the device, asks the library's own argument checks before anything touches a device (a
 dry run with NULL device pointers), allocates the workspace the library asks for, and turns the status bits of a job into
 exceptions.
+
+What a whole split needs on top of one such call lives next door in _split.py: the checks and the walk over groups of
+models that the *_of_split functions share, and the walk over a split by model name.
 """
 import numpy as np
 import torch

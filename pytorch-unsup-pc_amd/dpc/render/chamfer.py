@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import _batch, _native
+from . import _batch, _native, _split
 from .predictions import load_predictions
 
 _WHAT = "dpc.render Chamfer evaluation"
@@ -260,42 +260,6 @@ def chamfer_loss(preds, gts, gt_of=None, squared=False):
     return torch.cat(rows)[torch.from_numpy(inverse).to(dev)]
 
 
-def _host_unit_quaternion(q):
-    """The reference's q / |q| (util/quaternion.py quaternion_rotate), evaluated in CPU torch where its evaluation ran:
-    a device norm of four numbers is not guaranteed to round the same way."""
-    qt = q.detach().cpu() if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
-    if qt.dim() != 2 or qt.shape != (1, 4):
-        raise ValueError("reference_rotation must be a [1,4] quaternion, got %s" % (tuple(qt.shape),))
-    return torch.div(qt, qt.norm(p=2, dim=-1).reshape(qt.shape[0], 1))
-
-
-def _rotate(points, qn, dev):
-    """quaternion_rotate(points [V,N,3], q) with q already normalised: q * p * conj(q), the reference's products in its
-    order, in the promoted dtype (float64 for a float64 quaternion; no cast back, as eval_chamfer_to.py:116-120)."""
-    from . import quaternion_conjugate, quaternion_multiply
-
-    pc = points.to(dev).reshape(1, -1, 3)
-    q = qn.to(dev).reshape(1, 1, 4)
-    wxyz = quaternion_multiply(quaternion_multiply(q, pc), quaternion_conjugate(q))
-    return wxyz[:, :, 1:4].reshape(points.shape[0], points.shape[1], 3)
-
-
-def _prediction(entry, m):
-    if not isinstance(entry, (tuple, list)) or len(entry) not in (2, 3):
-        raise ValueError("predictions[%d] must be (points, num_points) or load_predictions' (points, camera_pose, num_points)" % m)
-    pts, nums = entry[0], entry[-1]
-    pts = pts if isinstance(pts, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pts))
-    if pts.dim() != 3 or pts.shape[2] != 3:
-        raise ValueError("predictions[%d] points must be [V,N,3], got %s" % (m, tuple(pts.shape)))
-    if nums is not None:
-        nums = np.asarray(nums.detach().cpu() if isinstance(nums, torch.Tensor) else nums).reshape(-1)
-        if (len(nums) != pts.shape[0] or not np.issubdtype(nums.dtype, np.integer) or (nums < 0).any()
-                or (nums > pts.shape[1]).any()):
-            raise ValueError("predictions[%d] num_points must be %d integers in [0, %d], got %r"
-                             % (m, pts.shape[0], pts.shape[1], nums))
-    return pts, nums
-
-
 def chamfer_of_split(predictions, gt_clouds, reference_rotation=None, models_per_call=256):
     """The reference's chamfer_dists (eval_chamfer_to.py:95-136) for M models: [M,V,2] float64 numpy, bit for bit.
 
@@ -304,38 +268,14 @@ def chamfer_of_split(predictions, gt_clouds, reference_rotation=None, models_per
     reference_rotation: a [1,4] quaternion (float64 as loadmat gives it) applied to every view first, the result kept in the
     promoted dtype (:116-120).  Models go through in groups of models_per_call (bounding device memory); the result does
     not depend on the grouping.  Every argument is checked before anything is launched."""
-    if len(predictions) != len(gt_clouds):
-        raise ValueError("chamfer_of_split: %d predictions and %d GT clouds" % (len(predictions), len(gt_clouds)))
-    if int(models_per_call) < 1:
-        raise ValueError("chamfer_of_split: models_per_call must be >= 1")
-    preds = [_prediction(e, m) for m, e in enumerate(predictions)]
-    gts = [_batch.cloud(g, "gt_clouds[%d]" % m) for m, g in enumerate(gt_clouds)]
-    views = {p.shape[0] for p, _ in preds}
-    if len(views) > 1:
-        raise ValueError("chamfer_of_split: every model needs the same number of views, got %s" % sorted(views))
-    V = views.pop() if views else 0
-    for m, ((p, nums), g) in enumerate(zip(preds, gts)):
-        if len(g) == 0 and (p.shape[1] if nums is None else nums.max(initial=0)) > 0:
-            raise ValueError("chamfer_of_split: GT cloud %d is empty" % m)
-    qn = None if reference_rotation is None else _host_unit_quaternion(reference_rotation)
-    M = len(preds)
-    out = np.zeros((M, V, 2), dtype=np.float64)
-    if M == 0 or V == 0:
+    split = _split.Split("chamfer_of_split", predictions, gt_clouds, reference_rotation, models_per_call, refuse_empty_gt=True)
+    out = np.zeros((split.M, split.V, 2), dtype=np.float64)
+    if split.empty:
         return out
-    dev = _batch.device(_WHAT, [p for p, _ in preds], gts)
-    step = int(models_per_call)
-    for a in range(0, M, step):
-        group = range(a, min(M, a + step))
-        views_list, gt_of = [], []
-        for j, m in enumerate(group):
-            pts, nums = preds[m]
-            if qn is not None:
-                pts = _rotate(pts, qn, dev)
-            for i in range(V):
-                views_list.append(pts[i] if nums is None else pts[i, :int(nums[i])])
-                gt_of.append(j)
-        res = chamfer_batched(views_list, [gts[m] for m in group], gt_of)
-        out[a:a + len(group)] = res.cpu().numpy().reshape(len(group), V, 2)
+    dev = _batch.device(_WHAT, *split.tensors())
+    for group in split.groups:
+        views_list, gt_of = split.views(group, dev)
+        split.store(out, group, chamfer_batched(views_list, [split.gts[m] for m in group], gt_of))
     return out
 
 
@@ -348,32 +288,24 @@ def eval_chamfer(save_dir, model_names, load_gt, num_views=None, reference_rotat
     Returns {"chamfer": [M',V,2], "model_names": the M' evaluated models, "final": np.mean(chamfer, axis=(0, 1)) * 100}.
     With out_name, writes "chamfer_<out_name>.txt" ("{} {}\\n" of final) into out_dir (default: save_dir's parent, the
     reference's experiment directory).  Models are read and evaluated models_per_call at a time."""
-    names, chamfer = [], []
-    pending, pending_gt, pending_names = [], [], []
-
-    def flush():
-        if pending:
-            chamfer.append(chamfer_of_split(pending, pending_gt, reference_rotation, models_per_call))
-            names.extend(pending_names)
-            del pending[:], pending_gt[:], pending_names[:]
-
-    for name in model_names:
+    def load(name, i):
         path = os.path.join(save_dir, "%s_pc.pkl" % name)
         if not os.path.isfile(path):
-            continue
+            return None
         gt = load_gt(name)
         if gt is None:
-            continue
+            return None
         points, _, nums = load_predictions(path)
         if num_views is not None:
             points = points[:num_views]
             nums = None if nums is None else nums[:num_views]
-        pending.append((points, nums))
-        pending_gt.append(gt)
-        pending_names.append(name)
-        if len(pending) >= models_per_call:
-            flush()
-    flush()
+        return (points, nums), gt
+
+    names, chamfer = [], []
+    for batch in _split.batches(model_names, load, models_per_call):
+        chamfer.append(chamfer_of_split([pred for _, (pred, _) in batch], [gt for _, (_, gt) in batch], reference_rotation,
+                                        models_per_call))
+        names.extend(name for name, _ in batch)
     V = num_views if num_views is not None else (chamfer[0].shape[1] if chamfer else 0)
     dists = np.concatenate(chamfer) if chamfer else np.zeros((0, V, 2), dtype=np.float64)
     final = np.mean(dists, axis=(0, 1)) * 100

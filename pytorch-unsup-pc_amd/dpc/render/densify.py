@@ -17,7 +17,7 @@ import numbers
 import numpy as np
 import torch
 
-from . import _batch, _native
+from . import _batch, _native, _split
 
 ROUNDS_PER_SYNC = 8  # rounds enqueued between two reads of the "models left" counter
 
@@ -200,20 +200,6 @@ def _densify_group(items, n, rounds_per_sync=ROUNDS_PER_SYNC):
     return res
 
 
-def _densify_or_isolate(items, names, n, errors, rounds_per_sync=ROUNDS_PER_SYNC):
-    """_densify_group; when a batch raises MeshError (a status bit is batch-wide), each of its models alone, so the error
-    names the model, or, with an `errors` dict, is recorded there and that model's result is None."""
-    try:
-        return _densify_group(items, n, rounds_per_sync)
-    except MeshError as exc:
-        if len(items) == 1:
-            if errors is None:
-                raise MeshError("model %r: %s" % (names[0], exc)) from exc
-            errors[names[0]] = str(exc)
-            return [None]
-    return [r for it, name in zip(items, names) for r in _densify_or_isolate([it], [name], n, errors, rounds_per_sync)]
-
-
 WORKSPACE_LIMIT = 32 << 30  # bytes of dpc_densify workspace per job (a single model may need more)
 
 
@@ -229,7 +215,8 @@ def densify_meshes(meshes, num_points=100000, rounds_per_sync=ROUNDS_PER_SYNC, w
     items = [_mesh(m, i) for i, m in enumerate(meshes)]
     res = []
     for a, b in _groups(items, n, len(items), workspace_limit):
-        res += _densify_or_isolate(items[a:b], ["mesh %d" % k for k in range(a, b)], n, None, rounds_per_sync)
+        res += _split.isolate(lambda group: _densify_group(group, n, rounds_per_sync), items[a:b],
+                              ["mesh %d" % k for k in range(a, b)], None)
     return res
 
 
@@ -244,36 +231,21 @@ def densify_split(model_names, load_mesh, num_points=100000, save=None, models_p
     loading or densification fails raises an error that names it; with an `errors` dict it is recorded there
     (errors[name] = message) and skipped instead, and the other models go on."""
     n = _budget(num_points)
-    step = int(models_per_call)
-    if step < 1:
-        raise ValueError("densify_split: models_per_call must be >= 1")
-    result, names, items = {}, [], []
+    step = _split.checked_step("densify_split", models_per_call)
+    result = {}
 
-    def flush():
+    def load(name, i):
+        mesh = load_mesh(name)
+        return None if mesh is None else _mesh(mesh, i)
+
+    for batch in _split.batches(model_names, load, step, errors, (ValueError, IndexError, OSError)):
+        names, items = [name for name, _ in batch], [item for _, item in batch]
         for a, b in _groups(items, n, step, workspace_limit):
-            for name, pts in zip(names[a:b], _densify_or_isolate(items[a:b], names[a:b], n, errors)):
+            for name, pts in zip(names[a:b], _split.isolate(lambda group: _densify_group(group, n), items[a:b], names[a:b], errors)):
                 if pts is None:
                     continue
                 if keep:
                     result[name] = pts
                 if save is not None:
                     save(name, pts)
-        del names[:], items[:]
-
-    for name in model_names:
-        try:
-            mesh = load_mesh(name)
-            if mesh is None:
-                continue
-            item = _mesh(mesh, len(items))
-        except (ValueError, IndexError, OSError) as exc:
-            if errors is None:
-                raise type(exc)("model %r: %s" % (name, exc)) from exc
-            errors[name] = str(exc)
-            continue
-        items.append(item)
-        names.append(name)
-        if len(names) >= step:
-            flush()
-    flush()
     return result

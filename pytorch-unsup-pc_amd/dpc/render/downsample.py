@@ -16,7 +16,7 @@ import numbers
 import numpy as np
 import torch
 
-from . import _batch, _native
+from . import _batch, _native, _split
 
 
 def _voxel_size(voxel_size):
@@ -98,27 +98,18 @@ def downsample_split(model_names, load_dense, voxel_size=0.01, save=None, clouds
     step = int(clouds_per_call)
     if step < 1:
         raise ValueError("downsample_split: clouds_per_call must be >= 1")
-    result, names, clouds = {}, [], []
+    result = {}
 
-    def flush():
-        if not names:
-            return
-        voxels, counts, offsets = _downsample_packed(clouds, vs)
+    def load(name, i):
+        dense = load_dense(name)
+        return None if dense is None else _cloud(dense, i)
+
+    for batch in _split.batches(model_names, load, step):
+        voxels, counts, offsets = _downsample_packed([cloud for _, cloud in batch], vs)
         host = voxels.cpu().numpy()
-        for name, o, n in zip(names, offsets, counts):
+        for (name, _), o, n in zip(batch, offsets, counts):
             pts = host[int(o):int(o) + int(n)]
             result[name] = pts
             if save is not None:
                 save(name, pts)
-        del names[:], clouds[:]
-
-    for name in model_names:
-        dense = load_dense(name)
-        if dense is None:
-            continue
-        clouds.append(_cloud(dense, len(clouds)))
-        names.append(name)
-        if len(names) >= step:
-            flush()
-    flush()
     return result

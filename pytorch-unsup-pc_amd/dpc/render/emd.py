@@ -17,10 +17,9 @@ The schedule, the tie rules and the summation order are in include/dpc_render.h 
 import numpy as np
 import torch
 
-from . import _batch, _native
+from . import _batch, _native, _split
 from . import sampling as _sampling
 from ._ops import status_word
-from .chamfer import _host_unit_quaternion, _prediction, _rotate
 
 _WHAT = "dpc.render EMD"
 MAX_POINTS = _native.DPC_EMD_MAX_POINTS
@@ -233,21 +232,11 @@ def emd_of_split(predictions, gt_clouds, reference_rotation=None, num_points=102
     deterministic and covers the cloud evenly; seed is ignored.  A cloud with more than DPC_FPS_MAX_POINTS points raises
     ValueError naming the model, a cloud with a NaN or infinite coordinate RuntimeError naming it.  Any other value of
     sampling raises ValueError."""
-    if len(predictions) != len(gt_clouds):
-        raise ValueError("emd_of_split: %d predictions and %d GT clouds" % (len(predictions), len(gt_clouds)))
-    if int(models_per_call) < 1:
-        raise ValueError("emd_of_split: models_per_call must be >= 1")
+    split = _split.Split("emd_of_split", predictions, gt_clouds, reference_rotation, models_per_call)
     num_points = int(num_points)
     if not 1 <= num_points <= MAX_POINTS:
         raise ValueError("emd_of_split: num_points must be in [1, DPC_EMD_MAX_POINTS = %d], got %d" % (MAX_POINTS, num_points))
-    preds = [_prediction(e, m) for m, e in enumerate(predictions)]
-    gts = [_batch.cloud(g, "gt_clouds[%d]" % m) for m, g in enumerate(gt_clouds)]
-    views = {p.shape[0] for p, _ in preds}
-    if len(views) > 1:
-        raise ValueError("emd_of_split: every model needs the same number of views, got %s" % sorted(views))
-    V = views.pop() if views else 0
-    counts = [(len(g), [int(p.shape[1]) if nums is None else int(nums[i]) for i in range(V)])
-              for (p, nums), g in zip(preds, gts)]
+    counts = [(len(g), n) for g, n in zip(split.gts, split.counts)]
     if sampling not in ("random", "fps"):
         raise ValueError("emd_of_split: sampling must be \"random\" or \"fps\", got %r" % (sampling,))
     fps = sampling == "fps"
@@ -255,28 +244,25 @@ def emd_of_split(predictions, gt_clouds, reference_rotation=None, num_points=102
         _fps_counts(counts, num_points)
     else:
         picks = subsample_indices(counts, num_points, seed)
-    qn = None if reference_rotation is None else _host_unit_quaternion(reference_rotation)
-    M = len(preds)
-    out = np.zeros((M, V), dtype=np.float64)
-    if M == 0 or V == 0:
+    V = split.V
+    out = np.zeros((split.M, V), dtype=np.float64)
+    if split.empty:
         return out
-    dev = _batch.device(_WHAT, [p for p, _ in preds], gts)
+    dev = _batch.device(_WHAT, *split.tensors())
     status = torch.zeros(1, dtype=torch.int32, device=dev)  # its own word: the failure is raised here, with names
-    step = int(models_per_call)
-    for a in range(0, M, step):
-        group = range(a, min(M, a + step))
+    for group in split.groups:
+        a = group[0]
         view_list, gt_list = [], []
         for m in group:
-            pts = preds[m][0]
-            pts = _rotate(pts, qn, dev) if qn is not None else pts.to(dev)
+            views = split.model(m, dev, on_device=True)
+            g = split.gts[m].to(dev)
             if fps:
-                g = gts[m].to(dev)
-                view_list.extend(pts[i][:counts[m][1][i]] for i in range(V))
+                view_list.extend(views)
                 gt_list.append(g)
                 continue
-            g = gts[m].to(dev)[torch.from_numpy(picks[m][0]).to(dev)]
-            for i in range(V):
-                view_list.append(pts[i][torch.from_numpy(picks[m][1][i]).to(dev)])
+            g = g[torch.from_numpy(picks[m][0]).to(dev)]
+            for v, idx in zip(views, picks[m][1]):
+                view_list.append(v[torch.from_numpy(idx).to(dev)])
                 gt_list.append(g)
         if fps:   # one call for the group's GT clouds, one for its views; the full clouds give way to their samples
             g_idx = _sampling._sample(gt_list, num_points, 0, status)[0]
@@ -286,7 +272,7 @@ def emd_of_split(predictions, gt_clouds, reference_rotation=None, num_points=102
             view_list = [v[i.long()] for v, i in zip(view_list, v_idx)]
         with torch.no_grad():
             emd = _run(view_list, gt_list, squared, eps, max_rounds, "emd_of_split", status)[0]
-        res = emd.cpu().numpy().reshape(len(group), V)
+        res = split.store(out, group, emd)
         if fps and bool((sampled < 0).any()):
             k = int(np.argmax(sampled.cpu().numpy() < 0))
             G = len(group)
@@ -296,5 +282,4 @@ def emd_of_split(predictions, gt_clouds, reference_rotation=None, num_points=102
             j, i = np.argwhere(np.isnan(res))[0]
             raise RuntimeError("emd_of_split: model %d, view %d did not converge within max_rounds (or holds a NaN "
                                "coordinate)" % (a + j, i))
-        out[a:a + len(group)] = res
     return out

@@ -25,7 +25,7 @@ import os
 import numpy as np
 import torch
 
-from . import _batch, _native
+from . import _batch, _native, _split
 from .alignment import as_rotation_matrix, quaternion_from_campos
 from .densify import MeshError
 from .visualise import read_png_any
@@ -663,24 +663,16 @@ def _groups(items, view_counts, step, workspace_limit):
         yield start, len(items)
 
 
-def _render_or_isolate(items, names, cams, errors, kwargs):
-    """One call for the batch; when it raises MeshError (a status bit is batch-wide), each model alone, so that the error
-    names the model or, with an `errors` dict, is recorded there and that model's result is None."""
-    try:
-        rgba, depth = render_mesh_views(items, cams, **kwargs)
-        rgba, depth = rgba.cpu().numpy(), depth.cpu().numpy()
-        out, o = [], 0
-        for c in cams:
-            out.append((rgba[o:o + len(c)], depth[o:o + len(c)]))
-            o += len(c)
-        return out
-    except MeshError as exc:
-        if len(items) == 1:
-            if errors is None:
-                raise MeshError("model %r: %s" % (names[0], exc)) from exc
-            errors[names[0]] = str(exc)
-            return [None]
-    return [r for it, name, c in zip(items, names, cams) for r in _render_or_isolate([it], [name], [c], errors, kwargs)]
+def _render_group(pairs, kwargs):
+    """One render_mesh_views call for (scene, cameras [v,3]) pairs: per pair (rgba [v,S,S,4], depth [v,S,S]) on the host."""
+    cams = [c for _, c in pairs]
+    rgba, depth = render_mesh_views([scene for scene, _ in pairs], cams, **kwargs)
+    rgba, depth = rgba.cpu().numpy(), depth.cpu().numpy()
+    out, o = [], 0
+    for c in cams:
+        out.append((rgba[o:o + len(c)], depth[o:o + len(c)]))
+        o += len(c)
+    return out
 
 
 def render_training_views(model_names, load_scene, cam_pos, save=None, models_per_call=64, errors=None, keep=True,
@@ -695,9 +687,7 @@ def render_training_views(model_names, load_scene, cam_pos, save=None, models_pe
     ShadedScenes load_obj_scene_shaded returns).  Returns {name: (rgba, depth)}, or {} with keep=False.  The
     images do not depend on the batching.  A model whose loading or rendering fails raises an error that names it; with
     an `errors` dict it is recorded there (errors[name] = message) and skipped, and the other models go on."""
-    step = int(models_per_call)
-    if step < 1:
-        raise ValueError("render_training_views: models_per_call must be >= 1")
+    step = _split.checked_step("render_training_views", models_per_call)
     model_names = list(model_names)
     if callable(cam_pos):
         cams_of = cam_pos
@@ -709,38 +699,27 @@ def render_training_views(model_names, load_scene, cam_pos, save=None, models_pe
             raise ValueError("render_training_views: cam_pos must be [%d,V,3], got %s" % (len(model_names), arr.shape))
         lookup = {n: arr[i] for i, n in enumerate(model_names)}
         cams_of = lookup.__getitem__
-    result, names, items, cams = {}, [], [], []
+    result = {}
 
-    def flush():
-        for a, b in _groups(items, [len(c) for c in cams], step, workspace_limit):
-            done = _render_or_isolate(items[a:b], names[a:b], cams[a:b], errors, render)
-            for name, c, res in zip(names[a:b], cams[a:b], done):
+    def load(name, i):
+        scene = load_scene(name)
+        if scene is None:
+            return None
+        item = _checked(scene, i)
+        c = np.asarray(cams_of(name), dtype=np.float64).reshape(-1, 3)
+        for p in c:
+            view_rotation(p)
+        return item, c
+
+    for batch in _split.batches(model_names, load, step, errors, (ValueError, IndexError, KeyError, OSError)):
+        names, pairs = [name for name, _ in batch], [pair for _, pair in batch]
+        for a, b in _groups([scene for scene, _ in pairs], [len(c) for _, c in pairs], step, workspace_limit):
+            done = _split.isolate(lambda group: _render_group(group, render), pairs[a:b], names[a:b], errors)
+            for name, (_, c), res in zip(names[a:b], pairs[a:b], done):
                 if res is None:
                     continue
                 if keep:
                     result[name] = res
                 if save is not None:
                     save(name, res[0], res[1], c)
-        del names[:], items[:], cams[:]
-
-    for name in model_names:
-        try:
-            scene = load_scene(name)
-            if scene is None:
-                continue
-            item = _checked(scene, len(items))
-            c = np.asarray(cams_of(name), dtype=np.float64).reshape(-1, 3)
-            for p in c:
-                view_rotation(p)
-        except (ValueError, IndexError, KeyError, OSError) as exc:
-            if errors is None:
-                raise type(exc)("model %r: %s" % (name, exc)) from exc
-            errors[name] = str(exc)
-            continue
-        items.append(item)
-        names.append(name)
-        cams.append(c)
-        if len(names) >= step:
-            flush()
-    flush()
     return result

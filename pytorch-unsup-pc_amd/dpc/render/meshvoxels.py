@@ -13,10 +13,10 @@ are those of voxelise, so the grid of a mesh and the grid of a cloud of the same
 import numpy as np
 import torch
 
-from . import _batch, _native
+from . import _batch, _native, _split
 from ._ops import status_word
 from .densify import MeshError
-from .voxels import MAX_SIDE, _bits_of_clouds, _bits_of_grids, _grid_tensor, _iou, _pair_stats, _shape_of, _unpack, _words
+from .voxels import MAX_SIDE, _bits_of_grids, _grid_tensor, _iou, _pair_stats, _shape_of, _unpack, _view_bits, _words
 
 _WHAT = "dpc.render mesh voxelisation"
 FILLS = {"none": _native.DPC_MESH_FILL_NONE, "carve": _native.DPC_MESH_FILL_CARVE, "parity": _native.DPC_MESH_FILL_PARITY}
@@ -147,52 +147,27 @@ def solid_iou_of_split(predictions, meshes, reference_rotation=None, vox_size=32
 
     predictions, reference_rotation and models_per_call as in iou_of_split; meshes as in voxelise_meshes, one per model.
     The result does not depend on the grouping.  Every argument is checked before anything is launched."""
-    from .chamfer import _host_unit_quaternion, _prediction, _rotate
-
     fn = "solid_iou_of_split"
     code = _fill(fill, fn)
     shape = _mesh_shape(vox_size, vox_size_z, fn)
-    if len(predictions) != len(meshes):
-        raise ValueError("%s: %d predictions and %d meshes" % (fn, len(predictions), len(meshes)))
-    step = int(models_per_call)
-    if step < 1:
-        raise ValueError("%s: models_per_call must be >= 1" % fn)
-    preds = [_prediction(e, m) for m, e in enumerate(predictions)]
-    M = len(preds)
-    groups = [range(a, min(M, a + step)) for a in range(0, M, step)]
-    checked = [_checked_meshes([meshes[m] for m in g], shape, code, fn) for g in groups]
-    views = {p.shape[0] for p, _ in preds}
-    if len(views) > 1:
-        raise ValueError("%s: every model needs the same number of views, got %s" % (fn, sorted(views)))
-    V = views.pop() if views else 0
-    qn = None if reference_rotation is None else _host_unit_quaternion(reference_rotation)
+    split = _split.Split(fn, predictions, meshes, reference_rotation, models_per_call, noun="meshes", gt_label=None)
+    checked = [_checked_meshes([meshes[m] for m in g], shape, code, fn) for g in split.groups]
+    M, V = split.M, split.V
     out = {"stats": np.zeros((M, V, 5), dtype=np.int64), "iou": np.full((M, V), np.nan), "dropped": np.zeros((M, V), dtype=np.int64),
            "info": np.zeros((M, 2), dtype=np.int64)}
     if M == 0:
         return out
-    dev = _batch.device(_WHAT, [p for p, _ in preds], [x for m in meshes for x in m[:2]])
-    for group, (items, desc) in zip(groups, checked):
+    dev = _batch.device(_WHAT, *split.tensors(), [x for m in meshes for x in m[:2]])
+    for group, (items, desc) in zip(split.groups, checked):
         gb, info = _bits_of_meshes(items, desc, shape, code, dev)
-        sl = slice(group[0], group[-1] + 1)
-        out["info"][sl] = info.cpu().numpy()
+        out["info"][group[0]:group[-1] + 1] = info.cpu().numpy()
         if V == 0:
             continue
-        views_list, gt_of = [], []
-        for j, m in enumerate(group):
-            pts, nums = preds[m]
-            pts = pts.detach()
-            if qn is not None:
-                pts = _rotate(pts, qn, dev)
-            for i in range(V):
-                views_list.append(pts[i] if nums is None else pts[i, :int(nums[i])])
-                gt_of.append(j)
-        views_list = [_batch.cloud(v, fn) for v in views_list]
-        pb, dropped = _bits_of_clouds(views_list, shape, dev, fn)
+        pb, dropped, pairs = _view_bits(split, group, shape, dev, fn)
         if carve_predictions:
             pb = _carved(pb, shape)
-        pairs = _batch.table(np.stack([np.arange(len(gt_of)), np.asarray(gt_of)], axis=1), 2, fn)
         stats = _pair_stats(pb, gb, pairs, shape)
-        out["stats"][sl] = stats.cpu().numpy().reshape(len(group), V, 5)
-        out["iou"][sl] = _iou(stats).cpu().numpy().reshape(len(group), V)
-        out["dropped"][sl] = dropped.cpu().numpy().reshape(len(group), V)
+        split.store(out["stats"], group, stats)
+        split.store(out["iou"], group, _iou(stats))
+        split.store(out["dropped"], group, dropped)
     return out

@@ -14,9 +14,9 @@ The rules of the search and of the normals (ties, padding, the sign, the accurac
 import numpy as np
 import torch
 
-from . import _batch, _native
+from . import _batch, _native, _split
 from ._ops import status_word
-from .chamfer import _host_unit_quaternion, _prediction, _rotate, nearest_batched
+from .chamfer import nearest_batched
 from .closest import _ClosestPlan
 from .pointmesh import _index_map
 
@@ -334,49 +334,26 @@ def normal_consistency_of_split(predictions, gt_clouds, gt_normals=None, k=16, r
     are the mesh faces').  The predictions' normals are always estimated with k.  The result does not
     depend on the grouping.  Every argument is checked before anything is launched."""
     fn = "normal_consistency_of_split"
-    if len(predictions) != len(gt_clouds):
-        raise ValueError("%s: %d predictions and %d GT clouds" % (fn, len(predictions), len(gt_clouds)))
-    step = int(models_per_call)
-    if step < 1:
-        raise ValueError("%s: models_per_call must be >= 1" % fn)
+    split = _split.Split(fn, predictions, gt_clouds, reference_rotation, models_per_call, gt_label=fn + ": gt_clouds[%d]",
+                         refuse_empty_gt=True)
     k = _check_k(k, fn)
-    preds = [_prediction(e, m) for m, e in enumerate(predictions)]
-    gts = [_batch.cloud(g, "%s: gt_clouds[%d]" % (fn, m)) for m, g in enumerate(gt_clouds)]
+    gts = split.gts
     given = _given_normals(gt_normals, gts, fn, "gt_normals", "gt_clouds")
-    views = {p.shape[0] for p, _ in preds}
-    if len(views) > 1:
-        raise ValueError("%s: every model needs the same number of views, got %s" % (fn, sorted(views)))
-    V = views.pop() if views else 0
-    for m, ((p, nums), g) in enumerate(zip(preds, gts)):
-        if len(g) == 0 and (p.shape[1] if nums is None else nums.max(initial=0)) > 0:
-            raise ValueError("%s: GT cloud %d is empty" % (fn, m))
-        if not p.is_cuda and p.numel() and not bool(torch.isfinite(p).all()):
-            raise ValueError("%s: predictions[%d] holds a NaN or inf coordinate" % (fn, m))
-    _refuse_nonfinite(gts, ["gt_clouds[%d]" % m for m in range(len(gts))], fn, True)
-    qn = None if reference_rotation is None else _host_unit_quaternion(reference_rotation)
-    M = len(preds)
+    _refuse_nonfinite([p for p, _ in split.preds], ["predictions[%d]" % m for m in range(split.M)], fn, True)
+    _refuse_nonfinite(gts, ["gt_clouds[%d]" % m for m in range(split.M)], fn, True)
     if gt_meshes is not None:
         # The meshes' own checks and the dry run of every group's table.  normal_consistency builds the same plan again
         # for each group; building them here first is what makes every refusal come before the first group is launched.
         _check_gt_meshes(gt_meshes, gt_normals, gts, fn)
-        for a in range(0, M, step):
-            _ClosestPlan(gts[a:a + step], gt_meshes[a:a + step], None, fn, "gt_clouds")
-    out = np.zeros((M, V, 3), dtype=np.float64)
-    if M == 0 or V == 0:
+        for g in split.groups:
+            _ClosestPlan([gts[m] for m in g], [gt_meshes[m] for m in g], None, fn, "gt_clouds")
+    out = np.zeros((split.M, split.V, 3), dtype=np.float64)
+    if split.empty:
         return out
-    dev = _batch.device(_WHAT, [p for p, _ in preds], gts, [] if gt_meshes is None else [x for m in gt_meshes for x in m[:2]])
-    for a in range(0, M, step):
-        group = range(a, min(M, a + step))
-        views_list, gt_of = [], []
-        for j, m in enumerate(group):
-            pts, nums = preds[m]
-            if qn is not None:
-                pts = _rotate(pts, qn, dev)
-            for i in range(V):
-                views_list.append(pts[i] if nums is None else pts[i, :int(nums[i])])
-                gt_of.append(j)
-        res = normal_consistency(views_list, [gts[m] for m in group], gt_of, k, None,
-                                 None if given is None else [given[m] for m in group],
-                                 None if gt_meshes is None else [gt_meshes[m] for m in group])
-        out[a:a + len(group)] = res.cpu().numpy().reshape(len(group), V, 3)
+    dev = _batch.device(_WHAT, *split.tensors(), [] if gt_meshes is None else [x for m in gt_meshes for x in m[:2]])
+    for group in split.groups:
+        views_list, gt_of = split.views(group, dev)
+        split.store(out, group, normal_consistency(views_list, [gts[m] for m in group], gt_of, k, None,
+                                                   None if given is None else [given[m] for m in group],
+                                                   None if gt_meshes is None else [gt_meshes[m] for m in group]))
     return out

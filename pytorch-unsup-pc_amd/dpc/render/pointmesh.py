@@ -15,9 +15,9 @@ The rules of the distance (zero-area faces, non-finite vertices) are stated in i
 import numpy as np
 import torch
 
-from . import _batch, _native
+from . import _batch, _native, _split
 from ._ops import status_word
-from .chamfer import _host_unit_quaternion, _prediction, _rotate, nearest_batched
+from .chamfer import nearest_batched
 from .densify import MeshError
 from .meshvoxels import _mesh
 
@@ -252,44 +252,21 @@ def fscore_of_split(predictions, gt_clouds, thresholds, reference_rotation=None,
     num_points[i] points, the rotation is applied to every view first); thresholds and gt_meshes (one mesh per model) as in
     fscore.  The result does not depend on the grouping.  Every argument is checked before anything is launched."""
     fn = "fscore_of_split"
-    if len(predictions) != len(gt_clouds):
-        raise ValueError("%s: %d predictions and %d GT clouds" % (fn, len(predictions), len(gt_clouds)))
+    split = _split.Split(fn, predictions, gt_clouds, reference_rotation, models_per_call, gt_label=fn + ": gt_clouds[%d]",
+                         refuse_empty_gt=True)
     if gt_meshes is not None and len(gt_meshes) != len(gt_clouds):
         raise ValueError("%s: %d GT clouds and %d GT meshes" % (fn, len(gt_clouds), len(gt_meshes)))
-    step = int(models_per_call)
-    if step < 1:
-        raise ValueError("%s: models_per_call must be >= 1" % fn)
     thr = _thresholds(thresholds, fn)
-    preds = [_prediction(e, m) for m, e in enumerate(predictions)]
-    gts = [_batch.cloud(g, "%s: gt_clouds[%d]" % (fn, m)) for m, g in enumerate(gt_clouds)]
-    views = {p.shape[0] for p, _ in preds}
-    if len(views) > 1:
-        raise ValueError("%s: every model needs the same number of views, got %s" % (fn, sorted(views)))
-    V = views.pop() if views else 0
-    for m, ((p, nums), g) in enumerate(zip(preds, gts)):
-        if len(g) == 0 and (p.shape[1] if nums is None else nums.max(initial=0)) > 0:
-            raise ValueError("%s: GT cloud %d is empty" % (fn, m))
-    qn = None if reference_rotation is None else _host_unit_quaternion(reference_rotation)
-    M = len(preds)
-    groups = [range(a, min(M, a + step)) for a in range(0, M, step)]
     if gt_meshes is not None:   # the meshes' own checks, and the table of every group with the views' sizes
-        for g in groups:
-            sizes = [torch.empty((p.shape[1] if nums is None else int(nums[i]), 3), device="meta")
-                     for p, nums in (preds[m] for m in g) for i in range(V)]
-            _Plan(sizes, [gt_meshes[m] for m in g], [j for j in range(len(g)) for _ in range(V)], fn, "views", "gt_of")
-    out = np.zeros((M, V, len(thr), 3), dtype=np.float64)
-    if M == 0 or V == 0:
+        for g in split.groups:
+            sizes = [torch.empty((n, 3), device="meta") for m in g for n in split.counts[m]]
+            _Plan(sizes, [gt_meshes[m] for m in g], [j for j in range(len(g)) for _ in range(split.V)], fn, "views", "gt_of")
+    out = np.zeros((split.M, split.V, len(thr), 3), dtype=np.float64)
+    if split.empty:
         return out
-    dev = _batch.device(_WHAT, [p for p, _ in preds], gts, [] if gt_meshes is None else [x for m in gt_meshes for x in m[:2]])
-    for group in groups:
-        views_list, gt_of = [], []
-        for j, m in enumerate(group):
-            pts, nums = preds[m]
-            if qn is not None:
-                pts = _rotate(pts, qn, dev)
-            for i in range(V):
-                views_list.append(pts[i] if nums is None else pts[i, :int(nums[i])])
-                gt_of.append(j)
-        res = fscore(views_list, [gts[m] for m in group], thr, gt_of, None if gt_meshes is None else [gt_meshes[m] for m in group])
-        out[group[0]:group[-1] + 1] = res.cpu().numpy().reshape(len(group), V, len(thr), 3)
+    dev = _batch.device(_WHAT, *split.tensors(), [] if gt_meshes is None else [x for m in gt_meshes for x in m[:2]])
+    for group in split.groups:
+        views_list, gt_of = split.views(group, dev)
+        split.store(out, group, fscore(views_list, [split.gts[m] for m in group], thr, gt_of,
+                                       None if gt_meshes is None else [gt_meshes[m] for m in group]))
     return out

@@ -20,7 +20,7 @@ import zlib
 import numpy as np
 import torch
 
-from . import _batch, _native
+from . import _batch, _native, _split
 
 POINT_SIZE = 0.01      # DEFAULT_SIZE x the unit UV-sphere prototype (render_point_cloud_blender.py:137, :196)
 SENSOR_MM = 32.0       # sensor_height (render_point_cloud_blender.py:86)
@@ -215,43 +215,33 @@ def render_split(model_names, load_points, save=None, view=0, colored_subsets=No
     bool, colors [k,3]) restates load_data's subsets.  **camera goes to render_point_clouds (azimuth, elevation, dist,
     image_size, supersample, point_size, lens_mm).  Returns {name: uint8 [S,S,3] numpy image}; the images do not depend
     on models_per_call."""
-    step = int(models_per_call)
-    if step < 1:
-        raise ValueError("render_split: models_per_call must be >= 1")
+    step = _split.checked_step("render_split", models_per_call)
     size = float(camera.pop("point_size", POINT_SIZE))
-    result, names, clouds, cols, rads = {}, [], [], [], []
+    result = {}
 
-    def flush():
-        if not names:
-            return
-        imgs = render_point_clouds(clouds, colors=cols if colored_subsets is not None else None,
-                                   radii=rads if colored_subsets is not None else None, point_size=size, **camera)
-        host = imgs.cpu().numpy()
-        for name, img in zip(names, host):
-            result[name] = img
-            if save is not None:
-                save(name, img)
-        del names[:], clouds[:], cols[:], rads[:]
-
-    for name in model_names:
+    def load(name, i):
+        """(cloud, colours | None, radii | None) of the model's view."""
         pcs = load_points(name)
         if pcs is None:
-            continue
+            return None
         pcs = np.asarray(pcs.detach().cpu() if isinstance(pcs, torch.Tensor) else pcs)
         if pcs.ndim == 2:
             pcs = pcs[None]
         if pcs.ndim != 3 or pcs.shape[2] != 3 or not 0 <= view < pcs.shape[0]:
             raise ValueError("render_split: model %r: points must be [V,N,3] with view %d, got %s" % (name, view, pcs.shape))
-        model = pcs[view]
-        if colored_subsets is not None:
-            model, c, scale = _subset_cloud(model, colored_subsets)
-            cols.append(c)
-            rads.append(scale * size)
-        clouds.append(model)
-        names.append(name)
-        if len(names) >= step:
-            flush()
-    flush()
+        if colored_subsets is None:
+            return pcs[view], None, None
+        model, c, scale = _subset_cloud(pcs[view], colored_subsets)
+        return model, c, scale * size
+
+    for batch in _split.batches(model_names, load, step):
+        clouds, cols, rads = ([item[k] for _, item in batch] for k in range(3))
+        imgs = render_point_clouds(clouds, colors=cols if colored_subsets is not None else None,
+                                   radii=rads if colored_subsets is not None else None, point_size=size, **camera)
+        for (name, _), img in zip(batch, imgs.cpu().numpy()):
+            result[name] = img
+            if save is not None:
+                save(name, img)
     return result
 
 

@@ -17,9 +17,9 @@ are those of voxel_stats (voxels.py).
 import numpy as np
 import torch
 
-from . import _batch, _native
+from . import _batch, _native, _split
 from ._ops import status_word
-from .voxels import _bits_of_clouds, _bits_of_grids, _grid_tensor, _shape_of, _source_bits, _sources, _unpack
+from .voxels import _bits_of_clouds, _bits_of_grids, _grid_tensor, _shape_of, _source_bits, _sources, _unpack, _view_bits
 
 _WHAT = "dpc.render voxel distances"
 NONE = _native.DPC_VOXEL_EDT_NONE
@@ -216,47 +216,21 @@ def voxel_fscore_of_split(predictions, gt_clouds, thresholds, reference_rotation
     checks; thresholds and surface as in voxel_fscore.  The result does not depend on models_per_call.  A group of models
     needs 4 bytes per voxel per distinct grid for its distance fields: models_per_call * (V + 1) grids, 1.5 GiB at the
     defaults with 5 views of 64^3.  Every argument is checked before anything is launched."""
-    from .chamfer import _host_unit_quaternion, _prediction, _rotate
-
     fn = "voxel_fscore_of_split"
     shape = _shape_of(vox_size, vox_size_z, fn)
     thr_sq = _thresholds_sq(thresholds, fn)
-    if len(predictions) != len(gt_clouds):
-        raise ValueError("%s: %d predictions and %d GT clouds" % (fn, len(predictions), len(gt_clouds)))
-    if int(models_per_call) < 1:
-        raise ValueError("%s: models_per_call must be >= 1" % fn)
-    preds = [_prediction(e, m) for m, e in enumerate(predictions)]
-    gts = [_batch.cloud(g, "gt_clouds[%d]" % m) for m, g in enumerate(gt_clouds)]
-    views = {p.shape[0] for p, _ in preds}
-    if len(views) > 1:
-        raise ValueError("%s: every model needs the same number of views, got %s" % (fn, sorted(views)))
-    V = views.pop() if views else 0
-    qn = None if reference_rotation is None else _host_unit_quaternion(reference_rotation)
-    M, K = len(preds), len(thr_sq)
+    split = _split.Split(fn, predictions, gt_clouds, reference_rotation, models_per_call)
+    M, V, K = split.M, split.V, len(thr_sq)
     out = {"stats": np.zeros((M, V, 2, 3 + K), dtype=np.int64), "fscore": np.full((M, V, K, 3), np.nan),
            "dropped": np.zeros((M, V), dtype=np.int64)}
-    if M == 0 or V == 0:
+    if split.empty:
         return out
-    dev = _batch.device(_WHAT, [p for p, _ in preds], gts)
-    step = int(models_per_call)
-    for a in range(0, M, step):
-        group = range(a, min(M, a + step))
-        views_list, gt_of = [], []
-        for j, m in enumerate(group):
-            pts, nums = preds[m]
-            pts = pts.detach()
-            if qn is not None:
-                pts = _rotate(pts, qn, dev)
-            for i in range(V):
-                views_list.append(pts[i] if nums is None else pts[i, :int(nums[i])])
-                gt_of.append(j)
-        views_list = [_batch.cloud(v, fn) for v in views_list]
-        pb, dropped = _bits_of_clouds(views_list, shape, dev, fn)
-        gb, _ = _bits_of_clouds([gts[m] for m in group], shape, dev, fn)
-        pairs = _batch.table(np.stack([np.arange(len(gt_of)), np.asarray(gt_of)], axis=1), 2, fn)
+    dev = _batch.device(_WHAT, *split.tensors())
+    for group in split.groups:
+        pb, dropped, pairs = _view_bits(split, group, shape, dev, fn)
+        gb, _ = _bits_of_clouds([split.gts[m] for m in group], shape, dev, fn)
         stats = _surface_stats(pb, gb, pairs, shape, thr_sq, bool(surface))
-        sl = slice(a, a + len(group))
-        out["stats"][sl] = stats.cpu().numpy().reshape(len(group), V, 2, 3 + K)
-        out["fscore"][sl] = _fscore_of(stats).cpu().numpy().reshape(len(group), V, K, 3)
-        out["dropped"][sl] = dropped.cpu().numpy().reshape(len(group), V)
+        split.store(out["stats"], group, stats)
+        split.store(out["fscore"], group, _fscore_of(stats))
+        split.store(out["dropped"], group, dropped)
     return out

@@ -15,7 +15,7 @@ inclusive, voxel2pc's axis order -- are in include/dpc_render.h (dpc_voxelise).
 import numpy as np
 import torch
 
-from . import _batch, _native
+from . import _batch, _native, _split
 from ._ops import status_word
 
 _WHAT = "dpc.render voxel evaluation"
@@ -348,48 +348,29 @@ def iou_of_split(predictions, gt_clouds, reference_rotation=None, vox_size=64, v
     num_points [V] | None), view i truncated to its first num_points[i] points and rotated by the quaternion first; the
     result does not depend on the grouping.  A non-finite coordinate is dropped and sets DPC_STATUS_NONFINITE in the
     status word.  Every argument is checked before anything is launched."""
-    from .chamfer import _host_unit_quaternion, _prediction, _rotate
-
     fn = "iou_of_split"
     shape = _shape_of(vox_size, vox_size_z, fn)
-    if len(predictions) != len(gt_clouds):
-        raise ValueError("%s: %d predictions and %d GT clouds" % (fn, len(predictions), len(gt_clouds)))
-    if int(models_per_call) < 1:
-        raise ValueError("%s: models_per_call must be >= 1" % fn)
-    preds = [_prediction(e, m) for m, e in enumerate(predictions)]
-    gts = [_batch.cloud(g, "gt_clouds[%d]" % m) for m, g in enumerate(gt_clouds)]
-    views = {p.shape[0] for p, _ in preds}
-    if len(views) > 1:
-        raise ValueError("%s: every model needs the same number of views, got %s" % (fn, sorted(views)))
-    V = views.pop() if views else 0
-    qn = None if reference_rotation is None else _host_unit_quaternion(reference_rotation)
-    M = len(preds)
+    split = _split.Split(fn, predictions, gt_clouds, reference_rotation, models_per_call)
+    M, V = split.M, split.V
     out = {"stats": np.zeros((M, V, 5), dtype=np.int64), "iou": np.full((M, V), np.nan), "dropped": np.zeros((M, V), dtype=np.int64)}
-    if M == 0 or V == 0:
+    if split.empty:
         return out
-    dev = _batch.device(_WHAT, [p for p, _ in preds], gts)
-    step = int(models_per_call)
-    for a in range(0, M, step):
-        group = range(a, min(M, a + step))
-        views_list, gt_of = [], []
-        for j, m in enumerate(group):
-            pts, nums = preds[m]
-            pts = pts.detach()
-            if qn is not None:
-                pts = _rotate(pts, qn, dev)
-            for i in range(V):
-                views_list.append(pts[i] if nums is None else pts[i, :int(nums[i])])
-                gt_of.append(j)
-        views_list = [_batch.cloud(v, fn) for v in views_list]
-        pb, dropped = _bits_of_clouds(views_list, shape, dev, fn)
-        gb, _ = _bits_of_clouds([gts[m] for m in group], shape, dev, fn)
-        pairs = _batch.table(np.stack([np.arange(len(gt_of)), np.asarray(gt_of)], axis=1), 2, fn)
+    dev = _batch.device(_WHAT, *split.tensors())
+    for group in split.groups:
+        pb, dropped, pairs = _view_bits(split, group, shape, dev, fn)
+        gb, _ = _bits_of_clouds([split.gts[m] for m in group], shape, dev, fn)
         stats = _pair_stats(pb, gb, pairs, shape)
-        sl = slice(a, a + len(group))
-        out["stats"][sl] = stats.cpu().numpy().reshape(len(group), V, 5)
-        out["iou"][sl] = _iou(stats).cpu().numpy().reshape(len(group), V)
-        out["dropped"][sl] = dropped.cpu().numpy().reshape(len(group), V)
+        split.store(out["stats"], group, stats)
+        split.store(out["iou"], group, _iou(stats))
+        split.store(out["dropped"], group, dropped)
     return out
+
+
+def _view_bits(split, group, shape, dev, fn):
+    """(bit grids, dropped, the [P,2] host table of (view, its model's position in the group)) of a group's views."""
+    views_list, gt_of = split.views(group, dev)
+    pb, dropped = _bits_of_clouds([_batch.cloud(v, fn) for v in views_list], shape, dev, fn)
+    return pb, dropped, _batch.table(np.stack([np.arange(len(gt_of)), np.asarray(gt_of)], axis=1), 2, fn)
 
 
 def render_voxels(voxels, threshold, **kw):

@@ -118,7 +118,7 @@ def test_f16_chamfer_restated_bit_for_bit(f16):
 def test_f16_rotation_path_restated_bit_for_bit(f16):
     """chamfer_of_split's rotation (host q / |q|, then the reference's quaternion products) evaluated in CPU torch gives the
     reference's rotated clouds; with them the restated means are F16's."""
-    from dpc.render.chamfer import _host_unit_quaternion, _rotate
+    from dpc.render._split import _host_unit_quaternion, _rotate
 
     qn = _host_unit_quaternion(f16["rotation"])
     rotate = lambda p: _rotate(torch.from_numpy(p), qn, torch.device("cpu")).numpy()

@@ -309,7 +309,7 @@ def test_gradient_of_coincident_couples_and_of_inputs_without_grad(squared):
 # 9 ---------------------------------------------------------------------------------------------------------------
 def test_emd_of_split_equals_emd_loss_on_the_same_subsamples():
     """Three models, two views, a reference rotation, one model with truncated views."""
-    from dpc.render.chamfer import _host_unit_quaternion, _rotate
+    from dpc.render._split import _host_unit_quaternion, _rotate
 
     rng = np.random.default_rng(12)
     M, V, N, K = 3, 2, 200, 128
@@ -335,3 +335,17 @@ def test_emd_of_split_equals_emd_loss_on_the_same_subsamples():
     with pytest.raises(RuntimeError, match="model 0, view 0 did not converge"):
         R.emd_of_split(preds, gts, num_points=K, eps=1e-6, max_rounds=2)
     assert R.check_status() == 0   # the split's failure was raised with names; the shared status word stays clean
+
+
+# 10 --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sampling", ["random", "fps"])
+def test_emd_of_split_does_not_depend_on_models_per_call(sampling):
+    """Three models (the last group is short at 2 per call), two views of 24 points, one view truncated to 16, a rotation."""
+    rng = np.random.default_rng(21)
+    preds = [((rng.random((2, 24, 3)) * 0.6 - 0.3).astype(np.float32), np.array([24, 16]) if m == 1 else None) for m in range(3)]
+    gts = [rng.random((20 + m, 3)) - 0.5 for m in range(3)]
+    q = np.array([[0.9, 0.1, -0.3, 0.2]])
+    got = [R.emd_of_split(preds, gts, reference_rotation=q, num_points=16, seed=3, eps=1e-6, models_per_call=step,
+                          sampling=sampling) for step in (1, 2, 256)]
+    assert got[0].shape == (3, 2) and got[0].dtype == np.float64 and (got[0] > 0).all()
+    assert got[0].tobytes() == got[1].tobytes() == got[2].tobytes()

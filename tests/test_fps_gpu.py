@@ -227,7 +227,7 @@ def test_a_device_table_that_differs_from_the_host_table_is_not_run():
 def test_emd_of_split_with_fps_equals_emd_loss_on_the_same_samples():
     """Three models, two views, a reference rotation, one model with truncated views: sampling="fps" equals emd_loss on
     clouds gathered with farthest_point_sample(first=0); sampling="random" equals the value through subsample_indices."""
-    from dpc.render.chamfer import _host_unit_quaternion, _rotate
+    from dpc.render._split import _host_unit_quaternion, _rotate
 
     rng = np.random.default_rng(12)
     M, V, N, K = 3, 2, 300, 64

@@ -252,3 +252,20 @@ def test_solid_iou_of_split_against_the_counts_composed_by_hand():
                 assert out["dropped"][m, v] == dropped and out["iou"][m, v] == VO.iou(s)
         assert out["dropped"][0, 0] == 3
     R.check_status()
+
+
+@pytest.mark.parametrize("carve_predictions", [True, False])
+def test_solid_iou_of_split_does_not_depend_on_models_per_call(carve_predictions):
+    """Three models (the last group is short at 2 per call), two views of 24 points, one view truncated to 16, a rotation,
+    a tetrahedron per model."""
+    rng = np.random.default_rng(21)
+    preds = [((rng.random((2, 24, 3)) * 0.6 - 0.3).astype(np.float32), np.array([24, 16]) if m == 1 else None) for m in range(3)]
+    corners = np.array([[-0.4, -0.4, -0.4], [0.4, -0.3, -0.35], [-0.3, 0.4, -0.3], [-0.35, -0.3, 0.4]])
+    meshes = [((corners * (1.0 - 0.1 * m)).astype(np.float32), np.array([[0, 2, 1], [0, 1, 3], [0, 3, 2], [1, 2, 3]])) for m in range(3)]
+    q = np.array([[0.9, 0.1, -0.3, 0.2]])
+    got = [R.solid_iou_of_split(preds, meshes, reference_rotation=q, vox_size=8, carve_predictions=carve_predictions,
+                                models_per_call=step) for step in (1, 2, 256)]
+    assert set(got[0]) == {"stats", "iou", "dropped", "info"} and got[0]["stats"].shape == (3, 2, 5) and got[0]["stats"][..., 1].any()
+    for key, a in got[0].items():
+        assert a.dtype == got[1][key].dtype == got[2][key].dtype and a.tobytes() == got[1][key].tobytes() == got[2][key].tobytes(), key
+    R.check_status()

@@ -274,7 +274,7 @@ def test_normal_consistency_closed_forms(f30, dev, pairs):
 
 def test_normal_consistency_of_split(f30, dev, pairs):
     import dpc.render as R
-    from dpc.render.chamfer import _host_unit_quaternion, _rotate
+    from dpc.render._split import _host_unit_quaternion, _rotate
 
     preds, gts, _, _, _ = pairs
     rng = np.random.default_rng(3)

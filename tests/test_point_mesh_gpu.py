@@ -202,7 +202,7 @@ def test_fscore_of_split_grouping_rotation_and_num_points(f28):
             for m in range(M):
                 p = torch.from_numpy(pts[m])
                 if rot is not None:
-                    p = R.chamfer._rotate(p, R.chamfer._host_unit_quaternion(rot), torch.device("cuda"))
+                    p = R._split._rotate(p, R._split._host_unit_quaternion(rot), torch.device("cuda"))
                 for i in range(V):
                     views.append(p[i] if nums[m] is None else p[i, :int(nums[m][i])])
                     gt_of.append(m)

@@ -326,7 +326,7 @@ def test_reference_functions_on_the_fixture_inputs_equal_the_fixture():
 def test_iou_of_split_against_per_pair_oracle_calls():
     """3 models x 2 views, one model with truncated views, a reference rotation: stats, iou and dropped equal the oracle on
     the rotated, truncated views; models_per_call 1 and 256 agree bit for bit."""
-    from dpc.render.chamfer import _host_unit_quaternion, _rotate
+    from dpc.render._split import _host_unit_quaternion, _rotate
 
     rng = np.random.default_rng(12)
     M, V, N, G = 3, 2, 300, 16
