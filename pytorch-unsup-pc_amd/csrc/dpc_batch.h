@@ -2,7 +2,7 @@
 // dpc_densify.hip).  Items (clouds, pairs of clouds, meshes) are (start, count) ranges of packed buffers, listed in a
 // host int32 descriptor table with a device copy.  The host checks the table (check_desc) and carves one
 // caller-allocated workspace (Carver); the device builds per-item prefixes (block_scan), and each block finds its item
-// by binary search in them (owner).
+// by binary search in them (owner).  The voxel files share check_pairs and block_sum as well.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,6 +50,15 @@ int check_desc(const int32_t* desc, int rows, const int64_t (&len)[K], int64_t l
   return DPC_OK;
 }
 
+// Host check of a table of `pairs` rows (i, j) of int32: items i of n_a and j of n_b.
+inline int check_pairs(const int32_t* host_pairs, int pairs, int n_a, int n_b) {
+  for (int p = 0; p < pairs; ++p) {
+    const int32_t i = host_pairs[2 * (int64_t)p], j = host_pairs[2 * (int64_t)p + 1];
+    if (i < 0 || i >= n_a || j < 0 || j >= n_b) return DPC_ERR_SHAPE;
+  }
+  return DPC_OK;
+}
+
 // The largest i < n with pre[i] <= x, for an exclusive prefix pre[0..n]: items without work share their prefix with the
 // next item that has some, so the search always lands on the item that owns work unit x.
 __device__ inline int owner(const int32_t* __restrict__ pre, int n, int x) {
@@ -84,4 +93,21 @@ __device__ inline T block_scan(T v, T* excl, T* scratch) {
   const T total = scratch[N / 64];
   __syncthreads();
   return total;
+}
+
+// The sum of one T per thread over a block of THREADS threads, in thread 0 alone (0 elsewhere): wave sums in T by
+// shuffles, then thread 0 adds the waves in wave order in Acc.  scratch holds THREADS / 64 T in LDS.  Every thread of
+// the block must call it.
+template <int THREADS, class Acc, class T>
+__device__ inline Acc block_sum(T v, T* scratch) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  if (lane == 0) scratch[wave] = v;
+  __syncthreads();
+  Acc s = 0;
+  if (t == 0)
+    for (int w = 0; w < THREADS / 64; ++w) s += scratch[w];
+  __syncthreads();
+  return s;
 }

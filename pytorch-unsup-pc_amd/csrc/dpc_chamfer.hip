@@ -24,7 +24,7 @@
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
 #include "dpc_nearest.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -298,7 +298,7 @@ int chamfer_impl(const T* pts, const int32_t* desc, const ChGeom& g, int pairs, 
   }
   DPC_LAUNCH("k_chamfer_mean", dpc_kid("k_chamfer_mean"), k_chamfer_mean, dim3((pairs + 63) / 64), dim3(64), 0, st, pairs,
              w.pre, (const double*)w.chunk_sum, mean);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 // The mean stage alone, over values the caller packed in pair order (the squared distances of the Chamfer loss).
@@ -315,7 +315,7 @@ int chamfer_means_impl(const T* values, const int32_t* desc, const ChGeom& g, in
                k_chamfer_chunks<T>, dim3((unsigned)g.chunks), dim3(64), 0, st, pairs, w.pre, values, w.chunk_sum);
   DPC_LAUNCH("k_chamfer_mean", dpc_kid("k_chamfer_mean"), k_chamfer_mean, dim3((pairs + 63) / 64), dim3(64), 0, st, pairs,
              w.pre, (const double*)w.chunk_sum, mean);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // namespace

@@ -23,7 +23,7 @@
 
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -252,7 +252,7 @@ int bwd_impl(const T* pts, int n_pts, const int32_t* desc, const BwGeom& g, int 
   DPC_LAUNCH("k_chamfer_bwd_gather", dpc_kid(kIsF64 ? "k_chamfer_bwd_gather<double>" : "k_chamfer_bwd_gather<float>"),
              k_chamfer_bwd_gather<T>, dim3((unsigned)bw_blocks(n_pts)), dim3(kBwThreads), 0, st, desc, pairs, w.pre, n_pts,
              (const T*)term, (const T*)tsum, dpts);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // namespace

@@ -22,7 +22,7 @@
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
 #include "dpc_point_mesh.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -178,7 +178,7 @@ int pc_launch(const void* pts, int n_pts, const void* verts, int n_verts, const 
   DPC_LAUNCH("k_pc_finish", dpc_kid("k_pc_finish", PF64, VF64), (k_pc_finish<PF64, VF64>),
              dim3((unsigned)((g.points + kPmOutBlock - 1) / kPmOutBlock)), dim3(kPmOutBlock), 0, st, pts, n_pts, verts, n_verts, faces,
              n_faces, desc, pairs, g.chunk, w, (int)slots, (int)g.points, d2, face, closest, weights, normal);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // namespace

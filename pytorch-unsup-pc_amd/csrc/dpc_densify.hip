@@ -23,7 +23,7 @@
 
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -566,7 +566,7 @@ int dpc_densify(const double* verts, int n_verts, const int32_t* edges, int n_ed
     DPC_LAUNCH("k_dn_faces", dpc_kid("k_dn_faces"), k_dn_faces, dim3(kDnFaceBlocks, models), dim3(kDnThreads), 0, st, w,
                out, status);
   }
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // extern "C"

@@ -26,7 +26,7 @@
 
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -464,7 +464,7 @@ int ds_impl(const T* pts, const int32_t* desc, int clouds, int members, double v
   }
   DPC_LAUNCH("k_ds_clouds", dpc_kid("k_ds_clouds"), k_ds_clouds, dim3((clouds + kDsThreads - 1) / kDsThreads),
              dim3(kDsThreads), 0, st, clouds, w, out_count, out_offset);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // namespace

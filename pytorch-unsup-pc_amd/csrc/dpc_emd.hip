@@ -27,13 +27,12 @@
 // k_emd_bwd<T>: one thread per point index of a pair, writing that index's pred row and gt row of the gradient.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -330,31 +329,17 @@ int em_check(int pairs, const int32_t* desc, int64_t n_pred, int64_t n_gt, int* 
   return DPC_OK;
 }
 
-// the auction needs more dynamic LDS than the default limit: raised once per kernel and device
-template <class T>
-int em_raise_lds() {
-  static std::atomic<int> raised[16];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return DPC_ERR_LAUNCH;
-  const bool tracked = dev >= 0 && dev < 16;
-  if (tracked && raised[dev].load(std::memory_order_relaxed)) return DPC_OK;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_emd_auction<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)em_lds_bytes(DPC_EMD_MAX_POINTS)) != hipSuccess)
-    return DPC_ERR_LAUNCH;
-  if (tracked) raised[dev].store(1, std::memory_order_relaxed);
-  return DPC_OK;
-}
-
 template <class T>
 int em_fwd(const T* pred, int n_pred, const T* gt, int n_gt, const int32_t* desc, int pairs, int n_cap, int squared, double eps,
            int max_rounds, double* emd, int32_t* assignment, int32_t* inverse, int32_t* rounds, int32_t* status, hipStream_t st) {
-  const int rc = em_raise_lds<T>();
+  static LdsLimit limit;  // the largest pair's size, so one driver call per kernel and device
+  const int rc = set_lds(k_emd_auction<T>, em_lds_bytes(DPC_EMD_MAX_POINTS), limit);
   if (rc != DPC_OK) return rc;
   constexpr bool kIsF64 = sizeof(T) == sizeof(double);
   DPC_LAUNCH("k_emd_auction", dpc_kid(kIsF64 ? "k_emd_auction<double>" : "k_emd_auction<float>"), k_emd_auction<T>,
              dim3((unsigned)pairs), dim3(kEmThreads), em_lds_bytes(n_cap), st, pred, n_pred, gt, n_gt, desc, n_cap, squared, eps,
              max_rounds, emd, assignment, inverse, rounds, status);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 template <class T>
@@ -364,7 +349,7 @@ int em_bwd(const T* pred, const T* gt, const int32_t* desc, int pairs, int n_cap
   DPC_LAUNCH("k_emd_bwd", dpc_kid(kIsF64 ? "k_emd_bwd<double>" : "k_emd_bwd<float>"), k_emd_bwd<T>,
              dim3((unsigned)pairs, (unsigned)((n_cap + kEmBwThreads - 1) / kEmBwThreads)), dim3(kEmBwThreads), 0, st, pred, gt,
              desc, squared, emd, assignment, inverse, gemd, dpred, dgt);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // namespace

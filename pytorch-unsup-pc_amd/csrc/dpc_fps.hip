@@ -25,14 +25,13 @@
 // (the host table said otherwise), is flagged DPC_STATUS_BAD_INDEX by the first launch and not run.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <climits>
 #include <cstdint>
 #include <type_traits>
 
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -248,21 +247,12 @@ int fp_launch(const void* pts, int n_pts, const int32_t* desc, int clouds, int n
   constexpr int THREADS = kFpThreads[CLS], PPT = kFpPpt[CLS];
   constexpr size_t lds = FpLds<THREADS, PPT, (F64 != 0 && PPT > 8)>::kBytes;
   static_assert(lds <= 160 * 1024, "a cloud's state must fit the CU's 160 KiB of LDS");
-  if (lds > 64 * 1024) {  // more dynamic LDS than the default limit: raised once per kernel and device
-    static std::atomic<int> raised[16];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return DPC_ERR_LAUNCH;
-    const bool tracked = dev >= 0 && dev < 16;
-    if (!(tracked && raised[dev].load(std::memory_order_relaxed))) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_fps<F64, THREADS, PPT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DPC_ERR_LAUNCH;
-      if (tracked) raised[dev].store(1, std::memory_order_relaxed);
-    }
-  }
+  static LdsLimit limit;
+  const int rc = set_lds(k_fps<F64, THREADS, PPT>, lds, limit);
+  if (rc != DPC_OK) return rc;
   DPC_LAUNCH("k_fps", dpc_kid("k_fps", F64, THREADS, PPT), (k_fps<F64, THREADS, PPT>), dim3((unsigned)clouds), dim3(THREADS), lds,
              st, pts, n_pts, desc, n_out, mask, flagger, indices, radius2, status);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 template <int F64>

@@ -30,7 +30,7 @@
 #include <algorithm>
 
 #include "dpc_common.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace dpcg {
 
@@ -308,8 +308,6 @@ float scale_of(int G, double sigma, int normalise) {
   const double sn = sigma * (double)G;
   return (float)(1.0 / (kMagic * sn * sn * sn));
 }
-
-int launch_ok() { return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH; }
 
 }  // namespace dpcg
 

@@ -20,7 +20,7 @@
 // The taps come as a launch argument (a host array) or are read from device memory by the kernel (a DeviceSchedule's
 // taps_xy: a captured graph follows sigma).  Equal inputs give equal bits on every run.
 #include "dpc_common.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace dpcs {
 
@@ -127,7 +127,7 @@ int dpc_gt_smooth(const float* gt, int S, int C, int Hs, int Ws, int planar, int
   hipStream_t st = (hipStream_t)stream;
   DPC_LAUNCH("k_gt_smooth", dpc_kid("k_gt_smooth"), k_gt_smooth, dim3((unsigned)blocks), dim3(kThreads), lds_bytes(ntaps), st, gt, p,
              taps, dev_taps, out);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // extern "C"

@@ -22,7 +22,7 @@
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
 #include "dpc_nearest.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -399,7 +399,7 @@ int dpc_icp_point_to_point(const double* src, int n_src, const double* tgt, int 
     DPC_LAUNCH("k_icp_solve", dpc_kid("k_icp_solve"), k_icp_solve, dim3((pairs + 63) / 64), dim3(64), 0, st, tgt, pair_desc,
                pairs, sb, round, max_iter, rel_fitness, rel_rmse, w, transform, fitness, inlier_rmse, iterations);
   }
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // extern "C"

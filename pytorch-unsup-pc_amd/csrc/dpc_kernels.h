@@ -11,7 +11,7 @@
 #include <atomic>
 
 #include "dpc_common.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 #ifdef DPC_ABLATE
 // Diagnostic builds only (-DDPC_ABLATE): per-translation-unit switches that cut work out of the kernels (timing
@@ -700,31 +700,10 @@ inline int planes_fit(const DpcParams* p) { return kLdsBudget / ((p->H * (p->W |
 inline int slab_threads(const DpcParams* p) { return (long long)p->H * p->W >= 2048 ? kSlabThreads : 256; }
 inline int col_tiles(const DpcParams* p) { return (p->H * p->W + kColThreads - 1) / kColThreads; }
 
-// Raise a kernel's dynamic-LDS limit.  hipFuncSetAttribute is a driver call, so it is made once per kernel, device and
-// size instead of on every launch: every launcher keeps, per device, the largest size it has set (relaxed atomics: two
-// threads racing on the first launch both make the call, which is idempotent).  `slot` is a static of the launcher's
-// template instantiation = one per kernel.
-struct LdsLimit {
-  std::atomic<size_t> set[16];
-};
-template <class K>
-int set_lds(K kernel, size_t bytes, LdsLimit& slot) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return DPC_ERR_LAUNCH;
-  const bool tracked = dev >= 0 && dev < 16;
-  if (tracked && slot.set[dev].load(std::memory_order_relaxed) >= bytes) return DPC_OK;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-    return DPC_ERR_LAUNCH;
-  if (tracked) slot.set[dev].store(bytes, std::memory_order_relaxed);
-  return DPC_OK;
-}
-
 inline RayHost ray_host(const DpcParams* p) {
   const double eps = (double)p->clip_val;
   return RayHost{p->clip_val, (float)(1.0 - eps), (float)expm1(eps)};
 }
-
-inline int launch_ok() { return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH; }
 
 inline Cells cells_view(const DpcParams* p, const void* cells) {
   return Cells{static_cast<const uint8_t*>(cells), chunk_bytes(p->D), num_chunks(p->N)};

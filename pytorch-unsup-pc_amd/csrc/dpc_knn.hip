@@ -25,7 +25,7 @@
 
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -324,7 +324,7 @@ int knn_impl(const void* pts, int n_pts, const int32_t* desc, int rows, int k, i
     case 128: knn_launch<T, 128>(p, n_pts, desc, rows, k, max_q, total_q, idx, d, status, st); break;
     default: knn_launch<T, 64>(p, n_pts, desc, rows, k, max_q, total_q, idx, d, status, st); break;
   }
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 template <class T>
@@ -337,7 +337,7 @@ int pca_impl(const void* pts, int n_pts, const int32_t* desc, int rows, int k, i
     DPC_LAUNCH("k_pca_normals", dpc_kid("k_pca_normals", kIsF64 ? 1 : 0), k_pca_normals<T>, dim3(gx, gy), dim3(kPcaBlock), 0, st,
                static_cast<const T*>(pts), n_pts, desc, row0, k, total_q, idx, viewpoints, normals, evals, status);
   }
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // namespace

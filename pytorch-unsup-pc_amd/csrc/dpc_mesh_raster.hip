@@ -24,7 +24,7 @@
 
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -561,7 +561,7 @@ int mr_launch(const double* verts, const int32_t* faces, const int32_t* face_mat
     DPC_LAUNCH("k_mr_tile", dpc_kid("k_mr_tile", 0), k_mr_tile<false>, tile, dim3(kMrThreads), 0, st, verts, faces, face_mat,
                kd, meshes, view_mesh, view_cam, sp.voff, sp.foff, sp.proj, sp.boxes, tiles_x, S, ss, rgba, depth, face_id);
   }
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 // The checks of sizes both entry points make first.

@@ -26,14 +26,14 @@
 // Nothing waits on another workgroup; every loop is bounded by a host-checked size or a checked table entry.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <climits>
 #include <cstdint>
 #include <type_traits>
 
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
+#include "dpc_voxel_bits.h"
 
 namespace {
 
@@ -50,19 +50,14 @@ static_assert(kMvPadWords >= 2 * kMvPlaneWords, "a slab holds a plane and its ha
 
 constexpr int mv_class(int64_t words) { return words <= kMvWords[0] ? 0 : words <= kMvWords[1] ? 1 : 2; }
 
-struct MvGrid {
-  int D, H, W, V, words;
+struct MvGrid : VoxelGrid {
   int Wp, PW;       // words of a padded row, of a padded plane
   int halo;         // 1: a slab's last word may reach into the next plane
   int zs, slabs;    // planes a slab owns, slabs of a grid
 };
 
 bool mv_grid(int D, int H, int W, int min_side, MvGrid* g) {
-  if (D < min_side || H < min_side || W < min_side || D > DPC_VOXEL_MAX_SIDE || H > DPC_VOXEL_MAX_SIDE || W > DPC_VOXEL_MAX_SIDE)
-    return false;
-  g->D = D; g->H = H; g->W = W;
-  g->V = D * H * W;
-  g->words = (g->V + 31) / 32;
+  if (!voxel_grid(D, H, W, min_side, g)) return false;
   g->Wp = (W + 31) / 32;
   g->PW = H * g->Wp;
   g->halo = (H * W) % 32 != 0;
@@ -101,20 +96,6 @@ __device__ inline uint32_t mv_flat_word(const uint32_t* rows, int j, int za, int
     f += n;
   }
   return out;
-}
-
-template <int THREADS>
-__device__ inline int mv_block_sum(int v, int* scratch) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  if (lane == 0) scratch[wave] = v;
-  __syncthreads();
-  int s = 0;
-  if (t == 0)
-    for (int w = 0; w < THREADS / 64; ++w) s += scratch[w];
-  __syncthreads();
-  return s;
 }
 
 constexpr int kMvBadIndex = 1, kMvNonFinite = 2, kMvOutside = 4;
@@ -479,7 +460,7 @@ __global__ __launch_bounds__(THREADS) void k_mv_parity(const void* __restrict__ 
   const uint32_t* s = surface + (size_t)mesh * words;
   uint32_t* out = bits + (size_t)mesh * words;
   for (int j = j0 + t; j < j1; j += THREADS) out[j] = s[j] | mv_flat_word(rows, j, za, H, W, Wp, V);
-  const int total = mv_block_sum<THREADS>(open, extra + 2);
+  const int total = block_sum<THREADS, int>(open, extra + 2);
   if (slab == 0 && t == 0) info[2 * (size_t)mesh + 1] = total;
 }
 
@@ -564,33 +545,20 @@ __global__ __launch_bounds__(THREADS) void k_mv_carve(const uint32_t* __restrict
   for (int j = j0 + t; j < j1; j += THREADS) out[j] = mv_flat_word(res, j, za, H, W, Wp, V);
 }
 
-// more dynamic LDS than the default limit: raised once per kernel and device
-template <class K>
-bool mv_raise_lds(K kernel, size_t lds, std::atomic<int>* raised) {
-  if (lds <= 48 * 1024) return true;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return false;
-  const bool tracked = dev >= 0 && dev < 16;
-  if (tracked && raised[dev].load(std::memory_order_relaxed) >= (int)lds) return true;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return false;
-  if (tracked) raised[dev].store((int)lds, std::memory_order_relaxed);
-  return true;
-}
-
 template <int F64, int CLS>
 int mv_surface_launch(const void* verts, int n_verts, const int32_t* faces, int n_faces, const int32_t* desc, int meshes,
                       const MvGrid& g, uint32_t* bits, int32_t* info, int32_t* status, hipStream_t st) {
   constexpr int WORDS = kMvWords[CLS], THREADS = kMvThreads[CLS];
   constexpr size_t lds = sizeof(uint32_t) * (WORDS + kMvExtra + 2 * THREADS);
   static_assert(lds <= 80 * 1024, "two workgroups share the CU's 160 KiB of LDS");
-  static std::atomic<int> raised[16];
-  if (!mv_raise_lds(k_mv_surface<F64, WORDS, THREADS>, lds, raised)) return DPC_ERR_LAUNCH;
+  static LdsLimit limit;
+  const int rc = set_lds(k_mv_surface<F64, WORDS, THREADS>, lds, limit);
+  if (rc != DPC_OK) return rc;
   const int slabs = (g.words + WORDS - 1) / WORDS;
   DPC_LAUNCH("k_mv_surface", dpc_kid("k_mv_surface", F64, WORDS, THREADS), (k_mv_surface<F64, WORDS, THREADS>),
              dim3((unsigned)meshes * (unsigned)slabs), dim3(THREADS), lds, st, verts, n_verts, faces, n_faces, desc, slabs, g.D, g.H,
              g.W, g.words, bits, info, status);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 template <int F64>
@@ -610,22 +578,24 @@ template <int F64, int THREADS>
 int mv_parity_launch(const void* verts, int n_verts, const int32_t* faces, int n_faces, const int32_t* desc, int meshes,
                      const MvGrid& g, const uint32_t* surface, uint32_t* bits, int32_t* info, hipStream_t st) {
   const size_t lds = sizeof(uint32_t) * ((size_t)(g.zs + g.halo + 2) * g.PW + THREADS + 2 + THREADS / 64 + 1);
-  static std::atomic<int> raised[16];
-  if (!mv_raise_lds(k_mv_parity<F64, THREADS>, lds, raised)) return DPC_ERR_LAUNCH;
+  static LdsLimit limit;
+  const int rc = set_lds(k_mv_parity<F64, THREADS>, lds, limit);
+  if (rc != DPC_OK) return rc;
   DPC_LAUNCH("k_mv_parity", dpc_kid("k_mv_parity", F64, THREADS), (k_mv_parity<F64, THREADS>),
              dim3((unsigned)meshes * (unsigned)g.slabs), dim3(THREADS), lds, st, verts, n_verts, faces, n_faces, desc, g.slabs, g.zs,
              g.halo, g.D, g.H, g.W, g.words, surface, bits, info);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 template <int THREADS>
 int mv_carve_launch(const uint32_t* in, int B, const MvGrid& g, uint32_t* out, hipStream_t st) {
   const size_t lds = sizeof(uint32_t) * ((size_t)(2 * (g.zs + g.halo) + 2) * g.PW);
-  static std::atomic<int> raised[16];
-  if (!mv_raise_lds(k_mv_carve<THREADS>, lds, raised)) return DPC_ERR_LAUNCH;
+  static LdsLimit limit;
+  const int rc = set_lds(k_mv_carve<THREADS>, lds, limit);
+  if (rc != DPC_OK) return rc;
   DPC_LAUNCH("k_mv_carve", dpc_kid("k_mv_carve", THREADS), (k_mv_carve<THREADS>), dim3((unsigned)B * (unsigned)g.slabs), dim3(THREADS),
              lds, st, in, g.slabs, g.zs, g.halo, g.D, g.H, g.W, g.words, out);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 int mv_carve(const uint32_t* in, int B, const MvGrid& g, uint32_t* out, hipStream_t st) {

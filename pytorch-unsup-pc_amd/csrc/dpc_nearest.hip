@@ -14,7 +14,7 @@
 
 #include "../../include/dpc_render.h"
 #include "dpc_nearest.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -84,7 +84,7 @@ int nearest_impl(const T* vs, const T* vt, int ns, int nt, T* proj, T* min_dist,
   DPC_LAUNCH("k_nearest_partial", dpc_kid(kIsF64 ? "k_nearest_partial<double>" : "k_nearest_partial<float>"), k_nearest_partial<T>, grid, dim3(kNnThreads), 0, st, vs, vt, ns, nt, slice, part_dist, part_idx);
   DPC_LAUNCH("k_nearest_merge", dpc_kid(kIsF64 ? "k_nearest_merge<double>" : "k_nearest_merge<float>"), k_nearest_merge<T>, dim3(grid.x), dim3(kNnThreads), 0, st, vt, ns, nslice,
              (const T*)part_dist, (const int*)part_idx, proj, min_dist, idx);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // namespace

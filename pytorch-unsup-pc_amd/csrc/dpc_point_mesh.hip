@@ -32,7 +32,7 @@
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
 #include "dpc_point_mesh.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -101,7 +101,7 @@ int pm_launch(const void* pts, int n_pts, const void* verts, int n_verts, const 
               int pairs, const PmGeom& g, const PmWork& w, double* d2, int32_t* status, hipStream_t st) {
   DPC_LAUNCH("k_pm_dist", dpc_kid("k_pm_dist", PF64, VF64), (k_pm_dist<PF64, VF64>), dim3((unsigned)g.work), dim3(kPmBlock), 0, st, pts,
              n_pts, verts, n_verts, faces, n_faces, desc, pairs, g.chunk, w, (int)g.points, d2, status);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // namespace

@@ -18,7 +18,7 @@
 
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -230,7 +230,7 @@ int dpc_render_points(const double* points, const float* colors, const double* r
   hipStream_t st = (hipStream_t)stream;
   DPC_LAUNCH("k_rs_tile", dpc_kid("k_rs_tile"), k_rs_tile, dim3(images * tiles_x * tiles_x), dim3(kRsThreads), 0, st,
              points, colors, radii, table, frames, tiles_x, S, ss, focal, radius, image, ids, status);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // extern "C"

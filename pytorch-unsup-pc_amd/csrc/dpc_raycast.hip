@@ -29,7 +29,7 @@
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
 #include "dpc_point_mesh.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -227,7 +227,7 @@ int rc_launch(const void* org, const void* dir, int n_rays, const void* verts, i
   DPC_LAUNCH("k_rc_finish", dpc_kid("k_rc_finish", RF64, VF64), (k_rc_finish<RF64, VF64>),
              dim3((unsigned)((g.points + kPmOutBlock - 1) / kPmOutBlock)), dim3(kPmOutBlock), 0, st, org, dir, n_rays, verts, n_verts, faces,
              n_faces, desc, pairs, g.chunk, w, (int)slots, (int)g.points, t, face, weights, hits, normal, status);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // namespace

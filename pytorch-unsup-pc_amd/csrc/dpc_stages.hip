@@ -5,6 +5,7 @@
 #include <math.h>
 
 #include "dpc_common.h"
+#include "dpc_launch.h"
 
 namespace {
 
@@ -20,8 +21,6 @@ int validate(const DpcParams* p) {
   if ((p->dev_taps_xy != nullptr && p->taps_xy < 1) || (p->dev_taps_z != nullptr && p->taps_z < 1)) return DPC_ERR_TAPS;
   return DPC_OK;
 }
-
-int launch_ok() { return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH; }
 
 // ------------------------------------------------------------------------------------------------------
 // pc_perspective_transform                              dpc/util/point_cloud_to.py:118-178

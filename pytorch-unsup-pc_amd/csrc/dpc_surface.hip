@@ -29,7 +29,7 @@
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
 #undef DPC_LAUNCH_TWICE  // the timing experiment of dpc_profile.h is for idempotent kernels only; k_surface_scan is not one
-#include "dpc_profile.h"
+#include "dpc_launch.h"
 #include "dpc_surface_table.h"
 
 namespace {
@@ -402,7 +402,7 @@ int dpc_surface_count(const void* values, int n_values, int is_f64, const int32_
   else sf_launch_tiles<0>(values, n_values, grid_desc, B, max_tiles, iso, w.tiles, status, st);
   DPC_LAUNCH("k_surface_scan", dpc_kid("k_surface_scan"), k_surface_scan, dim3((unsigned)B), dim3(kSfThreads), 0, st, grid_desc,
              n_values, max_tiles, w.tiles, counts, (const int32_t*)nullptr, 0, 0, (int32_t*)nullptr, status);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 int dpc_surface_extract(const void* values, int n_values, int is_f64, const int32_t* grid_desc, const int32_t* host_grid_desc,
@@ -437,7 +437,7 @@ int dpc_surface_extract(const void* values, int n_values, int is_f64, const int3
   const dim3 grid((unsigned)max_tiles, (unsigned)(B < 65535 ? B : 65535));
   DPC_LAUNCH("k_surface_faces", dpc_kid("k_surface_faces"), k_surface_faces, grid, dim3(kSfThreads), 0, st, grid_desc, n_values, B,
              max_tiles, w.tiles, w.ok, out_desc, w.map, faces);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // extern "C"

@@ -37,7 +37,8 @@
 
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
+#include "dpc_voxel_bits.h"
 
 namespace {
 
@@ -47,28 +48,7 @@ static_assert((int64_t)kEdtInf + 2 * (DPC_VOXEL_MAX_SIDE - 1) * (DPC_VOXEL_MAX_S
 static_assert(3 * (DPC_VOXEL_MAX_SIDE - 1) * (DPC_VOXEL_MAX_SIDE - 1) < kEdtInf, "every finite distance is below the infinite value");
 static_assert(DPC_VOXEL_EDT_NONE == INT32_MAX, "the value of a grid without a seed");
 
-struct EdtGrid {
-  int D, H, W, V, words;
-};
-
-// 1 <= D, H, W <= DPC_VOXEL_MAX_SIDE
-bool edt_grid(int D, int H, int W, EdtGrid* g) {
-  if (D < 1 || H < 1 || W < 1 || D > DPC_VOXEL_MAX_SIDE || H > DPC_VOXEL_MAX_SIDE || W > DPC_VOXEL_MAX_SIDE) return false;
-  g->D = D; g->H = H; g->W = W;
-  g->V = D * H * W;
-  g->words = (g->V + 31) / 32;
-  return true;
-}
-
 constexpr int edt_class(int side) { return side <= 32 ? 32 : side <= 64 ? 64 : 128; }
-
-// the 32 bits of a grid from bit p on (p may be negative or reach past the last word: those bits read as zero)
-__device__ inline uint32_t edt_window(const uint32_t* __restrict__ w, int words, int p) {
-  const int j = p >> 5, s = p & 31;
-  const uint32_t lo = (j >= 0 && j < words) ? w[j] : 0u;
-  const uint32_t hi = (s != 0 && j + 1 >= 0 && j + 1 < words) ? w[j + 1] : 0u;
-  return s ? (lo >> s) | (hi << (32 - s)) : lo;
-}
 
 template <int S, int THREADS>
 __global__ __launch_bounds__(THREADS) void k_edt_plane(const uint32_t* __restrict__ bits, int D, int H, int W, int words, int of_clear,
@@ -91,7 +71,7 @@ __global__ __launch_bounds__(THREADS) void k_edt_plane(const uint32_t* __restric
     const int left = W - 32 * k;  // bits of this word inside the row
     uint32_t m = 0u;
     if (left > 0) {
-      m = edt_window(grid, words, f0 + h * W + 32 * k);
+      m = voxel_window(grid, words, f0 + h * W + 32 * k);
       if (of_clear) m = ~m;
       if (left < 32) m &= (1u << left) - 1u;
     }
@@ -202,9 +182,9 @@ __global__ __launch_bounds__(256) void k_voxel_shell(const uint32_t* __restrict_
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
     const uint32_t* __restrict__ g = bits + (size_t)b * words;
     // a neighbour counts only where it lies inside the grid, so no padding bit is ever looked at
-    const uint32_t inner = (edt_window(g, words, f0 - 1) & w_lo) & (edt_window(g, words, f0 + 1) & w_hi) &
-                           (edt_window(g, words, f0 - W) & h_lo) & (edt_window(g, words, f0 + W) & h_hi) &
-                           (edt_window(g, words, f0 - HW) & d_lo) & (edt_window(g, words, f0 + HW) & d_hi);
+    const uint32_t inner = (voxel_window(g, words, f0 - 1) & w_lo) & (voxel_window(g, words, f0 + 1) & w_hi) &
+                           (voxel_window(g, words, f0 - W) & h_lo) & (voxel_window(g, words, f0 + W) & h_hi) &
+                           (voxel_window(g, words, f0 - HW) & d_lo) & (voxel_window(g, words, f0 + HW) & d_hi);
     out[(size_t)b * words + j] = g[j] & valid & ~inner;
   }
 }
@@ -215,20 +195,6 @@ static_assert(32 % kEdtStatsBurst == 0, "whole bursts in a round of 64 words");
 struct EdtThresholds {
   int32_t t[DPC_VOXEL_EDT_MAX_THRESHOLDS];
 };
-
-// the sum of v over the workgroup in thread 0 (wave sums by shuffles, then the waves in order); scratch: 4 values
-__device__ inline long long edt_block_sum(long long v, long long* scratch) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  if (lane == 0) scratch[wave] = v;
-  __syncthreads();
-  long long s = 0;
-  if (t == 0)
-    for (int w = 0; w < 4; ++w) s += scratch[w];
-  __syncthreads();
-  return s;
-}
 
 __global__ __launch_bounds__(256) void k_voxel_edt_stats(const int32_t* __restrict__ sq, int n_fields, const uint32_t* __restrict__ bits,
                                                          int n_grids, int V, int words, const int32_t* __restrict__ pair_desc,
@@ -251,8 +217,7 @@ __global__ __launch_bounds__(256) void k_voxel_edt_stats(const int32_t* __restri
   const int lane = t & 63, wave = t >> 6;
   for (int j0 = 64 * wave; j0 < words; j0 += 256) {  // a wave takes 64 words a round, a word a lane: the same trips in every lane
     const int j = j0 + lane;
-    uint32_t mine = j < words ? g[j] : 0u;
-    if (j == words - 1 && (V & 31)) mine &= (1u << (V & 31)) - 1u;  // a padding bit is not a voxel
+    const uint32_t mine = voxel_clear_padding(j < words ? g[j] : 0u, j, words, V);  // a padding bit is not a voxel
     n += __popc(mine);
     const unsigned long long some = __ballot(mine != 0u);
     for (int i0 = 0; i0 < 32; i0 += kEdtStatsBurst) {  // words 2 i and 2 i + 1 of the round are 64 consecutive voxels, a lane each
@@ -276,7 +241,8 @@ __global__ __launch_bounds__(256) void k_voxel_edt_stats(const int32_t* __restri
     }
   }
   long long* row = out + (size_t)(3 + K) * blockIdx.x;
-  const long long s_n = edt_block_sum(n, scratch), s_reached = edt_block_sum(reached, scratch), s_sum = edt_block_sum(sum, scratch);
+  const long long s_n = block_sum<256, long long>((long long)n, scratch), s_reached = block_sum<256, long long>((long long)reached, scratch),
+                  s_sum = block_sum<256, long long>(sum, scratch);
   if (t == 0) {
     row[0] = s_n;
     row[1] = s_reached;
@@ -284,25 +250,25 @@ __global__ __launch_bounds__(256) void k_voxel_edt_stats(const int32_t* __restri
   }
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) {
-    if (k < K) {  // the same in every thread: edt_block_sum has barriers
-      const long long s = edt_block_sum(within[k], scratch);
+    if (k < K) {  // the same in every thread: block_sum has barriers
+      const long long s = block_sum<256, long long>((long long)within[k], scratch);
       if (t == 0) row[3 + k] = s;
     }
   }
 }
 
 template <int S, int THREADS>
-int edt_plane(const uint32_t* bits, int B, const EdtGrid& g, int of_clear, int32_t* sq, hipStream_t st) {
+int edt_plane(const uint32_t* bits, int B, const VoxelGrid& g, int of_clear, int32_t* sq, hipStream_t st) {
   DPC_LAUNCH("k_edt_plane", dpc_kid("k_edt_plane", S, THREADS), (k_edt_plane<S, THREADS>), dim3((unsigned)B * (unsigned)g.D),
              dim3(THREADS), 0, st, bits, g.D, g.H, g.W, g.words, of_clear, sq);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 template <int S>
-int edt_depth(int B, const EdtGrid& g, int tiles, int32_t* sq, hipStream_t st) {
+int edt_depth(int B, const VoxelGrid& g, int tiles, int32_t* sq, hipStream_t st) {
   DPC_LAUNCH("k_edt_depth", dpc_kid("k_edt_depth", S), (k_edt_depth<S>), dim3((unsigned)B * (unsigned)tiles), dim3(256), 0, st, g.D,
              g.H * g.W, tiles, sq);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // namespace
@@ -310,8 +276,8 @@ int edt_depth(int B, const EdtGrid& g, int tiles, int32_t* sq, hipStream_t st) {
 extern "C" {
 
 int dpc_voxel_edt(const uint32_t* bits, int B, int D, int H, int W, int of_clear, int32_t* sq, void* stream) {
-  EdtGrid g;
-  if (B < 0 || !edt_grid(D, H, W, &g)) return DPC_ERR_SHAPE;
+  VoxelGrid g;
+  if (B < 0 || !voxel_grid(D, H, W, 1, &g)) return DPC_ERR_SHAPE;
   const int tiles = (g.H * g.W + kEdtCols - 1) / kEdtCols;
   if ((int64_t)B * g.D > INT32_MAX || (int64_t)B * tiles > INT32_MAX) return DPC_ERR_SHAPE;
   if (B == 0) return DPC_OK;
@@ -332,22 +298,22 @@ int dpc_voxel_edt(const uint32_t* bits, int B, int D, int H, int W, int of_clear
 }
 
 int dpc_voxel_shell(const uint32_t* bits, int B, int D, int H, int W, uint32_t* out, void* stream) {
-  EdtGrid g;
-  if (B < 0 || !edt_grid(D, H, W, &g)) return DPC_ERR_SHAPE;
+  VoxelGrid g;
+  if (B < 0 || !voxel_grid(D, H, W, 1, &g)) return DPC_ERR_SHAPE;
   if (B == 0) return DPC_OK;
   if (!bits || !out) return DPC_ERR_NULL;
   if (out == bits) return DPC_ERR_SHAPE;  // a word's neighbours are read after other words have been written
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)((g.words + 255) / 256), (unsigned)(B < 65535 ? B : 65535));
   DPC_LAUNCH("k_voxel_shell", dpc_kid("k_voxel_shell"), k_voxel_shell, grid, dim3(256), 0, st, bits, B, g.D, g.H, g.W, g.V, g.words, out);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 int dpc_voxel_edt_stats(const int32_t* sq, int n_fields, const uint32_t* bits, int n_grids, int D, int H, int W,
                         const int32_t* pair_desc, const int32_t* host_pair_desc, int pairs, const int32_t* host_thresholds_sq, int K,
                         int64_t* out, int32_t* status, void* stream) {
-  EdtGrid g;
-  if (n_fields < 0 || n_grids < 0 || pairs < 0 || !edt_grid(D, H, W, &g)) return DPC_ERR_SHAPE;
+  VoxelGrid g;
+  if (n_fields < 0 || n_grids < 0 || pairs < 0 || !voxel_grid(D, H, W, 1, &g)) return DPC_ERR_SHAPE;
   if (K < 0 || K > DPC_VOXEL_EDT_MAX_THRESHOLDS) return DPC_ERR_SHAPE;
   if ((K > 0 && !host_thresholds_sq) || (pairs > 0 && !host_pair_desc)) return DPC_ERR_NULL;
   EdtThresholds thr = {};
@@ -355,16 +321,14 @@ int dpc_voxel_edt_stats(const int32_t* sq, int n_fields, const uint32_t* bits, i
     if (host_thresholds_sq[k] < 0 || host_thresholds_sq[k] >= DPC_VOXEL_EDT_NONE) return DPC_ERR_SHAPE;
     thr.t[k] = host_thresholds_sq[k];
   }
-  for (int p = 0; p < pairs; ++p) {
-    const int32_t fi = host_pair_desc[2 * (int64_t)p], gi = host_pair_desc[2 * (int64_t)p + 1];
-    if (fi < 0 || fi >= n_fields || gi < 0 || gi >= n_grids) return DPC_ERR_SHAPE;
-  }
+  const int rc = check_pairs(host_pair_desc, pairs, n_fields, n_grids);
+  if (rc != DPC_OK) return rc;
   if (pairs == 0) return DPC_OK;
   if (!sq || !bits || !pair_desc || !out) return DPC_ERR_NULL;
   hipStream_t st = (hipStream_t)stream;
   DPC_LAUNCH("k_voxel_edt_stats", dpc_kid("k_voxel_edt_stats"), k_voxel_edt_stats, dim3((unsigned)pairs), dim3(256), 0, st, sq, n_fields,
              bits, n_grids, g.V, g.words, pair_desc, thr, K, reinterpret_cast<long long*>(out), status);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // extern "C"

@@ -24,14 +24,14 @@
 // Nothing waits on another workgroup; every loop is bounded by a host-checked size or a checked table entry.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <climits>
 #include <cstdint>
 #include <type_traits>
 
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
+#include "dpc_voxel_bits.h"
 
 namespace {
 
@@ -44,41 +44,6 @@ static_assert((int64_t)DPC_VOXEL_MAX_SIDE * DPC_VOXEL_MAX_SIDE * DPC_VOXEL_MAX_S
 constexpr int vx_class(int64_t words) { return words <= kVxWords[0] ? 0 : words <= kVxWords[1] ? 1 : 2; }
 static_assert(vx_class(32 * 32 * 32 / 32) == 0 && vx_class(32 * 32 * 32 / 32 + 1) == 1 && vx_class(64 * 64 * 64 / 32) == 1 &&
                   vx_class(64 * 64 * 64 / 32 + 1) == 2, "32^3 is the largest grid of class 0, 64^3 of class 1");
-
-struct VxGrid {
-  int D, H, W, V, words;
-};
-
-// 1 <= D, H, W <= DPC_VOXEL_MAX_SIDE
-bool vx_grid(int D, int H, int W, VxGrid* g) {
-  if (D < 1 || H < 1 || W < 1 || D > DPC_VOXEL_MAX_SIDE || H > DPC_VOXEL_MAX_SIDE || W > DPC_VOXEL_MAX_SIDE) return false;
-  g->D = D; g->H = H; g->W = W;
-  g->V = D * H * W;
-  g->words = (g->V + 31) / 32;
-  return true;
-}
-
-// word j of a bit grid of V voxels, its padding bits cleared whatever the caller left there
-__device__ inline uint32_t vx_word(const uint32_t* __restrict__ w, int j, int words, int V) {
-  uint32_t m = w[j];
-  if (j == words - 1 && (V & 31)) m &= (1u << (V & 31)) - 1u;
-  return m;
-}
-
-// the sum of v over the workgroup in thread 0 (wave sums by shuffles, then the waves in order); scratch: THREADS / 64 ints
-template <int THREADS>
-__device__ inline long long vx_block_sum(int v, int* scratch) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  if (lane == 0) scratch[wave] = v;
-  __syncthreads();
-  long long s = 0;
-  if (t == 0)
-    for (int w = 0; w < THREADS / 64; ++w) s += scratch[w];
-  __syncthreads();
-  return s;
-}
 
 // the node of coordinate a on an axis of G nodes; a is inside [-0.5, 0.5]
 __device__ inline int vx_node(double a, int G) {
@@ -206,14 +171,14 @@ __global__ __launch_bounds__(256) void k_voxel_stats(const uint32_t* __restrict_
   int both = 0, fp = 0, fn = 0;
 #pragma unroll 4
   for (int j = t; j < words; j += 256) {
-    const uint32_t a = vx_word(p, j, words, V), b = vx_word(g, j, words, V);
+    const uint32_t a = voxel_word(p, j, words, V), b = voxel_word(g, j, words, V);
     both += __popc(a & b);
     fp += __popc(a & ~b);
     fn += __popc(~a & b);
   }
-  const long long s_both = vx_block_sum<256>(both, scratch);
-  const long long s_fp = vx_block_sum<256>(fp, scratch);
-  const long long s_fn = vx_block_sum<256>(fn, scratch);
+  const long long s_both = block_sum<256, long long>(both, scratch);
+  const long long s_fp = block_sum<256, long long>(fp, scratch);
+  const long long s_fn = block_sum<256, long long>(fn, scratch);
   if (t == 0) {
     long long* row = stats + 5 * (size_t)blockIdx.x;
     row[0] = s_fp + s_fn;           // diff = popcount(p ^ g)
@@ -229,8 +194,8 @@ __global__ __launch_bounds__(256) void k_voxel_count(const uint32_t* __restrict_
   const uint32_t* w = bits + (size_t)blockIdx.x * words;
   int n = 0;
 #pragma unroll 4
-  for (int j = threadIdx.x; j < words; j += 256) n += __popc(vx_word(w, j, words, V));
-  const long long s = vx_block_sum<256>(n, scratch);
+  for (int j = threadIdx.x; j < words; j += 256) n += __popc(voxel_word(w, j, words, V));
+  const long long s = block_sum<256, long long>(n, scratch);
   if (threadIdx.x == 0) counts[blockIdx.x] = (int32_t)s;
 }
 
@@ -250,7 +215,7 @@ __global__ __launch_bounds__(256) void k_voxel2pc(const uint32_t* __restrict__ b
   int base = 0;
   for (int j0 = 0; j0 < words; j0 += 256) {  // the same trip count in every thread: block_scan has barriers
     const int j = j0 + t;
-    uint32_t m = j < words ? vx_word(w, j, words, V) : 0u;
+    uint32_t m = j < words ? voxel_word(w, j, words, V) : 0u;
     int excl;
     const int total = block_scan<256>((int)__popc(m), &excl, scratch);
     int o = base + excl;
@@ -274,32 +239,23 @@ __global__ __launch_bounds__(256) void k_voxel2pc(const uint32_t* __restrict__ b
 }
 
 template <int F64, int CLS>
-int vx_launch(const void* pts, int n_pts, const int32_t* desc, int clouds, const VxGrid& g, uint32_t* bits, int32_t* dropped,
+int vx_launch(const void* pts, int n_pts, const int32_t* desc, int clouds, const VoxelGrid& g, uint32_t* bits, int32_t* dropped,
               int32_t* status, hipStream_t st) {
   constexpr int WORDS = kVxWords[CLS], THREADS = kVxThreads[CLS];
   constexpr size_t lds = sizeof(uint32_t) * (WORDS + kVxExtra);
   static_assert(lds <= 80 * 1024, "two workgroups share the CU's 160 KiB of LDS");
-  if (lds > 64 * 1024) {  // more dynamic LDS than the default limit: raised once per kernel and device
-    static std::atomic<int> raised[16];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return DPC_ERR_LAUNCH;
-    const bool tracked = dev >= 0 && dev < 16;
-    if (!(tracked && raised[dev].load(std::memory_order_relaxed))) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_voxelise<F64, WORDS, THREADS>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return DPC_ERR_LAUNCH;
-      if (tracked) raised[dev].store(1, std::memory_order_relaxed);
-    }
-  }
+  static LdsLimit limit;
+  const int rc = set_lds(k_voxelise<F64, WORDS, THREADS>, lds, limit);
+  if (rc != DPC_OK) return rc;
   const int slabs = (g.words + WORDS - 1) / WORDS;
   DPC_LAUNCH("k_voxelise", dpc_kid("k_voxelise", F64, WORDS, THREADS), (k_voxelise<F64, WORDS, THREADS>),
              dim3((unsigned)clouds * (unsigned)slabs), dim3(THREADS), lds, st, pts, n_pts, desc, slabs, g.D, g.H, g.W, g.words, bits,
              dropped, status);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 template <int F64>
-int vx_run(const void* pts, int n_pts, const int32_t* desc, int clouds, const VxGrid& g, uint32_t* bits, int32_t* dropped,
+int vx_run(const void* pts, int n_pts, const int32_t* desc, int clouds, const VoxelGrid& g, uint32_t* bits, int32_t* dropped,
            int32_t* status, hipStream_t st) {
   switch (vx_class(g.words)) {
     case 0: return vx_launch<F64, 0>(pts, n_pts, desc, clouds, g, bits, dropped, status, st);
@@ -309,12 +265,12 @@ int vx_run(const void* pts, int n_pts, const int32_t* desc, int clouds, const Vx
 }
 
 template <int DT>
-int vx_threshold(const void* grids, int B, const VxGrid& g, double threshold, int inclusive, uint32_t* bits, hipStream_t st) {
+int vx_threshold(const void* grids, int B, const VoxelGrid& g, double threshold, int inclusive, uint32_t* bits, hipStream_t st) {
   const int nchunk = (g.V + 63) / 64;
   const dim3 grid((unsigned)((nchunk + 4 * kVxChunks - 1) / (4 * kVxChunks)), (unsigned)(B < 65535 ? B : 65535));
   DPC_LAUNCH("k_voxel_threshold", dpc_kid("k_voxel_threshold", DT), (k_voxel_threshold<DT>), grid, dim3(256), 0, st, grids, B, g.V,
              g.words, threshold, inclusive, bits);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // namespace
@@ -323,8 +279,8 @@ extern "C" {
 
 int dpc_voxelise(const void* pts, int n_pts, int is_f64, const int32_t* cloud_desc, const int32_t* host_cloud_desc, int clouds,
                  int D, int H, int W, uint32_t* bits, int32_t* dropped, int32_t* status, void* stream) {
-  VxGrid g;
-  if (n_pts < 0 || clouds < 0 || !vx_grid(D, H, W, &g)) return DPC_ERR_SHAPE;
+  VoxelGrid g;
+  if (n_pts < 0 || clouds < 0 || !voxel_grid(D, H, W, 1, &g)) return DPC_ERR_SHAPE;
   if (clouds > 0 && !host_cloud_desc) return DPC_ERR_NULL;
   const int64_t len[1] = {n_pts};
   const int rc = check_desc<2, 1>(host_cloud_desc, clouds, len, INT32_MAX, nullptr, [](const int32_t*) { return true; });
@@ -340,8 +296,8 @@ int dpc_voxelise(const void* pts, int n_pts, int is_f64, const int32_t* cloud_de
 
 int dpc_voxel_threshold(const void* grids, int dtype, int B, int D, int H, int W, double threshold, int inclusive, uint32_t* bits,
                         void* stream) {
-  VxGrid g;
-  if (B < 0 || dtype < 0 || dtype > 2 || !vx_grid(D, H, W, &g)) return DPC_ERR_SHAPE;
+  VoxelGrid g;
+  if (B < 0 || dtype < 0 || dtype > 2 || !voxel_grid(D, H, W, 1, &g)) return DPC_ERR_SHAPE;
   if (B == 0) return DPC_OK;
   if (!grids || !bits) return DPC_ERR_NULL;
   hipStream_t st = (hipStream_t)stream;
@@ -351,49 +307,47 @@ int dpc_voxel_threshold(const void* grids, int dtype, int B, int D, int H, int W
 }
 
 int dpc_voxel_unpack(const uint32_t* bits, int B, int D, int H, int W, uint8_t* out, void* stream) {
-  VxGrid g;
-  if (B < 0 || !vx_grid(D, H, W, &g)) return DPC_ERR_SHAPE;
+  VoxelGrid g;
+  if (B < 0 || !voxel_grid(D, H, W, 1, &g)) return DPC_ERR_SHAPE;
   if (B == 0) return DPC_OK;
   if (!bits || !out) return DPC_ERR_NULL;
   hipStream_t st = (hipStream_t)stream;
   if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return DPC_ERR_SHAPE;  // the four-voxel stores need it
   const dim3 grid((unsigned)((g.V + 1023) / 1024), (unsigned)(B < 65535 ? B : 65535));
   DPC_LAUNCH("k_voxel_unpack", dpc_kid("k_voxel_unpack"), k_voxel_unpack, grid, dim3(256), 0, st, bits, B, g.V, g.words, out);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 int dpc_voxel_stats(const uint32_t* pred_bits, int n_pred, const uint32_t* gt_bits, int n_gt, int D, int H, int W,
                     const int32_t* pair_desc, const int32_t* host_pair_desc, int pairs, int64_t* stats, int32_t* status,
                     void* stream) {
-  VxGrid g;
-  if (n_pred < 0 || n_gt < 0 || pairs < 0 || !vx_grid(D, H, W, &g)) return DPC_ERR_SHAPE;
+  VoxelGrid g;
+  if (n_pred < 0 || n_gt < 0 || pairs < 0 || !voxel_grid(D, H, W, 1, &g)) return DPC_ERR_SHAPE;
   if (pairs > 0 && !host_pair_desc) return DPC_ERR_NULL;
-  for (int p = 0; p < pairs; ++p) {
-    const int32_t pi = host_pair_desc[2 * (int64_t)p], gi = host_pair_desc[2 * (int64_t)p + 1];
-    if (pi < 0 || pi >= n_pred || gi < 0 || gi >= n_gt) return DPC_ERR_SHAPE;
-  }
+  const int rc = check_pairs(host_pair_desc, pairs, n_pred, n_gt);
+  if (rc != DPC_OK) return rc;
   if (pairs == 0) return DPC_OK;
   if (!pred_bits || !gt_bits || !pair_desc || !stats) return DPC_ERR_NULL;
   hipStream_t st = (hipStream_t)stream;
   DPC_LAUNCH("k_voxel_stats", dpc_kid("k_voxel_stats"), k_voxel_stats, dim3((unsigned)pairs), dim3(256), 0, st, pred_bits, n_pred,
              gt_bits, n_gt, g.V, g.words, pair_desc, reinterpret_cast<long long*>(stats), status);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 int dpc_voxel_count(const uint32_t* bits, int B, int D, int H, int W, int32_t* counts, void* stream) {
-  VxGrid g;
-  if (B < 0 || !vx_grid(D, H, W, &g)) return DPC_ERR_SHAPE;
+  VoxelGrid g;
+  if (B < 0 || !voxel_grid(D, H, W, 1, &g)) return DPC_ERR_SHAPE;
   if (B == 0) return DPC_OK;
   if (!bits || !counts) return DPC_ERR_NULL;
   hipStream_t st = (hipStream_t)stream;
   DPC_LAUNCH("k_voxel_count", dpc_kid("k_voxel_count"), k_voxel_count, dim3((unsigned)B), dim3(256), 0, st, bits, g.V, g.words, counts);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 int dpc_voxel2pc(const uint32_t* bits, int B, int G, const int32_t* out_desc, const int32_t* host_out_desc, int n_out, double* xyz,
                  int32_t* status, void* stream) {
-  VxGrid g;
-  if (B < 0 || n_out < 0 || G < 2 || !vx_grid(G, G, G, &g)) return DPC_ERR_SHAPE;  // linspace over one node divides by zero
+  VoxelGrid g;
+  if (B < 0 || n_out < 0 || G < 2 || !voxel_grid(G, G, G, 1, &g)) return DPC_ERR_SHAPE;  // linspace over one node divides by zero
   if (B > 0 && !host_out_desc) return DPC_ERR_NULL;
   int64_t end = 0;
   for (int b = 0; b < B; ++b) {  // output ranges ascend without overlap, inside [0, n_out), none longer than a grid
@@ -406,7 +360,7 @@ int dpc_voxel2pc(const uint32_t* bits, int B, int G, const int32_t* out_desc, co
   hipStream_t st = (hipStream_t)stream;
   DPC_LAUNCH("k_voxel2pc", dpc_kid("k_voxel2pc"), k_voxel2pc, dim3((unsigned)B), dim3(256), 0, st, bits, G, g.V, g.words, out_desc,
              n_out, xyz, status);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // extern "C"

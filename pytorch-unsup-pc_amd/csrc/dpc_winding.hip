@@ -30,7 +30,8 @@
 #include "../../include/dpc_render.h"
 #include "dpc_batch.h"
 #include "dpc_point_mesh.h"
-#include "dpc_profile.h"
+#include "dpc_launch.h"
+#include "dpc_voxel_bits.h"
 
 namespace {
 
@@ -143,13 +144,12 @@ int wn_launch(const void* pts, int n_pts, const void* verts, int n_verts, const 
              n_pts, verts, n_verts, faces, n_faces, desc, pairs, g.chunk, w, (int)slots, status);
   DPC_LAUNCH("k_wn_finish", dpc_kid("k_wn_finish", PF64), (k_wn_finish<PF64>), dim3((unsigned)((g.points + kPmOutBlock - 1) / kPmOutBlock)),
              dim3(kPmOutBlock), 0, st, pts, n_pts, n_verts, n_faces, desc, pairs, g.chunk, w, (int)slots, (int)g.points, sums, winding);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // grids
-struct WvGeom {
-  int D, H, W, V, words;
+struct WvGeom : VoxelGrid {
   int nb;           // blocks of nodes of one grid
   int chunk, ncmax; // faces per chunk, chunks of the mesh with the most faces
   int64_t work, slots;
@@ -158,8 +158,9 @@ struct WvGeom {
 // the checks of both grid entry points: DPC_OK with the geometry, or the code to return
 int wv_plan(int n_verts, int n_faces, const int32_t* host_mesh_desc, int meshes, int D, int H, int W, WvGeom* g) {
   if (n_verts < 0 || n_faces < 0 || meshes < 0) return DPC_ERR_SHAPE;
-  if (D < 2 || H < 2 || W < 2 || D > DPC_VOXEL_MAX_SIDE || H > DPC_VOXEL_MAX_SIDE || W > DPC_VOXEL_MAX_SIDE) return DPC_ERR_SHAPE;
-  *g = WvGeom{D, H, W, D * H * W, (D * H * W + 31) / 32, pm_blocks(D * H * W), kPmTile * DPC_PM_CHUNK_TILES, 0, 0, 0};
+  VoxelGrid v;
+  if (!voxel_grid(D, H, W, 2, &v)) return DPC_ERR_SHAPE;
+  *g = WvGeom{v, pm_blocks(v.V), kPmTile * DPC_PM_CHUNK_TILES, 0, 0, 0};
   if (meshes == 0) return DPC_OK;
   if (!host_mesh_desc) return DPC_ERR_NULL;
   const int64_t len[2] = {n_verts, n_faces};
@@ -241,7 +242,7 @@ int wv_launch(const void* verts, int n_verts, const int32_t* faces, int n_faces,
                faces, n_faces, desc, meshes, g.D, g.H, g.W, g.nb, g.chunk, g.ncmax, part, status);
   DPC_LAUNCH("k_wn_vox_finish", dpc_kid("k_wn_vox_finish"), k_wn_vox_finish, dim3((unsigned)(meshes * g.nb)), dim3(kPmBlock), 0, st, desc,
              n_verts, n_faces, meshes, g.V, g.words, g.nb, g.chunk, g.ncmax, part, threshold_q, bits, status);
-  return hipGetLastError() == hipSuccess ? DPC_OK : DPC_ERR_LAUNCH;
+  return launch_ok();
 }
 
 }  // namespace
